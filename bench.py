@@ -8,9 +8,14 @@ already resident in HBM (device-pointer entry of the C ABI); for N > 1 the step 
 all-gather of the packed flux/heating-rate block that reassembles the outputs on every rank (north_star).
 One JSON line is printed by rank 0.
 
-Extra objects in the line:
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step).  --dump-outputs DIR then writes
+what the last timed step computed: every output array (uflx, dflx, uflxc, dflxc [, duflx_dt, duflxc_dt], hr, hrc) as
+DIR/<name>.npy, float64 of shape (columns, levels), on a fixed seeded sample of the columns that keeps the files below 64 MB.
+
+--full adds the secondary measurements, each after the timed steps (the CPU baseline before the GPU is touched):
   roofline      HBM roofline of the PATH: algorithmic bytes of a step (33.0 KB per 72-layer column, SURVEY.md 8d, x columns per rank)
-                / the summed kernel time of the step, measured live with HIP events on the launch stream.  The dominant kernel
+                / the summed kernel time of the step, measured with HIP events on the launch stream in a second pass of K steps
+                (the events stay out of the timed steps that give `value`).  The dominant kernel
                 (largest total time) is reported inside it with ITS time share of those bytes - the whole column's bytes are not
                 attributed to one kernel - and the PMC-measured HBM traffic per launch where a summary is committed under profiles/.
   compute       the instruction side ("so that the low HBM fraction is explained rather than hidden"): vector
@@ -20,6 +25,7 @@ Extra objects in the line:
   path          per-kernel milliseconds of a step.
   cpu_baseline  the reference's own Fortran (oracle/_ref, "reference") or the C port ("port") on the host cores,
                 measured before the GPU is touched, rank 0 at N=1 only.
+  end_to_end    the host-pointer entry (PCIe-inclusive) on --host-cols columns, rank 0 at N=1 only.
 """
 import argparse
 import ctypes
@@ -35,6 +41,8 @@ ALGO_BYTES_PER_COL_72 = 33.0e3      # 29.5 KB in + 3.5 KB out pe
 HBM_PEAK_GBS = 8000.0               # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable)
 VALU_PEAK_LANE_INSTR = 256 * 4 * 32 * 2.4e9      # 78.6e12: 256 CUs x 4 SIMDs x 32 lanes per clock x 2.4 GHz (f32-class; f64 issues at half of it)
 LDS_PEAK_BYTES = 150e12             # MI355X_MICROARCH.md, LDS: ~150 TB/s aggregate for ds_read_b64 / b128
+DUMP_BYTES = 48 << 20               # --dump-outputs: bytes of the column sample (kept below 64 MB in all)
+DUMP_SEED = 20240607
 
 
 def algo_bytes_per_col(nlay, idrv):
@@ -77,7 +85,12 @@ def main():
     ap.add_argument("--n1-prototype", action="store_true",
                     help="measurement only: cloud-free calls through the one-column-per-wavefront prototype k_n1 (profiles/round2_n1_expf.md)")
     ap.add_argument("--host-cols", type=int, default=131072,
-                    help="columns of the end-to-end (host-pointer, PCIe-inclusive) measurement after the timed region; 0 = skip")
+                    help="columns of the end-to-end (host-pointer, PCIe-inclusive) measurement after the timed region (--full); 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the per-kernel path / roofline / compute figures (a profiled pass of its own) and the "
+                         "host-pointer end to end; a plain run measures the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (float64, a fixed seeded column sample)")
     args = ap.parse_args()
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # (dmabuf IPC: what RCCL needs on this pool; already exported by the image)
@@ -91,7 +104,7 @@ def main():
 
     # ---- CPU baseline first: worker processes are spawned, which must happen before this process touches the GPU
     cpu, cpu_sample = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle.cpu_baseline import measure
         cpu = measure(nlay=args.nlay, config=args.config, cols_per_core=args.cpu_cols_per_core, sample_cols=0 if args.mcica else 256)
         cpu.pop("wall_s", None)
@@ -207,26 +220,52 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    def timed_steps():
+        """wall seconds of args.steps steps (the slowest rank's)"""
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        drain()                                  # every all-gather of the timed steps completes inside the timed region
+        barrier()
+        dt = time.perf_counter() - t0
+        api.check(stream)
+        if use_dist:
+            t = torch.tensor([dt], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t.item())
+        return dt
+
+    dt = timed_steps()
+
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs as a caller receives them: (columns, levels) per array, the gathered block's global columns
+        # where the step gathers, this rank's block otherwise; a fixed seeded column sample bounds the files to DUMP_BYTES
+        import numpy as np
+        k = (sharded.count - 1) & 1
+        navail = args.ncol if do_gather else ncol
+        n = min(navail, DUMP_BYTES // (8 * sharded.rows))
+        cols = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(navail, n, replace=False))).to(dev)
+        if do_gather:
+            blk = sharded.gathered[k].view(world, sharded.rows, per)[cols // per, :, cols % per].T
+        else:
+            blk = sharded.outbufs[k][:, cols]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for nm, a in output_views(blk.cpu().numpy(), nlay, idrv).items():
+            np.save(os.path.join(args.dump_outputs, nm + ".npy"), np.ascontiguousarray(a.T, dtype=np.float64))
+
+    # ---- per-kernel HIP-event times (roofline / path / compute) in a pass of their own, so that the events stay out of `value`
     buf = ctypes.create_string_buffer(1 << 16)
-    barrier()
-    api.lib().rrtmg_lw_hip_profile_begin()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    drain()                                  # every all-gather of the timed steps completes inside the timed region
-    barrier()
-    dt = time.perf_counter() - t0
-    api.lib().rrtmg_lw_hip_profile_end(buf, len(buf))
-    api.check(stream)
-    if use_dist:
-        t = torch.tensor([dt], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
+    dt_prof = None
+    if args.full:
+        api.lib().rrtmg_lw_hip_profile_begin()
+        dt_prof = timed_steps()
+        api.lib().rrtmg_lw_hip_profile_end(buf, len(buf))
 
     # ---- end to end through the host-pointer entry (what the Fortran shim calls): pageable host arrays in, H2D staging,
     # kernels, D2H, host arrays out.  Reported beside `value`, never as `value` (SURVEY.md 8d).
     e2e = None
-    if rank == 0 and world == 1 and args.host_cols > 0 and not args.mcica:
+    if args.full and rank == 0 and world == 1 and args.host_cols > 0 and not args.mcica:
         import numpy as np
         nh = min(args.host_cols, args.ncol)
 
@@ -315,10 +354,10 @@ def main():
         path = None
         compute = None
         if kern:
-            ktot = sum(v[1] for v in kern.values())                 # summed kernel milliseconds of the timed steps (this rank)
-            # the path's time: the summed kernel time, or the wall time of the timed region where that is shorter (the sweep launches of
+            ktot = sum(v[1] for v in kern.values())                 # summed kernel milliseconds of the profiled steps (this rank)
+            # the path's time: the summed kernel time, or the wall time of the profiled pass where that is shorter (the sweep launches of
             # the four band groups run on four streams and the per-column kernels on a fifth: their HIP-event times overlap)
-            tpath = min(ktot, 1e3 * dt)
+            tpath = min(ktot, 1e3 * dt_prof)
             pach = bpc * ncol * args.steps / (tpath * 1e-3) / 1e9
             # dominant kernel of the critical path: k_colprep / k_cloudscan / k_cloudlay run on the auxiliary stream underneath the previous
             # batch's k_layer / sweeps (driver.hip: run_pipelined) and are left out of the choice
@@ -395,8 +434,9 @@ def main():
                                gather="rccl all_gather_into_tensor of the packed outputs, overlapped with the next step's kernels" if do_gather else "none",
                                kdata="stand-in (real k-data absent from the reference mount)" if api.kdata_is_standin() else "real",
                                sweeps="k_n1 prototype (measurement)" if args.n1_prototype else "production"),
-                   workspace_GB=round(api.workspace_bytes() / 1e9, 3),
-                   roofline=roof, compute=compute, path=path, cpu_baseline=cpu, end_to_end=e2e)
+                   workspace_GB=round(api.workspace_bytes() / 1e9, 3))
+        if args.full:
+            res.update(roofline=roof, compute=compute, path=path, cpu_baseline=cpu, end_to_end=e2e)
         print(json.dumps(res))
     if use_dist:
         dist.destroy_process_group()

@@ -7,7 +7,7 @@ out=gpurun_out/$tag.txt
 for rep in 1 2; do
 for lib in "$@"; do
     echo "== $lib rep $rep $BENCH_ARGS" | tee -a $out
-    RRTMG_LW_HIP_LIB=$PWD/$lib RRTMG_LW_ALLOW_STANDIN=1 timeout -k 10 300 python bench.py --no-cpu-baseline --host-cols 0 --steps ${STEPS:-6} --warmup 2 --check $BENCH_ARGS 2>&1 | python -c "
+    RRTMG_LW_HIP_LIB=$PWD/$lib RRTMG_LW_ALLOW_STANDIN=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline --host-cols 0 --steps ${STEPS:-6} --warmup 2 --check $BENCH_ARGS 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('# check'): print(l.strip())

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 export RRTMG_LW_ALLOW_STANDIN=1
 for cfg in cloudy cloudy_towers cloudy_scatter cloudy_deep; do
-  timeout -k 10 400 python3 bench.py --config $cfg --steps 5 --warmup 1 --no-cpu-baseline --host-cols 0 > $O/bench_$cfg.json 2> $O/bench_$cfg.err || exit 1
+  timeout -k 10 400 python3 bench.py --full --config $cfg --steps 5 --warmup 1 --no-cpu-baseline --host-cols 0 > $O/bench_$cfg.json 2> $O/bench_$cfg.err || exit 1
   python3 - $cfg $O/bench_$cfg.json <<'PY'
 import sys, json
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ O=gpurun_out/${1:-r2_n1expf}.log
 export RRTMG_LW_ALLOW_STANDIN=1
 echo "== k_n1 correctness" >> $O
 timeout -k 10 300 python -m pytest tests/test_hip_parity.py -m gpu -q -k north_star >> $O 2>&1
-b() { timeout -k 10 300 python bench.py --no-cpu-baseline --host-cols 0 --steps 5 --warmup 1 --check "$@" 2>> $O | python -c "
+b() { timeout -k 10 300 python bench.py --full --no-cpu-baseline --host-cols 0 --steps 5 --warmup 1 --check "$@" 2>> $O | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -8,13 +8,13 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
 export RRTMG_LW_ALLOW_STANDIN=1
-python3 bench.py --steps 10 --warmup 2 > $O/bench_1e6.json 2> $O/bench_1e6.err
+python3 bench.py --full --steps 10 --warmup 2 > $O/bench_1e6.json 2> $O/bench_1e6.err
 echo "bench 1e6 done" ; tail -c 300 $O/bench_1e6.json
-python3 bench.py --steps 5 --warmup 1 --mcica 5 --no-cpu-baseline --host-cols 0 > $O/bench_1e6_mcica5.json 2> $O/bench_1e6_mcica5.err
-python3 bench.py --steps 5 --warmup 1 --config aer_idrv --nlay 137 --ncol 500000 --no-cpu-baseline --host-cols 0 > $O/bench_5e5_aer137.json 2> $O/bench_aer137.err
-python3 bench.py --steps 20 --warmup 5 --config clear --ncol 10000 --no-cpu-baseline --host-cols 0 > $O/bench_1e4_clear.json 2> $O/bench_1e4_clear.err
-python3 bench.py --steps 5 --warmup 1 --config clear --no-cpu-baseline --host-cols 0 > $O/bench_1e6_clear.json 2> $O/bench_1e6_clear.err
-python3 bench.py --steps 10 --warmup 2 --ncol 125000 --no-cpu-baseline --host-cols 0 > $O/bench_125000_rank_proxy.json 2> $O/bench_125000.err
+python3 bench.py --full --steps 5 --warmup 1 --mcica 5 --no-cpu-baseline --host-cols 0 > $O/bench_1e6_mcica5.json 2> $O/bench_1e6_mcica5.err
+python3 bench.py --full --steps 5 --warmup 1 --config aer_idrv --nlay 137 --ncol 500000 --no-cpu-baseline --host-cols 0 > $O/bench_5e5_aer137.json 2> $O/bench_aer137.err
+python3 bench.py --full --steps 20 --warmup 5 --config clear --ncol 10000 --no-cpu-baseline --host-cols 0 > $O/bench_1e4_clear.json 2> $O/bench_1e4_clear.err
+python3 bench.py --full --steps 5 --warmup 1 --config clear --no-cpu-baseline --host-cols 0 > $O/bench_1e6_clear.json 2> $O/bench_1e6_clear.err
+python3 bench.py --full --steps 10 --warmup 2 --ncol 125000 --no-cpu-baseline --host-cols 0 > $O/bench_125000_rank_proxy.json 2> $O/bench_125000.err
 echo "benches done"
 rocprofv3 --kernel-trace --stats -d $O/stats -f csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --host-cols 0 > $O/stats.log 2>&1
 echo "stats done"

@@ -6,14 +6,14 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 export RRTMG_LW_ALLOW_STANDIN=1
 B="--no-cpu-baseline --host-cols 0"
-python3 bench.py --steps 10 --warmup 2 > $O/bench_1e6.json 2> $O/bench_1e6.err || exit 1
+python3 bench.py --full --steps 10 --warmup 2 > $O/bench_1e6.json 2> $O/bench_1e6.err || exit 1
 echo "bench 1e6 done"; tail -c 200 $O/bench_1e6.json
-python3 bench.py --steps 5 --warmup 1 --mcica 5 $B > $O/bench_1e6_mcica5.json 2> $O/bench_1e6_mcica5.err || exit 1
-python3 bench.py --steps 5 --warmup 1 --config aer_idrv --nlay 137 --ncol 500000 $B > $O/bench_5e5_aer137.json 2> $O/bench_aer137.err || exit 1
-python3 bench.py --steps 20 --warmup 5 --config clear --ncol 10000 $B > $O/bench_1e4_clear.json 2> $O/bench_1e4_clear.err || exit 1
-python3 bench.py --steps 5 --warmup 1 --config clear $B > $O/bench_1e6_clear.json 2> $O/bench_1e6_clear.err || exit 1
-python3 bench.py --steps 10 --warmup 2 --ncol 125000 $B > $O/bench_125000_rank_proxy.json 2> $O/bench_125000.err || exit 1
-for cfg in cloudy_towers cloudy_scatter cloudy_deep; do python3 bench.py --config $cfg --steps 5 --warmup 1 $B > $O/bench_1e6_$cfg.json 2> $O/bench_$cfg.err || exit 1; done
+python3 bench.py --full --steps 5 --warmup 1 --mcica 5 $B > $O/bench_1e6_mcica5.json 2> $O/bench_1e6_mcica5.err || exit 1
+python3 bench.py --full --steps 5 --warmup 1 --config aer_idrv --nlay 137 --ncol 500000 $B > $O/bench_5e5_aer137.json 2> $O/bench_aer137.err || exit 1
+python3 bench.py --full --steps 20 --warmup 5 --config clear --ncol 10000 $B > $O/bench_1e4_clear.json 2> $O/bench_1e4_clear.err || exit 1
+python3 bench.py --full --steps 5 --warmup 1 --config clear $B > $O/bench_1e6_clear.json 2> $O/bench_1e6_clear.err || exit 1
+python3 bench.py --full --steps 10 --warmup 2 --ncol 125000 $B > $O/bench_125000_rank_proxy.json 2> $O/bench_125000.err || exit 1
+for cfg in cloudy_towers cloudy_scatter cloudy_deep; do python3 bench.py --full --config $cfg --steps 5 --warmup 1 $B > $O/bench_1e6_$cfg.json 2> $O/bench_$cfg.err || exit 1; done
 echo "benches done"
 rocprofv3 --kernel-trace --stats -d $O/stats -f csv -- python3 bench.py --steps 5 --warmup 2 $B > $O/stats.log 2>&1 || exit 1
 cp $O/stats/*/*_kernel_stats.csv $O/kernel_stats.csv

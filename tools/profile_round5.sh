@@ -30,17 +30,17 @@ if [ "$2" != "quick" ]; then
 fi
 # the bench lines below take `traffic` and `compute` from the passes just made
 cp $O/pmc_traffic.json profiles/pmc_traffic.json; cp $O/pmc_compute.json profiles/pmc_compute.json
-python3 bench.py --steps 10 --warmup 2 > $O/bench_1e6.json 2> $O/bench_1e6.err || exit 1
+python3 bench.py --full --steps 10 --warmup 2 > $O/bench_1e6.json 2> $O/bench_1e6.err || exit 1
 echo "bench 1e6 done"; tail -c 300 $O/bench_1e6.json
-python3 bench.py --steps 5 --warmup 1 --mcica 5 $B > $O/bench_1e6_mcica5.json 2> $O/bench_1e6_mcica5.err || exit 1
-python3 bench.py --steps 5 --warmup 1 --config aer_idrv --nlay 137 --ncol 500000 $B > $O/bench_5e5_aer137.json 2> $O/bench_aer137.err || exit 1
-python3 bench.py --steps 20 --warmup 5 --config clear --ncol 10000 $B > $O/bench_1e4_clear.json 2> $O/bench_1e4_clear.err || exit 1
-python3 bench.py --steps 5 --warmup 1 --config clear $B > $O/bench_1e6_clear.json 2> $O/bench_1e6_clear.err || exit 1
-python3 bench.py --steps 10 --warmup 2 --ncol 125000 $B > $O/bench_125000_rank_proxy.json 2> $O/bench_125000.err || exit 1
-for cfg in cloudy_towers cloudy_scatter cloudy_deep cloudy_orography; do python3 bench.py --config $cfg --steps 5 --warmup 1 $B > $O/bench_1e6_$cfg.json 2> $O/bench_$cfg.err || exit 1; done
+python3 bench.py --full --steps 5 --warmup 1 --mcica 5 $B > $O/bench_1e6_mcica5.json 2> $O/bench_1e6_mcica5.err || exit 1
+python3 bench.py --full --steps 5 --warmup 1 --config aer_idrv --nlay 137 --ncol 500000 $B > $O/bench_5e5_aer137.json 2> $O/bench_aer137.err || exit 1
+python3 bench.py --full --steps 20 --warmup 5 --config clear --ncol 10000 $B > $O/bench_1e4_clear.json 2> $O/bench_1e4_clear.err || exit 1
+python3 bench.py --full --steps 5 --warmup 1 --config clear $B > $O/bench_1e6_clear.json 2> $O/bench_1e6_clear.err || exit 1
+python3 bench.py --full --steps 10 --warmup 2 --ncol 125000 $B > $O/bench_125000_rank_proxy.json 2> $O/bench_125000.err || exit 1
+for cfg in cloudy_towers cloudy_scatter cloudy_deep cloudy_orography; do python3 bench.py --full --config $cfg --steps 5 --warmup 1 $B > $O/bench_1e6_$cfg.json 2> $O/bench_$cfg.err || exit 1; done
 echo "benches done"
 # the driver's multi-GPU command with one rank: RCCL initialised, the all-gather of the packed outputs in the timed region
-python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 5 --warmup 1 --force-gather $B > $O/bench_1e6_torchrun1.json 2> $O/bench_torchrun1.err || echo "torchrun rehearsal failed"
+python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 5 --warmup 1 --force-gather $B > $O/bench_1e6_torchrun1.json 2> $O/bench_torchrun1.err || echo "torchrun rehearsal failed"
 rocprofv3 --kernel-trace --stats -d $O/stats -f csv -- python3 bench.py --steps 5 --warmup 2 $B > $O/stats.log 2>&1 || exit 1
 cp $O/stats/*/*_kernel_stats.csv $O/kernel_stats.csv
 echo "stats done"

@@ -216,6 +216,81 @@ int rrtmg_lw_hip_run_mcica_subcol_device(
     double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
     double *duflx_dt, double *duflxc_dt, void *stream);
 
+/* Spectral (per-band) fluxes --------------------------------------------------------------------- */
+/* The six entries below take the argument list of the entry they are named after, followed by four more outputs (in the device entries
+ * in front of `stream`), and compute everything that entry computes - the broadband outputs bit for bit as it does - plus, per band:
+ *     uflxs, dflxs      total-sky upward / downward flux of each band     (ncol,nlay+1,16), required
+ *     uflxcs, dflxcs    clear-sky upward / downward flux of each band     (ncol,nlay+1,16), both NULL or both set
+ * Element (i, k, b), 0-based, lies at i + ncol*(k + (nlay+1)*b): columns fastest, level 0 at the surface, band last (a host that keeps
+ * band-first arrays, as CAM does, transposes).  The flux of band b at level k is the term the reference adds into totuflux(k) /
+ * totdflux(k) / totuclfl(k) / totdclfl(k) for that band, uflux(k) x delwave(b) x fluxfac (src/rrtmg_lw_rtrn.f90:549-562 and the same
+ * lines of rtrnmr / rtrnmc); summed over the 16 bands it gives uflx / dflx / uflxc / dflxc up to rounding.
+ * Band 16 is the band's share of a broadband call: its Planck function runs from 2600 cm-1 to infinity (src/rrtmg_lw_setcoef.f90:228-252).
+ * It is NOT the column driver's IOUT = 16 / 99 output, which uses the 2600-3250 cm-1 table (rrtmg_lw_hip_run_columns with istart = 16).
+ * Heating rates and d(flux)/dT stay broadband (duflx_dt / duflxc_dt as in the plain entries).  The host-pointer spectral entries do not
+ * join the combining of concurrent small calls: they take the library's entry lock like any other call.  A NULL uflxs or dflxs, or only
+ * one of uflxcs / dflxcs, is RRTMG_LW_HIP_EARG. */
+int rrtmg_lw_hip_run_nomcica_spectral(
+    int ncol, int nlay, int *icld, int idrv,
+    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
+    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
+    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
+    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
+    const double *reice, const double *reliq, const double *tauaer,
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
+    double *duflx_dt, double *duflxc_dt, double *uflxs, double *dflxs, double *uflxcs, double *dflxcs);
+int rrtmg_lw_hip_run_nomcica_spectral_device(
+    int ncol, int nlay, int *icld, int idrv,
+    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
+    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
+    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
+    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
+    const double *reice, const double *reliq, const double *tauaer,
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
+    double *duflx_dt, double *duflxc_dt, double *uflxs, double *dflxs, double *uflxcs, double *dflxcs, void *stream);
+int rrtmg_lw_hip_run_mcica_spectral(
+    int ncol, int nlay, int *icld, int idrv,
+    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
+    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
+    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
+    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
+    const double *cldfmcl, const double *taucmcl, const double *ciwpmcl, const double *clwpmcl,
+    const double *reicmcl, const double *relqmcl, const double *tauaer,
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
+    double *duflx_dt, double *duflxc_dt, double *uflxs, double *dflxs, double *uflxcs, double *dflxcs);
+int rrtmg_lw_hip_run_mcica_spectral_device(
+    int ncol, int nlay, int *icld, int idrv,
+    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
+    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
+    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
+    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
+    const double *cldfmcl, const double *taucmcl, const double *ciwpmcl, const double *clwpmcl,
+    const double *reicmcl, const double *relqmcl, const double *tauaer,
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
+    double *duflx_dt, double *duflxc_dt, double *uflxs, double *dflxs, double *uflxcs, double *dflxcs, void *stream);
+int rrtmg_lw_hip_run_mcica_subcol_spectral(
+    int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng,
+    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
+    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
+    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
+    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
+    const double *reice, const double *reliq, const double *alpha, const double *tauaer,
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
+    double *duflx_dt, double *duflxc_dt, double *uflxs, double *dflxs, double *uflxcs, double *dflxcs);
+int rrtmg_lw_hip_run_mcica_subcol_spectral_device(
+    int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng,
+    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
+    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
+    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
+    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
+    const double *reice, const double *reliq, const double *alpha, const double *tauaer,
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
+    double *duflx_dt, double *duflxc_dt, double *uflxs, double *dflxs, double *uflxcs, double *dflxcs, void *stream);
+
 /* Tuning / introspection ------------------------------------------------------------------------- */
 /* Aggregation of small calls.  A host model that calls rrtmg_lw per chunk of a few dozen columns (the reference is called that way:
  * `do iplon = 1, ncol` inside, pcols-sized chunks outside, src/rrtmg_lw_rad.nomcica.f90:472) pays ~0.5 ms of launch latency per call on

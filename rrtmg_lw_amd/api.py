@@ -243,11 +243,33 @@ def _out_ok(a, shape, name):
     return a
 
 
+_SPEC = ("uflxs", "dflxs", "uflxcs", "dflxcs")
+
+
+def _spec_ptrs(out, ncol, nlay):
+    """Pointers to the spectral outputs (include/rrtmg_lw_hip.h, "Spectral (per-band) fluxes"): per band the flux it adds to the
+    broadband one, (ncol, nlay+1, 16) Fortran order, band 16 in the broadband call's convention.  Arrays missing from `out` are created
+    there; the caller's are checked like every output (_out_ok).  uflxcs = dflxcs = None: total sky only."""
+    shape = (ncol, nlay + 1, NBND)
+    for k in _SPEC:
+        if k not in out:
+            out[k] = np.empty(shape, order="F")
+    if (out["uflxcs"] is None) != (out["dflxcs"] is None):
+        raise ValueError("spectral outputs: uflxcs and dflxcs must be both None or both arrays")
+    return [C.cast(None, _dp) if out[k] is None and k in ("uflxcs", "dflxcs") else _p(_out_ok(out[k], shape, k)) for k in _SPEC]
+
+
+def _spec_dev(out):
+    """device variants: the spectral tensors' addresses (uflxcs / dflxcs may be None or absent: total sky only)"""
+    return [C.c_void_p(out[k].data_ptr()) if out.get(k) is not None else C.c_void_p(0) for k in _SPEC]
+
+
 def rrtmg_lw(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr,
              cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp,
-             cliqwp, reice, reliq, tauaer, out=None):
+             cliqwp, reice, reliq, tauaer, out=None, spectral=False):
     """Non-McICA rrtmg_lw with host arrays.  Returns dict(uflx, dflx, hr, uflxc, dflxc, hrc[, duflx_dt, duflxc_dt], icld);
-    `out` may hold preallocated (e.g. host_register'ed) Fortran-ordered output arrays."""
+    `out` may hold preallocated (e.g. host_register'ed) Fortran-ordered output arrays.  spectral=True: the dict also holds the fluxes
+    per band, uflxs, dflxs, uflxcs, dflxcs of shape (ncol, nlay+1, 16) (_spec_ptrs)."""
     a2 = [_f(x, (ncol, nlay)) for x in (play,)] + [_f(plev, (ncol, nlay + 1)), _f(tlay, (ncol, nlay)),
                                                   _f(tlev, (ncol, nlay + 1)), _f(tsfc, (ncol,))]
     gases = [_f(x, (ncol, nlay)) for x in (h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr)]
@@ -269,7 +291,10 @@ def rrtmg_lw(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr
     args += [_p(x) for x in cld]
     args += [_p(out[k]) for k in ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc")]
     args += [_p(out["duflx_dt"]) if idrv == 1 else null, _p(out["duflxc_dt"]) if idrv == 1 else null]
-    _check(lib().rrtmg_lw_hip_run_nomcica(*args))
+    if spectral:
+        _check(lib().rrtmg_lw_hip_run_nomcica_spectral(*args, *_spec_ptrs(out, ncol, nlay)))
+    else:
+        _check(lib().rrtmg_lw_hip_run_nomcica(*args))
     out["icld"] = icld_c.value
     return out
 
@@ -279,19 +304,20 @@ _GCM_ORDER = ("play", "plev", "tlay", "tlev", "tsfc", "h2ovmr", "o3vmr", "co2vmr
 _CLD_ORDER = ("cldfr", "taucld", "cicewp", "cliqwp", "reice", "reliq", "tauaer")
 
 
-def rrtmg_lw_from_dict(d, icld=None, idrv=None, out=None):
+def rrtmg_lw_from_dict(d, icld=None, idrv=None, out=None, spectral=False):
     """Convenience: call rrtmg_lw with the dictionaries produced by rrtmg_lw_amd.synth.make_gcm_inputs."""
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     return rrtmg_lw(d["ncol"], d["nlay"], icld, idrv, *[d[k] for k in _GCM_ORDER], d["inflglw"], d["iceflglw"],
-                    d["liqflglw"], *[d[k] for k in _CLD_ORDER], out=out)
+                    d["liqflglw"], *[d[k] for k in _CLD_ORDER], out=out, spectral=spectral)
 
 
 def rrtmg_lw_device(d, out, icld=None, idrv=None, stream=None):
     """Device-resident call: `d` holds torch CUDA tensors laid out column-fastest (synth.make_gcm_inputs(backend="torch")),
     `out` a dict of preallocated output tensors (uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt).
     Enqueues on `stream` (an integer hipStream_t handle, e.g. torch.cuda.current_stream().cuda_stream) and returns
-    immediately; call check(stream) to synchronise and collect physics errors."""
+    immediately; call check(stream) to synchronise and collect physics errors.  When `out` holds uflxs (and dflxs, optionally
+    uflxcs / dflxcs: (ncol, nlay+1, 16) laid out column-fastest, band last) the spectral entry fills them as well."""
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     icld_c = C.c_int(int(icld))
@@ -302,6 +328,9 @@ def rrtmg_lw_device(d, out, icld=None, idrv=None, stream=None):
     args += [ptr(d[k]) for k in _CLD_ORDER]
     args += [ptr(out[k]) for k in ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc")]
     args += [ptr(out[k]) if out.get(k) is not None else C.c_void_p(0) for k in ("duflx_dt", "duflxc_dt")]      # needed only with idrv = 1
+    if "uflxs" in out:
+        _check(lib().rrtmg_lw_hip_run_nomcica_spectral_device(*args, *_spec_dev(out), C.c_void_p(stream or 0)))
+        return icld_c.value
     args.append(C.c_void_p(stream or 0))
     _check(lib().rrtmg_lw_hip_run_nomcica_device(*args))
     return icld_c.value
@@ -333,6 +362,9 @@ def rrtmg_lw_mcica_device(d, sub, out, icld=None, idrv=None, stream=None):
     args += [ptr(sub[k]) for k in ("cldfmcl", "taucmcl", "ciwpmcl", "clwpmcl", "reicmcl", "relqmcl")] + [ptr(d["tauaer"])]
     args += [ptr(out[k]) for k in ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc")]
     args += [ptr(out[k]) if out.get(k) is not None else C.c_void_p(0) for k in ("duflx_dt", "duflxc_dt")]      # needed only with idrv = 1
+    if "uflxs" in out:          # spectral outputs (see rrtmg_lw_device)
+        _check(lib().rrtmg_lw_hip_run_mcica_spectral_device(*args, *_spec_dev(out), C.c_void_p(stream or 0)))
+        return icld_c.value
     args.append(C.c_void_p(stream or 0))
     _check(lib().rrtmg_lw_hip_run_mcica_device(*args))
     return icld_c.value
@@ -394,18 +426,22 @@ def _gcm_arrays(ncol, nlay, play, plev, tlay, tlev, tsfc, gases, emis):
 
 def rrtmg_lw_mcica(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr,
                    cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfmcl, taucmcl, ciwpmcl,
-                   clwpmcl, reicmcl, relqmcl, tauaer):
-    """McICA rrtmg_lw (src/rrtmg_lw_rad.f90:99-108) with host arrays; sub-column arrays are (140, ncol, nlay)."""
+                   clwpmcl, reicmcl, relqmcl, tauaer, spectral=False, out=None):
+    """McICA rrtmg_lw (src/rrtmg_lw_rad.f90:99-108) with host arrays; sub-column arrays are (140, ncol, nlay).
+    spectral=True: the fluxes per band as well (see rrtmg_lw); `out`: a dict of preallocated spectral outputs to fill."""
     a = _gcm_arrays(ncol, nlay, play, plev, tlay, tlev, tsfc,
                     (h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr), emis)
     ng = gpoints()
     cld = [_f(cldfmcl, (ng, ncol, nlay)), _f(taucmcl, (ng, ncol, nlay)), _f(ciwpmcl, (ng, ncol, nlay)),
            _f(clwpmcl, (ng, ncol, nlay)), _f(reicmcl, (ncol, nlay)), _f(relqmcl, (ncol, nlay)), _f(tauaer, (ncol, nlay, NBND))]
-    out = _out_arrays(ncol, nlay, idrv)
+    out = dict(out or {}, **_out_arrays(ncol, nlay, idrv))
     icld_c = C.c_int(int(icld))
     args = [C.c_int(ncol), C.c_int(nlay), C.byref(icld_c), C.c_int(int(idrv))] + [_p(x) for x in a]
     args += [C.c_int(int(inflglw)), C.c_int(int(iceflglw)), C.c_int(int(liqflglw))] + [_p(x) for x in cld] + _out_ptrs(out, idrv)
-    _check(lib().rrtmg_lw_hip_run_mcica(*args))
+    if spectral:
+        _check(lib().rrtmg_lw_hip_run_mcica_spectral(*args, *_spec_ptrs(out, ncol, nlay)))
+    else:
+        _check(lib().rrtmg_lw_hip_run_mcica(*args))
     out["icld"] = icld_c.value
     return out
 
@@ -413,11 +449,11 @@ def rrtmg_lw_mcica(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr,
 _MC_ORDER = ("cldfmcl", "taucmcl", "ciwpmcl", "clwpmcl", "reicmcl", "relqmcl", "tauaer")
 
 
-def rrtmg_lw_mcica_from_dict(d, icld=None, idrv=None):
+def rrtmg_lw_mcica_from_dict(d, icld=None, idrv=None, spectral=False, out=None):
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     return rrtmg_lw_mcica(d["ncol"], d["nlay"], icld, idrv, *[d[k] for k in _GCM_ORDER], d["inflglw"], d["iceflglw"],
-                          d["liqflglw"], *[d[k] for k in _MC_ORDER])
+                          d["liqflglw"], *[d[k] for k in _MC_ORDER], spectral=spectral, out=out)
 
 
 def get_alpha(ncol, nlay, icld, idcor, decorr_con, dz, lat, juldat, cldfrac):
@@ -455,29 +491,33 @@ def mcica_subcol_lw(ncol, nlay, icld, permuteseed, irng, play, cldfrac, ciwp, cl
 
 def rrtmg_lw_mcica_subcol(ncol, nlay, icld, idrv, permuteseed, irng, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr,
                           ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw,
-                          cldfr, taucld, cicewp, cliqwp, reice, reliq, alpha, tauaer):
-    """mcica_subcol_lw followed by the McICA rrtmg_lw in one call; the sub-columns stay on the device as bit masks."""
+                          cldfr, taucld, cicewp, cliqwp, reice, reliq, alpha, tauaer, spectral=False, out=None):
+    """mcica_subcol_lw followed by the McICA rrtmg_lw in one call; the sub-columns stay on the device as bit masks.
+    spectral=True: the fluxes per band as well (see rrtmg_lw); `out`: a dict of preallocated spectral outputs to fill."""
     a = _gcm_arrays(ncol, nlay, play, plev, tlay, tlev, tsfc,
                     (h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr), emis)
     cld = [_p(_f(cldfr, (ncol, nlay))), _p(_f(taucld, (NBND, ncol, nlay))), _p(_f(cicewp, (ncol, nlay))), _p(_f(cliqwp, (ncol, nlay))),
            _p(_f(reice, (ncol, nlay))), _p(_f(reliq, (ncol, nlay))),
            _p(_f(alpha, (ncol, nlay))) if alpha is not None else C.cast(None, _dp), _p(_f(tauaer, (ncol, nlay, NBND)))]
-    out = _out_arrays(ncol, nlay, idrv)
+    out = dict(out or {}, **_out_arrays(ncol, nlay, idrv))
     icld_c, irng_c = C.c_int(int(icld)), C.c_int(int(irng))
     args = [C.c_int(ncol), C.c_int(nlay), C.byref(icld_c), C.c_int(int(idrv)), C.c_int(int(permuteseed)), C.byref(irng_c)]
     args += [_p(x) for x in a] + [C.c_int(int(inflglw)), C.c_int(int(iceflglw)), C.c_int(int(liqflglw))] + cld + _out_ptrs(out, idrv)
-    _check(lib().rrtmg_lw_hip_run_mcica_subcol(*args))
+    if spectral:
+        _check(lib().rrtmg_lw_hip_run_mcica_subcol_spectral(*args, *_spec_ptrs(out, ncol, nlay)))
+    else:
+        _check(lib().rrtmg_lw_hip_run_mcica_subcol(*args))
     out["icld"] = icld_c.value
     out["irng"] = irng_c.value
     return out
 
 
-def rrtmg_lw_mcica_subcol_from_dict(d, permuteseed, irng, alpha=None, icld=None, idrv=None):
+def rrtmg_lw_mcica_subcol_from_dict(d, permuteseed, irng, alpha=None, icld=None, idrv=None, spectral=False, out=None):
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     return rrtmg_lw_mcica_subcol(d["ncol"], d["nlay"], icld, idrv, permuteseed, irng, *[d[k] for k in _GCM_ORDER], d["inflglw"],
                                  d["iceflglw"], d["liqflglw"], d["cldfr"], d["taucld"], d["cicewp"], d["cliqwp"], d["reice"],
-                                 d["reliq"], alpha, d["tauaer"])
+                                 d["reliq"], alpha, d["tauaer"], spectral=spectral, out=out)
 
 
 def rrtmg_lw_mcica_subcol_device(d, out, permuteseed, irng, alpha=None, icld=None, idrv=None, stream=None):
@@ -493,6 +533,9 @@ def rrtmg_lw_mcica_subcol_device(d, out, permuteseed, irng, alpha=None, icld=Non
     args += [ptr(alpha) if alpha is not None else C.c_void_p(0), ptr(d["tauaer"])]
     args += [ptr(out[k]) for k in ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc")]
     args += [ptr(out[k]) if out.get(k) is not None else C.c_void_p(0) for k in ("duflx_dt", "duflxc_dt")]      # needed only with idrv = 1
+    if "uflxs" in out:          # spectral outputs (see rrtmg_lw_device)
+        _check(lib().rrtmg_lw_hip_run_mcica_subcol_spectral_device(*args, *_spec_dev(out), C.c_void_p(stream or 0)))
+        return icld_c.value
     args.append(C.c_void_p(stream or 0))
     _check(lib().rrtmg_lw_hip_run_mcica_subcol_device(*args))
     return icld_c.value

@@ -292,16 +292,32 @@ hipEvent_t get_event()
     } while (0)
 
 // the sweeps stage the transmittance table in LDS: more than the 64 KB a kernel may use without asking
-template <int Q>
+template <int Q, bool SPEC = false>
 int sweepc_attr_one()
 {
 #ifndef RRLW_TUNE
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 0, false, sweepc_nt(Q, 0, false)>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 0, true, sweepc_nt(Q, 0, true)>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 2, true, sweepc_nt(Q, 2, true)>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 0, false, sweepc_nt(Q, 0, false), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 0, true, sweepc_nt(Q, 0, true), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 2, true, sweepc_nt(Q, 2, true), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
 #endif
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 1, false, sweepc_nt(Q, 1, false)>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 2, false, sweepc_nt(Q, 2, false)>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 1, false, sweepc_nt(Q, 1, false), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 2, false, sweepc_nt(Q, 2, false), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+    return 0;
+}
+// the SPEC instantiations of the cloud-zone sweep (spectral outputs): every quad class, mode and d/dT flag
+template <int Q>
+int sweepz_attr_spec()
+{
+#ifndef RRLW_TUNE
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 3, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 4, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+#endif
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
     return 0;
 }
 int ensure_sweep_attrs()
@@ -350,6 +366,14 @@ int ensure_sweep_attrs()
     if (int rc = sweepc_attr_one<2>()) return rc;
     if (int rc = sweepc_attr_one<3>()) return rc;
     if (int rc = sweepc_attr_one<4>()) return rc;
+    if (int rc = sweepc_attr_one<1, true>()) return rc;
+    if (int rc = sweepc_attr_one<2, true>()) return rc;
+    if (int rc = sweepc_attr_one<3, true>()) return rc;
+    if (int rc = sweepc_attr_one<4, true>()) return rc;
+    if (int rc = sweepz_attr_spec<1>()) return rc;
+    if (int rc = sweepz_attr_spec<2>()) return rc;
+    if (int rc = sweepz_attr_spec<3>()) return rc;
+    if (int rc = sweepz_attr_spec<4>()) return rc;
     HIP_TRY(hipFuncSetAttribute((const void *)k_flux<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FLUX_LDS_BYTES));
     HIP_TRY(hipFuncSetAttribute((const void *)k_flux<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FLUX_LDS_BYTES));
     G.sweep_attrs = true;
@@ -707,11 +731,12 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, int nb, int col0, int nct, in
     }
     const hipStream_t s_main = s;
 #ifndef RRLW_TUNE
-    if (G.n1 && mode == 0 && GCM && istart == 1 && iend == 16 && idrv == 0 && n1_lds_bytes(nlay) <= 160 * 1024) {
+    if (G.n1 && mode == 0 && GCM && istart == 1 && iend == 16 && idrv == 0 && !out.uflxs && n1_lds_bytes(nlay) <= 160 * 1024) {
         // prototype of the north-star mapping (one column per wavefront): replaces the sweeps, k_flux and k_rates of a cloud-free call
         SweepArgs sa{};
         sa.ncol = nb; sa.col0 = col0; sa.nct = nct; sa.idrv = 0; sa.istart = 1; sa.iend = 16;
         sa.emis = g.emis; sa.cldfrac = nullptr; sa.tlay = g.tlay; sa.tlev = g.tlev;
+        sa.uflxs = sa.dflxs = sa.uflxcs = sa.dflxcs = nullptr;
         static bool attr = false;
         if (!attr) { HIP_TRY(hipFuncSetAttribute((const void *)k_n1<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr = true; }
         const dim3 ngrid((nb + N1_WAVES - 1) / N1_WAVES), nblock(64 * N1_WAVES);
@@ -728,6 +753,11 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, int nb, int col0, int nct, in
     sa.cldfrac = GCM ? g.cldfr : c.cldfrac;
     sa.tlay = GCM ? g.tlay : c.tavel;
     sa.tlev = GCM ? g.tlev : c.tz;
+    // spectral outputs (GCM entries): the SPEC instantiations of the sweeps store every band's flux as well; the prototype k_n1 above
+    // takes no spectral call
+    const bool spec = GCM && out.uflxs;
+    sa.uflxs = spec ? out.uflxs : nullptr; sa.dflxs = spec ? out.dflxs : nullptr;
+    sa.uflxcs = spec ? out.uflxcs : nullptr; sa.dflxcs = spec ? out.dflxcs : nullptr;
     // Per class of bands with the same number of quads: a cloud-free call (mode 0) is one k_sweepc<., 0> launch; the cloudy modes run
     // k_sweepc<., 1> (layers above the batch's highest cloud, downward), k_sweepz<., mode> (layers 1 .. ltop down, surface, up) and
     // k_sweepc<., 2> (layers above, upward).  The classes are independent of each other: with `fan` each class has its own stream;
@@ -748,7 +778,8 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, int nb, int col0, int nct, in
         const int nsb = split ? 1 : sweepc_nsb(Q, PH, I, sa.nbands);                                                 \
         sa.ncb = (nb + 64 * nsb - 1) / (64 * nsb);                                                                   \
         const dim3 sgrid((unsigned)sa.ncb, split ? sa.nbands : 1), sblock(64, wnb * nt, nsb);                        \
-        LAUNCH_LDS("k_sweepc<" #Q "," #PH ">", (k_sweepc<Q, PH, I, nt>), sgrid, sblock, sweepc_lds_bytes(PH, I, wnb, nsb, nt), s, G.D, Wk, sa); \
+        if (spec) LAUNCH_LDS("k_sweepc<" #Q "," #PH ",spec>", (k_sweepc<Q, PH, I, nt, true>), sgrid, sblock, sweepc_lds_bytes(PH, I, wnb, nsb, nt), s, G.D, Wk, sa); \
+        else LAUNCH_LDS("k_sweepc<" #Q "," #PH ">", (k_sweepc<Q, PH, I, nt>), sgrid, sblock, sweepc_lds_bytes(PH, I, wnb, nsb, nt), s, G.D, Wk, sa); \
     } while (0)
 #ifdef RRLW_TUNE
 #define SWEEPC(Q, PH) do { if (idrv == 1) return fail(RRTMG_LW_HIP_EARG, "tuning build: idrv = 0 only"); else SWEEPC_I(Q, PH, false); } while (0)
@@ -772,7 +803,8 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, int nb, int col0, int nct, in
         const int nsb = split ? 1 : sweepz_nsb(Q, sa.nbands, I);                                                     \
         sa.ncb = (nb + 64 * nsb - 1) / (64 * nsb);                                                                   \
         const dim3 sgrid((unsigned)sa.ncb, split ? sa.nbands : 1), sblock(64, wnb * nt, nsb);                        \
-        LAUNCH_LDS("k_sweepz<" #Q "," #M ">", (k_sweepz<Q, M, I>), sgrid, sblock, sweepz_lds_bytes(wnb, nsb, nt, I), s, G.D, Wk, sa); \
+        if (spec) LAUNCH_LDS("k_sweepz<" #Q "," #M ",spec>", (k_sweepz<Q, M, I, true>), sgrid, sblock, sweepz_lds_bytes(wnb, nsb, nt, I), s, G.D, Wk, sa); \
+        else LAUNCH_LDS("k_sweepz<" #Q "," #M ">", (k_sweepz<Q, M, I>), sgrid, sblock, sweepz_lds_bytes(wnb, nsb, nt, I), s, G.D, Wk, sa); \
     } while (0)
 #ifdef RRLW_TUNE
 #define SWEEPZ_M(Q, M) do { if (idrv == 1) return fail(RRTMG_LW_HIP_EARG, "tuning build: idrv = 0 only"); else SWEEPZ_I(Q, M, false); } while (0)
@@ -912,7 +944,8 @@ int run_pipelined(hipStream_t s, int ncol, int nlay, int mode, int idrv, const G
         key_put(key, ncol); key_put(key, nlay); key_put(key, mode); key_put(key, idrv); key_put(key, inflag); key_put(key, iceflag); key_put(key, liqflag);
         const double *gp[] = {g.play, g.plev, g.tlay, g.tlev, g.tsfc, g.h2ovmr, g.o3vmr, g.co2vmr, g.ch4vmr, g.n2ovmr, g.o2vmr, g.cfc11vmr, g.cfc12vmr,
                               g.cfc22vmr, g.ccl4vmr, g.emis, g.cldfr, g.taucld, g.cicewp, g.cliqwp, g.reice, g.reliq, g.tauaer, g.tauctot,
-                              out.uflx, out.dflx, out.hr, out.uflxc, out.dflxc, out.hrc, out.duflx_dt, out.duflxc_dt, out.fnet, out.fnetc};
+                              out.uflx, out.dflx, out.hr, out.uflxc, out.dflxc, out.hrc, out.duflx_dt, out.duflxc_dt, out.fnet, out.fnetc,
+                              out.uflxs, out.dflxs, out.uflxcs, out.dflxcs};
         key_put(key, gp);
         // (what else decides which kernels run with which arguments: the workspace, the tuning switches)
         key_put(key, G.ws_base); key_put(key, G.ws_bytes); key_put(key, g_colsort); key_put(key, g_colsort_min); key_put(key, g_one_sweep_max);
@@ -1075,6 +1108,21 @@ int check_common(int ncol, int nlay)
     return 0;
 }
 
+// Spectral outputs of the *_spectral entries: per band the flux the band adds to the broadband one (ncol,nlay+1,16), uflxs and dflxs
+// required, the clear-sky pair both null or both set.  They reach the sweeps through FluxOut (run_sweep: the SPEC instantiations).
+struct SpecOut { double *uflxs = nullptr, *dflxs = nullptr, *uflxcs = nullptr, *dflxcs = nullptr; };
+int check_spec(const SpecOut &sp)
+{
+    if (!sp.uflxs || !sp.dflxs) return fail(RRTMG_LW_HIP_EARG, "spectral entry: uflxs and dflxs are required");
+    if (!sp.uflxcs != !sp.dflxcs) return fail(RRTMG_LW_HIP_EARG, "spectral entry: uflxcs and dflxcs must be both null or both set");
+    return 0;
+}
+void put_spec(FluxOut &o, const SpecOut *sp)
+{
+    if (!sp) return;
+    o.uflxs = sp->uflxs; o.dflxs = sp->dflxs; o.uflxcs = sp->uflxcs; o.dflxcs = sp->dflxcs;
+}
+
 
 // ---- host-pointer staging ---------------------------------------------------------------------------
 // Every array of the interface is [rows][ncol][inner] with `inner` fastest (inner = 1 for (ncol,nlay) arrays,
@@ -1091,6 +1139,17 @@ struct HostIn {
     unsigned long long static_gen = 0;                    // != 0: the caller declared the array static (rrtmg_lw_hip_host_static): row scans are cached per batch
 };
 struct HostOut { double *h; size_t rows; double *d; bool active; bool pinned = false; };
+// the spectral outputs of a host-pointer call as staged arrays of 16 (nlay + 1) rows, after the eight broadband ones (no rows when absent)
+void add_spec_outs(std::vector<HostOut> &outs, const SpecOut *sp, size_t L)
+{
+    const SpecOut so = sp ? *sp : SpecOut{};
+    for (double *h : {so.uflxs, so.dflxs, so.uflxcs, so.dflxcs}) outs.push_back({h, h ? (size_t)NBND * (L + 1) : 0, nullptr, h != nullptr});
+}
+void put_spec_staged(FluxOut &o, const std::vector<HostOut> &v)
+{
+    o.uflxs = v[8].active ? v[8].d : nullptr; o.dflxs = v[9].active ? v[9].d : nullptr;
+    o.uflxcs = v[10].active ? v[10].d : nullptr; o.dflxcs = v[11].active ? v[11].d : nullptr;
+}
 int bounce_h2d(void *dst, const void *src, size_t bytes);
 int bounce_d2h(void *dst, const void *src, size_t bytes);
 int bounce_h2d_rows(void *dst, const void *src, size_t row_bytes, size_t stride_bytes, size_t rows);
@@ -2302,7 +2361,7 @@ int rrtmg_lw_hip_check(void *stream)
 // the state (index into the devices of rrtmg_lw_hip_init_devices) this thread's last device-pointer entry ran on
 int rrtmg_lw_hip_last_device_state(void) { return tl_dev_state; }
 
-int rrtmg_lw_hip_run_nomcica_device(
+static int nomcica_device(
     int ncol, int nlay, int *icld, int idrv,
     const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
     const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
@@ -2311,10 +2370,11 @@ int rrtmg_lw_hip_run_nomcica_device(
     const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
     const double *reice, const double *reliq, const double *tauaer,
     double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
-    double *duflx_dt, double *duflxc_dt, void *stream)
+    double *duflx_dt, double *duflxc_dt, const SpecOut *sp, void *stream)
 {
     ENTRY_LOCK_FOR(play);
     if (int rc = check_common(ncol, nlay)) return rc;
+    if (sp) if (int rc = check_spec(*sp)) return rc;
     if (!icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
     if (*icld < 0 || *icld > 3) *icld = 2;                       // src/rrtmg_lw_rad.nomcica.f90:456
     if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
@@ -2324,7 +2384,34 @@ int rrtmg_lw_hip_run_nomcica_device(
     GcmIn g{play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr,
             ccl4vmr, emis, cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer};
     FluxOut out{uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt, nullptr, nullptr};
+    put_spec(out, sp);
     return run_pipelined((hipStream_t)stream, ncol, nlay, mode, idrv, g, inflglw, iceflglw, liqflglw, out, nullptr);
+}
+
+#define NOMCICA_PARAMS                                                                                          \
+    int ncol, int nlay, int *icld, int idrv,                                                                    \
+    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,         \
+    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr, \
+    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,               \
+    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,                        \
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,                     \
+    const double *reice, const double *reliq, const double *tauaer,                                            \
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,                         \
+    double *duflx_dt, double *duflxc_dt
+#define NOMCICA_ARGS                                                                                            \
+    ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, \
+    cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, \
+    tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt
+#define SPEC_PARAMS double *uflxs, double *dflxs, double *uflxcs, double *dflxcs
+
+int rrtmg_lw_hip_run_nomcica_device(NOMCICA_PARAMS, void *stream)
+{
+    return nomcica_device(NOMCICA_ARGS, nullptr, stream);
+}
+int rrtmg_lw_hip_run_nomcica_spectral_device(NOMCICA_PARAMS, SPEC_PARAMS, void *stream)
+{
+    const SpecOut sp{uflxs, dflxs, uflxcs, dflxcs};
+    return nomcica_device(NOMCICA_ARGS, &sp, stream);
 }
 
 }   // extern "C"
@@ -2339,7 +2426,7 @@ int nomcica_host_range(int ncol, int c0, int c1, int nlay, int icld, int idrv,
     const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
     const double *reice, const double *reliq, const double *tauaer,
     double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
-    double *duflx_dt, double *duflxc_dt)
+    double *duflx_dt, double *duflxc_dt, const SpecOut *sp)
 {
     if (int rc = check_common(ncol, nlay)) return rc;
     HIP_TRY(hipDeviceSynchronize());        // asynchronous device-entry work of earlier calls shares the workspace
@@ -2404,12 +2491,14 @@ int nomcica_host_range(int ncol, int c0, int c1, int nlay, int icld, int idrv,
     std::vector<HostOut> outs = {{uflx, L + 1, 0, true}, {dflx, L + 1, 0, true}, {hr, L, 0, true}, {uflxc, L + 1, 0, true},
                                  {dflxc, L + 1, 0, true}, {hrc, L, 0, true}, {duflx_dt, L + 1, 0, idrv == 1}, {duflxc_dt, L + 1, 0, idrv == 1}};
     for (size_t k = 0; k < 6; k++) if (!outs[k].h) return fail(RRTMG_LW_HIP_EARG, "null output array");
+    add_spec_outs(outs, sp, L);
     auto body = [&](hipStream_t s, int nb, int, std::vector<HostIn> &in, std::vector<HostOut> &out_) -> int {
         GcmIn g{in[0].d, in[1].d, in[2].d, in[3].d, in[4].d, in[5].d, in[6].d, in[7].d, in[8].d, in[9].d, in[10].d,
                 in[11].d, in[12].d, in[13].d, in[14].d, in[15].d, in[17].d, use_tot ? nullptr : in[18].d, in[19].d, in[20].d, in[21].d, in[22].d, in[16].d,
                 use_tot ? in[18].d : nullptr};
         ColIn c{};
         FluxOut out{out_[0].d, out_[1].d, out_[2].d, out_[3].d, out_[4].d, out_[5].d, out_[6].d, out_[7].d, nullptr, nullptr};
+        put_spec_staged(out, out_);
         return run_batch<true>(s, nb, 0, nb, nlay, mode, idrv, 1, 16, g, c, inflglw, iceflglw, liqflglw, out);
     };
     if (int rc = host_pipeline(ncol, c0, c1, nbmax, ins, outs, body, prep)) return rc;
@@ -2452,16 +2541,17 @@ int nomcica_host(int ncol, int nlay, int *icld, int idrv,
     const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
     const double *reice, const double *reliq, const double *tauaer,
     double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
-    double *duflx_dt, double *duflxc_dt)
+    double *duflx_dt, double *duflxc_dt, const SpecOut *sp = nullptr)
 {
     if (int rc = check_common(ncol, nlay)) return rc;
+    if (sp) if (int rc = check_spec(*sp)) return rc;
     if (!icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
     if (*icld < 0 || *icld > 3) *icld = 2;
     if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
     const int ic = *icld;
     return fan_out(ncol, [&](int c0, int c1) {
         return nomcica_host_range(ncol, c0, c1, nlay, ic, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis,
-                              inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt);
+                              inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt, sp);
     });
 }
 bool comb_enabled();
@@ -2497,6 +2587,14 @@ int rrtmg_lw_hip_run_nomcica(
     ENTRY_LOCK;
     return nomcica_host(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis,
                               inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt);
+}
+
+// the same with spectral outputs; such a call does not join the combining entry (it takes the entry lock like any other call)
+int rrtmg_lw_hip_run_nomcica_spectral(NOMCICA_PARAMS, SPEC_PARAMS)
+{
+    ENTRY_LOCK;
+    const SpecOut sp{uflxs, dflxs, uflxcs, dflxcs};
+    return nomcica_host(NOMCICA_ARGS, &sp);
 }
 
 // calls and device passes of the combining entry since the library was loaded (a pass serves one or more calls)
@@ -2777,7 +2875,8 @@ static int mcica_subcol_host(int ncol, int nlay, int *icld, int idrv, int permut
     const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
     const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp, const double *reice,
     const double *reliq, const double *alpha, const double *tauaer,
-    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc, double *duflx_dt, double *duflxc_dt);
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc, double *duflx_dt, double *duflxc_dt,
+    const SpecOut *sp = nullptr);
 static int solve_chunks(const std::vector<QueuedChunk> &chunks, long long N, int nlay, int icld_in, int idrv, int inflg, int iceflg, int liqflg,
                         int kind = 0, int permuteseed = 0, bool has_alpha = false)
 {
@@ -3018,14 +3117,21 @@ extern "C" {
 #define OUT_PARAMS                                                                                              \
     double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc, double *duflx_dt, double *duflxc_dt
 
-int rrtmg_lw_hip_run_mcica_device(
-    int ncol, int nlay, int *icld, int idrv, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw,
-    const double *cldfmcl, const double *taucmcl, const double *ciwpmcl, const double *clwpmcl,
-    const double *reicmcl, const double *relqmcl, const double *tauaer, OUT_PARAMS, void *stream)
+#define MCICA_PARAMS                                                                                            \
+    int ncol, int nlay, int *icld, int idrv, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw,               \
+    const double *cldfmcl, const double *taucmcl, const double *ciwpmcl, const double *clwpmcl,                 \
+    const double *reicmcl, const double *relqmcl, const double *tauaer, OUT_PARAMS
+#define MCICA_ARGS                                                                                              \
+    ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, \
+    cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfmcl, taucmcl, ciwpmcl, clwpmcl, reicmcl, \
+    relqmcl, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt
+
+static int mcica_device(MCICA_PARAMS, const SpecOut *sp, void *stream)
 {
     ENTRY_LOCK_FOR(play);
     if (int rc = check_mcica_build()) return rc;
     if (int rc = check_common(ncol, nlay)) return rc;
+    if (sp) if (int rc = check_spec(*sp)) return rc;
     if (!icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
     if (*icld < 0 || *icld > 3) *icld = 2;                       // src/rrtmg_lw_rad.f90:469
     if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
@@ -3036,17 +3142,25 @@ int rrtmg_lw_hip_run_mcica_device(
             ccl4vmr, emis, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tauaer};
     McIn m{cldfmcl, taucmcl, ciwpmcl, clwpmcl, reicmcl, relqmcl};
     FluxOut out{uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt, nullptr, nullptr};
+    put_spec(out, sp);
     return run_pipelined((hipStream_t)stream, ncol, nlay, mode, idrv, g, inflglw, iceflglw, liqflglw, out, &m);
 }
+int rrtmg_lw_hip_run_mcica_device(MCICA_PARAMS, void *stream)
+{
+    return mcica_device(MCICA_ARGS, nullptr, stream);
+}
+int rrtmg_lw_hip_run_mcica_spectral_device(MCICA_PARAMS, SPEC_PARAMS, void *stream)
+{
+    const SpecOut sp{uflxs, dflxs, uflxcs, dflxcs};
+    return mcica_device(MCICA_ARGS, &sp, stream);
+}
 
-int rrtmg_lw_hip_run_mcica(
-    int ncol, int nlay, int *icld, int idrv, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw,
-    const double *cldfmcl, const double *taucmcl, const double *ciwpmcl, const double *clwpmcl,
-    const double *reicmcl, const double *relqmcl, const double *tauaer, OUT_PARAMS)
+static int mcica_host(MCICA_PARAMS, const SpecOut *sp)
 {
     ENTRY_LOCK;
     if (int rc = check_mcica_build()) return rc;
     if (int rc = check_common(ncol, nlay)) return rc;
+    if (sp) if (int rc = check_spec(*sp)) return rc;
     if (!icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
     if (*icld < 0 || *icld > 3) *icld = 2;
     if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
@@ -3070,12 +3184,14 @@ int rrtmg_lw_hip_run_mcica(
     if (cloud) for (size_t k = 17; k < ins.size(); k++) if (!ins[k].h) return fail(RRTMG_LW_HIP_EARG, "null McICA cloud array");
     std::vector<HostOut> outs = {{uflx, L + 1, 0, true}, {dflx, L + 1, 0, true}, {hr, L, 0, true}, {uflxc, L + 1, 0, true},
                                  {dflxc, L + 1, 0, true}, {hrc, L, 0, true}, {duflx_dt, L + 1, 0, idrv == 1}, {duflxc_dt, L + 1, 0, idrv == 1}};
+    add_spec_outs(outs, sp, L);
     auto body = [&](hipStream_t s, int nb, int, std::vector<HostIn> &in, std::vector<HostOut> &out_) -> int {
         GcmIn g{in[0].d, in[1].d, in[2].d, in[3].d, in[4].d, in[5].d, in[6].d, in[7].d, in[8].d, in[9].d, in[10].d,
                 in[11].d, in[12].d, in[13].d, in[14].d, in[15].d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, in[16].d};
         McIn m{in[17].d, in[18].d, in[19].d, in[20].d, in[21].d, in[22].d};
         ColIn c{};
         FluxOut out{out_[0].d, out_[1].d, out_[2].d, out_[3].d, out_[4].d, out_[5].d, out_[6].d, out_[7].d, nullptr, nullptr};
+        put_spec_staged(out, out_);
         return run_batch<true>(s, nb, 0, nb, nlay, mode, idrv, 1, 16, g, c, inflglw, iceflglw, liqflglw, out, &m);
     };
     // layers whose sub-column cloud fractions are all below cldmin for the batch: cldprmc reads nothing else of them (src/rrtmg_lw_cldprmc.f90:182-183)
@@ -3092,6 +3208,15 @@ int rrtmg_lw_hip_run_mcica(
     hipStream_t s = G.stream;
     return read_physics_error(s);
     });
+}
+int rrtmg_lw_hip_run_mcica(MCICA_PARAMS)
+{
+    return mcica_host(MCICA_ARGS, nullptr);
+}
+int rrtmg_lw_hip_run_mcica_spectral(MCICA_PARAMS, SPEC_PARAMS)
+{
+    const SpecOut sp{uflxs, dflxs, uflxcs, dflxcs};
+    return mcica_host(MCICA_ARGS, &sp);
 }
 
 int rrtmg_lw_hip_get_alpha(int ncol, int nlay, int icld, int idcor, double decorr_con, const double *dz, const double *lat,
@@ -3207,13 +3332,19 @@ int rrtmg_lw_hip_mcica_subcol(
 
 // Fused generator + solver: mcica_subcol_lw followed by the McICA rrtmg_lw without materialising the (140,ncol,nlay)
 // sub-column arrays (they are implied by the mask and the grid-mean cloud properties).  DEVICE pointers.
-int rrtmg_lw_hip_run_mcica_subcol_device(
-    int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw,
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp, const double *reice,
-    const double *reliq, const double *alpha, const double *tauaer, OUT_PARAMS, void *stream)
+#define SUBCOL_PARAMS                                                                                                       \
+    int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw, \
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp, const double *reice,             \
+    const double *reliq, const double *alpha, const double *tauaer, OUT_PARAMS
+#define SUBCOL_ARGS                                                                                                         \
+    ncol, nlay, icld, idrv, permuteseed, irng, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr,    \
+    cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq,  \
+    alpha, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt
+static int mcica_subcol_device(SUBCOL_PARAMS, const SpecOut *sp, void *stream)
 {
     ENTRY_LOCK_FOR(play, irng && *irng != 0);
     if (int rc = check_mcica_build()) return rc;
+    if (sp) if (int rc = check_spec(*sp)) return rc;
     if (!icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
     if (int rc = check_subcol_args(ncol, nlay, *icld, irng)) return rc;
     if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
@@ -3233,7 +3364,17 @@ int rrtmg_lw_hip_run_mcica_subcol_device(
     GcmIn g{play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr,
             ccl4vmr, emis, cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer};
     FluxOut out{uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt, nullptr, nullptr};
+    put_spec(out, sp);
     return run_pipelined(s, ncol, nlay, mode, idrv, g, inflglw, iceflglw, liqflglw, out, nullptr, gen);
+}
+int rrtmg_lw_hip_run_mcica_subcol_device(SUBCOL_PARAMS, void *stream)
+{
+    return mcica_subcol_device(SUBCOL_ARGS, nullptr, stream);
+}
+int rrtmg_lw_hip_run_mcica_subcol_spectral_device(SUBCOL_PARAMS, SPEC_PARAMS, void *stream)
+{
+    const SpecOut sp{uflxs, dflxs, uflxcs, dflxcs};
+    return mcica_subcol_device(SUBCOL_ARGS, &sp, stream);
 }
 
 // columns [c0, c1) of the fused generator + solver call on the calling thread's current device state (kissvec seeds its stream per
@@ -3242,7 +3383,7 @@ int rrtmg_lw_hip_run_mcica_subcol_device(
 static int mcica_subcol_host_range(
     int ncol, int c0, int c1, int nlay, int icld_gen, int idrv, int permuteseed, int irng, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw,
     const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp, const double *reice,
-    const double *reliq, const double *alpha, const double *tauaer, OUT_PARAMS)
+    const double *reliq, const double *alpha, const double *tauaer, OUT_PARAMS, const SpecOut *sp)
 {
     if (int rc = check_common(ncol, nlay)) return rc;
     HIP_TRY(hipDeviceSynchronize());      // asynchronous device-entry work of earlier calls shares the workspace
@@ -3279,11 +3420,13 @@ static int mcica_subcol_host_range(
     std::vector<HostOut> outs = {{uflx, L + 1, 0, true}, {dflx, L + 1, 0, true}, {hr, L, 0, true}, {uflxc, L + 1, 0, true},
                                  {dflxc, L + 1, 0, true}, {hrc, L, 0, true}, {duflx_dt, L + 1, 0, idrv == 1}, {duflxc_dt, L + 1, 0, idrv == 1}};
     for (size_t k = 0; k < 6; k++) if (!outs[k].h) return fail(RRTMG_LW_HIP_EARG, "null output array");
+    add_spec_outs(outs, sp, L);
     auto body = [&](hipStream_t bs, int nb, int col0, std::vector<HostIn> &in, std::vector<HostOut> &out_) -> int {
         GcmIn g{in[0].d, in[1].d, in[2].d, in[3].d, in[4].d, in[5].d, in[6].d, in[7].d, in[8].d, in[9].d, in[10].d,
                 in[11].d, in[12].d, in[13].d, in[14].d, in[15].d, in[17].d, in[18].d, in[19].d, in[20].d, in[21].d, in[22].d, in[16].d};
         ColIn c{};
         FluxOut out{out_[0].d, out_[1].d, out_[2].d, out_[3].d, out_[4].d, out_[5].d, out_[6].d, out_[7].d, nullptr, nullptr};
+        put_spec_staged(out, out_);
         G.W.mask_col0 = (size_t)(col0 - c0);                      // staged arrays start at column 0, the mask holds the block's columns
         return run_batch<true>(bs, nb, 0, nb, nlay, mode, idrv, 1, 16, g, c, inflglw, iceflglw, liqflglw, out, nullptr);
     };
@@ -3299,9 +3442,10 @@ static int mcica_subcol_host_range(
 // the fused entry behind the lock (the caller holds it): argument checks, the columns over the devices
 static int mcica_subcol_host(int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw,
     const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp, const double *reice,
-    const double *reliq, const double *alpha, const double *tauaer, OUT_PARAMS)
+    const double *reliq, const double *alpha, const double *tauaer, OUT_PARAMS, const SpecOut *sp)
 {
     if (int rc = check_mcica_build()) return rc;
+    if (sp) if (int rc = check_spec(*sp)) return rc;
     if (!icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
     if (int rc = check_subcol_args(ncol, nlay, *icld, irng)) return rc;
     if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
@@ -3310,7 +3454,7 @@ static int mcica_subcol_host(int ncol, int nlay, int *icld, int idrv, int permut
     auto range = [&](int c0, int c1) -> int {
         return mcica_subcol_host_range(ncol, c0, c1, nlay, icld_gen, idrv, permuteseed, rng, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr,
                                        n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp,
-                                       reice, reliq, alpha, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt);
+                                       reice, reliq, alpha, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt, sp);
     };
     // the Mersenne-Twister stream (irng = 1) is ONE sequence over the (sub-column, column, layer) draws of the call
     // (src/mcica_subcol_gen_lw.f90:497-503): a column's deviates depend on every column before it, so the call stays on the first device
@@ -3344,6 +3488,14 @@ int rrtmg_lw_hip_run_mcica_subcol(
     return mcica_subcol_host(ncol, nlay, icld, idrv, permuteseed, irng, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr,
                              cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, alpha, tauaer,
                              uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt);
+}
+
+// the same with spectral outputs: does not join the combining entry (the entry lock, like any other call)
+int rrtmg_lw_hip_run_mcica_subcol_spectral(SUBCOL_PARAMS, SPEC_PARAMS)
+{
+    ENTRY_LOCK;
+    const SpecOut sp{uflxs, dflxs, uflxcs, dflxcs};
+    return mcica_subcol_host(SUBCOL_ARGS, &sp);
 }
 
 }  // extern "C"

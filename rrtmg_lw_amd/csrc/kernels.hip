@@ -218,6 +218,7 @@ struct McIn {
 struct FluxOut {
     double *uflx, *dflx, *hr, *uflxc, *dflxc, *hrc, *duflx_dt, *duflxc_dt;   // stride ncol_total
     double *fnet, *fnetc;                                                     // optional (column entry)
+    double *uflxs, *dflxs, *uflxcs, *dflxcs;                                  // optional spectral outputs (ncol_total, nlay+1, 16): written by the sweeps (SweepArgs)
 };
 
 enum ErrCode { E_NONE = 0, E_ICE_SMALL = 1, E_ICE_BOUNDS = 2, E_ICE_GEN_BOUNDS = 3, E_LIQ_BOUNDS = 4, E_BAD_FLAG = 5,
@@ -2782,7 +2783,16 @@ struct SweepArgs {
     const double *cldfrac;     // (nct,nlay)
     const double *tlay;        // (nct,nlay)     layer temperatures    (tlay | tavel)
     const double *tlev;        // (nct,nlay+1)   interface temperatures (tlev | tz)
+    // spectral outputs (the sweeps' SPEC instantiations only): per band the flux the band adds to the broadband one, x fluxfac,
+    // (nct,nlay+1,16) column fastest - element (i, k, b) at i + nct (k + (nlay + 1) b); clear-sky pair both null or both set
+    double *uflxs, *dflxs, *uflxcs, *dflxcs;
 };
+
+// index of (column gc, level lvl, band B) in a spectral output array
+__device__ __forceinline__ size_t spec_at(size_t gc, int lvl, int B, int nlay, int nct)
+{
+    return gc + (size_t)nct * ((size_t)lvl + (size_t)(nlay + 1) * (size_t)(B - 1));
+}
 
 // LDS of a sweep workgroup: transmittance table (float pairs), per band the Planck rows and the fraction rows
 #ifdef RRLW_SWEEP_EXPF
@@ -3094,7 +3104,8 @@ __device__ __forceinline__ double times(double x, double y)
 // NT threads (waves) per band, each with G = NQ / NT of its quads: the band's partial is the sum of their raw quad sums, formed - with the
 // band's weight - by the wave that adds the group (so a band split over two waves still rounds like one swept by a single thread).  Used
 // where all 16 g-points of a band with two streams would leave one wave per SIMD (sweepc_nt).
-template <int NQ, int PHASE, bool IDRV, int NT = 1>
+// SPEC: each band's flux of a level also goes, x fluxfac, to the caller's spectral arrays (SweepArgs::uflxs ..) at the lane's column.
+template <int NQ, int PHASE, bool IDRV, int NT = 1, bool SPEC = false>
 __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_waves(NQ / NT, PHASE, IDRV)) void k_sweepc(DevTables T, Workspace W, SweepArgs a)
 {
     static_assert(NQ % NT == 0 && (NT == 1 || NT == 2 || NT == 3), "threads per band");
@@ -3221,9 +3232,20 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
                     double pq = r[(unsigned)(q * NT * NC * ncw)];            // (the band's parts in the order one thread adds its quads: pairs first)
                     if constexpr (NT >= 2) pq = pq + r[(unsigned)((q * NT + 1) * NC * ncw)];
                     if constexpr (NT == 3) pq = pq + r[(unsigned)((q * NT + 2) * NC * ncw)];
-                    double v = (pq * 0.5) * T.delwave[(int)((bands >> (4 * q)) & 15ull)];
+                    const int bq = (int)((bands >> (4 * q)) & 15ull);
+                    double v = (pq * 0.5) * T.delwave[bq];
                     if (deriv) v = v * T.fluxfac;
                     sum = q == 0 ? v : sum + v;
+                    if constexpr (SPEC) {
+                        // one stream downward and in a cloud-free call: the clear-sky arrays take the same value
+                        if (incol && !deriv) {
+                            const size_t o = spec_at(gc, lvl, bq + 1, nlay, nct);
+                            const double f = v * T.fluxfac;
+                            if (DN) { a.dflxs[o] = f; if (a.dflxcs) a.dflxcs[o] = f; }
+                            else if (val == 0) { a.uflxs[o] = f; if (!TWO && a.uflxcs) a.uflxcs[o] = f; }
+                            else if (a.uflxcs) a.uflxcs[o] = f;
+                        }
+                    }
                 }
                 sv[val] = sum;
             }
@@ -3344,6 +3366,13 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
     if constexpr (DOWN) {
         // ------------------------------------------------------------------ downward: layers nlay .. lo
         if (incol && ty == 0) bstore_f64(gdn1 + (size_t)nlay * pcb, so8, 0.0);
+        if constexpr (SPEC) {
+            if (incol && part == 0) {
+                const size_t o = spec_at(gc, nlay, B, nlay, nct);
+                a.dflxs[o] = 0.0;
+                if (a.dflxcs) a.dflxcs[o] = 0.0;
+            }
+        }
         if (any_bin) sweep(true_type{}, true_type{}); else sweep(false_type{}, true_type{});
     }
     if constexpr (PHASE == 1) {                     // downward radiances at level ltop for k_sweepz
@@ -3452,7 +3481,8 @@ struct SweepzLev { double tl, tz, cf; unsigned w, flag; };
 
 // MODE: 1 rtrn (random overlap), 2 rtrnmr, 3 rtrnmc with per-g-point arrays, 4 rtrnmc with the generator's sub-column mask
 // IDRV: d(upward flux)/dT carried along (idrv = 1), src/rrtmg_lw_rtrnmr.f90:655-703 and its siblings
-template <int NQ, int MODE, bool IDRV = false>
+// SPEC: as in k_sweepc, every band's flux of a level also goes to the caller's spectral arrays
+template <int NQ, int MODE, bool IDRV = false, bool SPEC = false>
 __global__ __launch_bounds__(256 * sweepz_waves(NQ, IDRV), sweepz_waves(NQ, IDRV)) void k_sweepz(DevTables T, Workspace W, SweepArgs a)
 {
     static_assert(MODE >= 1 && MODE <= 4, "modes of the cloud-zone sweep");
@@ -3567,9 +3597,16 @@ __global__ __launch_bounds__(256 * sweepz_waves(NQ, IDRV), sweepz_waves(NQ, IDRV
                     if constexpr (NT >= 2) pq = pq + r[(unsigned)((q * NT + 1) * NC * ncw)];
                     if constexpr (NT == 3) pq = pq + r[(unsigned)((q * NT + 2) * NC * ncw)];
                     if constexpr (NT == 4) pq = pq + (r[(unsigned)((q * NT + 2) * NC * ncw)] + r[(unsigned)((q * NT + 3) * NC * ncw)]);
-                    double v = (pq * 0.5) * T.delwave[(int)((bands >> (4 * q)) & 15ull)];
+                    const int bq = (int)((bands >> (4 * q)) & 15ull);
+                    double v = (pq * 0.5) * T.delwave[bq];
                     if (val >= 2) v = v * T.fluxfac;
                     sum = q == 0 ? v : sum + v;
+                    if constexpr (SPEC) {
+                        if (incol && val < 2) {             // (total, clear; not their d/dT)
+                            double *dst = val == 0 ? (DN ? a.dflxs : a.uflxs) : (DN ? a.dflxcs : a.uflxcs);
+                            if (dst) dst[spec_at(gc, lvl, bq + 1, nlay, nct)] = v * T.fluxfac;
+                        }
+                    }
                 }
                 sv[val] = sum;
             }
@@ -3595,6 +3632,13 @@ __global__ __launch_bounds__(256 * sweepz_waves(NQ, IDRV), sweepz_waves(NQ, IDRV
 #pragma unroll                      // kernel walking all levels (k_blocksort, force_top) no clear-sky launch has written the hand-off array
             for (int j = 0; j < NG; j++) rad[j] = 0.0;
             if (incol && ty == 0) bstore_f64(W.gdn1 + gslab + (size_t)nlay * pcb, (unsigned)col * 8u, 0.0);      // downward flux at the top level
+            if constexpr (SPEC) {
+                if (incol && part == 0) {
+                    const size_t o = spec_at(gc, nlay, B, nlay, nct);
+                    a.dflxs[o] = 0.0;
+                    if (a.dflxcs) a.dflxcs[o] = 0.0;
+                }
+            }
         }
 #pragma unroll
         for (int j = 0; j < NG; j++) radc[j] = rad[j];

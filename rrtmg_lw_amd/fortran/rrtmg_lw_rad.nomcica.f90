@@ -31,6 +31,21 @@
             type(c_ptr), value :: duflx_dt, duflxc_dt
             integer(c_int) :: rc
          end function rrtmg_lw_hip_run_nomcica
+         function rrtmg_lw_hip_run_nomcica_spectral(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, &
+               h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, &
+               inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer, &
+               uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt, &
+               uflxs, dflxs, uflxcs, dflxcs) bind(C, name='rrtmg_lw_hip_run_nomcica_spectral') result(rc)
+            import :: c_int, c_double, c_ptr
+            integer(c_int), value :: ncol, nlay, idrv, inflglw, iceflglw, liqflglw
+            integer(c_int), intent(inout) :: icld
+            real(c_double), intent(in) :: play(*), plev(*), tlay(*), tlev(*), tsfc(*), h2ovmr(*), o3vmr(*), co2vmr(*)
+            real(c_double), intent(in) :: ch4vmr(*), n2ovmr(*), o2vmr(*), cfc11vmr(*), cfc12vmr(*), cfc22vmr(*), ccl4vmr(*)
+            real(c_double), intent(in) :: emis(*), cldfr(*), taucld(*), cicewp(*), cliqwp(*), reice(*), reliq(*), tauaer(*)
+            real(c_double), intent(out) :: uflx(*), dflx(*), hr(*), uflxc(*), dflxc(*), hrc(*)
+            type(c_ptr), value :: duflx_dt, duflxc_dt, uflxs, dflxs, uflxcs, dflxcs
+            integer(c_int) :: rc
+         end function rrtmg_lw_hip_run_nomcica_spectral
       end interface
 
       contains
@@ -44,7 +59,8 @@
              taucld  ,cicewp  ,cliqwp  ,reice   ,reliq   , &
              tauaer  , &
              uflx    ,dflx    ,hr      ,uflxc   ,dflxc,  hrc, &
-             duflx_dt,duflxc_dt )
+             duflx_dt,duflxc_dt, &
+             uflxs   ,dflxs   ,uflxcs  ,dflxcs )
 
       integer(kind=im), intent(in) :: ncol            ! Number of horizontal columns
       integer(kind=im), intent(in) :: nlay            ! Number of model layers
@@ -65,11 +81,19 @@
       real(kind=rb), intent(in) :: tauaer(:,:,:)      ! Aerosol optical depth               (ncol,nlay,nbndlw)
       real(kind=rb), intent(out) :: uflx(:,:), dflx(:,:), hr(:,:), uflxc(:,:), dflxc(:,:), hrc(:,:)
       real(kind=rb), intent(out), optional, target :: duflx_dt(:,:), duflxc_dt(:,:)
+      ! Spectral outputs (optional, this library's extension; include/rrtmg_lw_hip.h, "Spectral (per-band) fluxes"):
+      ! per band the flux the band adds to uflx / dflx / uflxc / dflxc, (ncol,nlay+1,nbndlw), band 16 in the broadband
+      ! call's convention (2600 cm-1 to infinity).  uflxs and dflxs together; uflxcs and dflxcs together, or neither.
+      ! Absent: the plain call.
+      real(kind=rb), intent(out), optional, target :: uflxs(:,:,:), dflxs(:,:,:), uflxcs(:,:,:), dflxcs(:,:,:)
 
       integer(c_int) :: rc, icld_c
       real(c_double), allocatable, target :: d1(:,:), d2(:,:)
       type(c_ptr) :: p1, p2
       logical :: inplace
+      real(c_double), allocatable, target :: s1(:,:,:), s2(:,:,:), s3(:,:,:), s4(:,:,:)
+      type(c_ptr) :: q1, q2, q3, q4
+      logical :: spectral
 
       icld_c = int(icld, c_int)
       p1 = c_null_ptr
@@ -107,16 +131,48 @@
       call check_extent('taucld', size(taucld,2), size(taucld,3), ncol, nlay)
       call check_extent('uflx', size(uflx,1), size(uflx,2), ncol, nlay+1)
       call check_extent('hr', size(hr,1), size(hr,2), ncol, nlay)
-      rc = rrtmg_lw_hip_run_nomcica(int(ncol, c_int), int(nlay, c_int), icld_c, int(idrv, c_int), &
-            play(1:ncol,1:nlay), plev(1:ncol,1:nlay+1), tlay(1:ncol,1:nlay), tlev(1:ncol,1:nlay+1), tsfc(1:ncol), &
-            h2ovmr(1:ncol,1:nlay), o3vmr(1:ncol,1:nlay), co2vmr(1:ncol,1:nlay), ch4vmr(1:ncol,1:nlay), &
-            n2ovmr(1:ncol,1:nlay), o2vmr(1:ncol,1:nlay), cfc11vmr(1:ncol,1:nlay), cfc12vmr(1:ncol,1:nlay), &
-            cfc22vmr(1:ncol,1:nlay), ccl4vmr(1:ncol,1:nlay), emis(1:ncol,1:16), &
-            int(inflglw, c_int), int(iceflglw, c_int), int(liqflglw, c_int), &
-            cldfr(1:ncol,1:nlay), taucld(1:16,1:ncol,1:nlay), cicewp(1:ncol,1:nlay), cliqwp(1:ncol,1:nlay), &
-            reice(1:ncol,1:nlay), reliq(1:ncol,1:nlay), tauaer(1:ncol,1:nlay,1:16), &
-            uflx(1:ncol,1:nlay+1), dflx(1:ncol,1:nlay+1), hr(1:ncol,1:nlay), &
-            uflxc(1:ncol,1:nlay+1), dflxc(1:ncol,1:nlay+1), hrc(1:ncol,1:nlay), p1, p2)
+      spectral = present(uflxs) .or. present(dflxs) .or. present(uflxcs) .or. present(dflxcs)
+      q3 = c_null_ptr
+      q4 = c_null_ptr
+      if (spectral) then
+         if (.not. (present(uflxs) .and. present(dflxs))) then
+            write(*,*) 'rrtmg_lw: spectral outputs need uflxs and dflxs'
+            error stop 1
+         endif
+         if (present(uflxcs) .neqv. present(dflxcs)) then
+            write(*,*) 'rrtmg_lw: uflxcs and dflxcs go together'
+            error stop 1
+         endif
+         call spec_arg('uflxs', uflxs, s1, q1, ncol, nlay)
+         call spec_arg('dflxs', dflxs, s2, q2, ncol, nlay)
+         if (present(uflxcs)) then
+            call spec_arg('uflxcs', uflxcs, s3, q3, ncol, nlay)
+            call spec_arg('dflxcs', dflxcs, s4, q4, ncol, nlay)
+         endif
+      endif
+      if (spectral) then
+         rc = rrtmg_lw_hip_run_nomcica_spectral(int(ncol, c_int), int(nlay, c_int), icld_c, int(idrv, c_int), &
+               play(1:ncol,1:nlay), plev(1:ncol,1:nlay+1), tlay(1:ncol,1:nlay), tlev(1:ncol,1:nlay+1), tsfc(1:ncol), &
+               h2ovmr(1:ncol,1:nlay), o3vmr(1:ncol,1:nlay), co2vmr(1:ncol,1:nlay), ch4vmr(1:ncol,1:nlay), &
+               n2ovmr(1:ncol,1:nlay), o2vmr(1:ncol,1:nlay), cfc11vmr(1:ncol,1:nlay), cfc12vmr(1:ncol,1:nlay), &
+               cfc22vmr(1:ncol,1:nlay), ccl4vmr(1:ncol,1:nlay), emis(1:ncol,1:16), &
+               int(inflglw, c_int), int(iceflglw, c_int), int(liqflglw, c_int), &
+               cldfr(1:ncol,1:nlay), taucld(1:16,1:ncol,1:nlay), cicewp(1:ncol,1:nlay), cliqwp(1:ncol,1:nlay), &
+               reice(1:ncol,1:nlay), reliq(1:ncol,1:nlay), tauaer(1:ncol,1:nlay,1:16), &
+               uflx(1:ncol,1:nlay+1), dflx(1:ncol,1:nlay+1), hr(1:ncol,1:nlay), &
+               uflxc(1:ncol,1:nlay+1), dflxc(1:ncol,1:nlay+1), hrc(1:ncol,1:nlay), p1, p2, q1, q2, q3, q4)
+      else
+         rc = rrtmg_lw_hip_run_nomcica(int(ncol, c_int), int(nlay, c_int), icld_c, int(idrv, c_int), &
+               play(1:ncol,1:nlay), plev(1:ncol,1:nlay+1), tlay(1:ncol,1:nlay), tlev(1:ncol,1:nlay+1), tsfc(1:ncol), &
+               h2ovmr(1:ncol,1:nlay), o3vmr(1:ncol,1:nlay), co2vmr(1:ncol,1:nlay), ch4vmr(1:ncol,1:nlay), &
+               n2ovmr(1:ncol,1:nlay), o2vmr(1:ncol,1:nlay), cfc11vmr(1:ncol,1:nlay), cfc12vmr(1:ncol,1:nlay), &
+               cfc22vmr(1:ncol,1:nlay), ccl4vmr(1:ncol,1:nlay), emis(1:ncol,1:16), &
+               int(inflglw, c_int), int(iceflglw, c_int), int(liqflglw, c_int), &
+               cldfr(1:ncol,1:nlay), taucld(1:16,1:ncol,1:nlay), cicewp(1:ncol,1:nlay), cliqwp(1:ncol,1:nlay), &
+               reice(1:ncol,1:nlay), reliq(1:ncol,1:nlay), tauaer(1:ncol,1:nlay,1:16), &
+               uflx(1:ncol,1:nlay+1), dflx(1:ncol,1:nlay+1), hr(1:ncol,1:nlay), &
+               uflxc(1:ncol,1:nlay+1), dflxc(1:ncol,1:nlay+1), hrc(1:ncol,1:nlay), p1, p2)
+      endif
       if (rc /= 0) call rrtmg_lw_hip_abort('rrtmg_lw')
       icld = int(icld_c, im)
       if (idrv == 1 .and. .not. inplace) then
@@ -124,7 +180,32 @@
          duflxc_dt(1:ncol, 1:nlay+1) = d2
       endif
 
+      if (allocated(s1)) uflxs(1:ncol, 1:nlay+1, 1:16) = s1
+      if (allocated(s2)) dflxs(1:ncol, 1:nlay+1, 1:16) = s2
+      if (allocated(s3)) uflxcs(1:ncol, 1:nlay+1, 1:16) = s3
+      if (allocated(s4)) dflxcs(1:ncol, 1:nlay+1, 1:16) = s4
+
       end subroutine rrtmg_lw
+
+      ! a spectral output (ncol,nlay+1,16): exactly sized, contiguous actuals go across in place (like duflx_dt);
+      ! larger or strided ones through the temporary t, copied back after the call
+      subroutine spec_arg(name, a, t, p, ncol, nlay)
+      character(len=*), intent(in) :: name
+      real(kind=rb), intent(inout), target :: a(:,:,:)
+      real(c_double), allocatable, target, intent(inout) :: t(:,:,:)
+      type(c_ptr), intent(out) :: p
+      integer(kind=im), intent(in) :: ncol, nlay
+      if (size(a,1) < ncol .or. size(a,2) < nlay+1 .or. size(a,3) < 16) then
+         write(*,'(a,a,a)') 'rrtmg_lw: ', name, ' smaller than (ncol, nlay+1, 16)'
+         error stop 1
+      endif
+      if (size(a,1) == ncol .and. size(a,2) == nlay+1 .and. size(a,3) == 16 .and. is_contiguous(a)) then
+         p = c_loc(a)
+      else
+         allocate(t(ncol, nlay+1, 16))
+         p = c_loc(t)
+      endif
+      end subroutine spec_arg
 
       subroutine check_extent(name, n1, n2, ncol, nl)
       character(len=*), intent(in) :: name

@@ -419,6 +419,48 @@ int rrtmg_lw_hip_host_changed(const void *ptr, int keep);
  * the combining entry and the device passes that served them, since the library was loaded. */
 void rrtmg_lw_hip_combine_stats(long long *calls, long long *passes);
 
+/* ---- Gas optics and Planck sources -----------------------------------------------------------------------------------------------
+ * What the solver forms between its inputs and its sweeps, for hosts with a solver of their own (scattering, multi-stream, "gas optics +
+ * sources" interop) and for emulator training data.  No cloud or aerosol arrays are taken and none of the solver's outputs formed.
+ *   taug  (ncol, nlay, NG)       taumol's taug(lay, ig) (src/rrtmg_lw_taumol.f90): the GAS optical depth only - no aerosol, no diffusivity
+ *                                secant (secdiff), no clamp: a negative interpolated value stays negative.  NG = rrtmg_lw_hip_gpoints()
+ *                                (140, or 256 in librrtmg_lw_hip_g256.so); g-points band by band as in the reference.  Band 16 above
+ *                                laytrop as the reference forms it: with nspb(16) = 0 (src/rrtmg_lw_init.f90:228) its table indices are 1
+ *                                in every layer (absb rows 1 and 2 with the layer's weights); the solver itself indexes that table by (jp, jt).
+ *   fracs (ncol, nlay, NG)       taumol's Planck fraction per g-point.  (The solver's sweeps carry the mixture weight of the binary-key bands
+ *                                in 28 bits; these are formed with the full weight, as the reference forms them.)
+ *   planklay (ncol, nlay, 16)    setcoef's planklay;  planklev (ncol, nlay+1, 16): setcoef's planklev(0:nlay), level 0 = the surface
+ *   plankbnd (ncol, 16)          setcoef's plankbnd, which includes semiss (emis);  dplankbnd_dt (ncol, 16): its d/dT
+ *                                (src/rrtmg_lw_setcoef.f90:173-269).  Band 16 as in a broadband call (istart = 1), like the spectral outputs.
+ * Layout: column fastest, the g-point or band index last: element (i, k, g) at i + ncol*(k + nlay*g) (0-based), like tauaer and the
+ * spectral outputs.  Layer 1 is the surface layer.  The solver's own optical depth of a cell is secdiff(band) * (taug + taua(band)).
+ * taug and fracs are required.  Each Planck output may be NULL: it is then neither formed nor stored.  dplankbnd_dt is required with
+ * idrv = 1; with idrv = 0 it may be NULL and is left untouched.  Inputs as for rrtmg_lw_hip_run_nomcica (inatm's hydrostatic amounts);
+ * errors: RRTMG_LW_HIP_EARG for null required arrays and bad dimensions (the limits of the other entries).
+ * The host entry splits the columns over the devices of rrtmg_lw_hip_init_devices like rrtmg_lw_hip_run_nomcica.  The device entry takes
+ * device pointers laid out as above, enqueues on `stream`, runs on the state of the arrays' device and does not synchronise:
+ * rrtmg_lw_hip_check(stream) reports errors, as for the other device entries.  These entries take the entry lock like any other call
+ * (no combining, no graph replay). */
+int rrtmg_lw_hip_gas_optics(int ncol, int nlay, int idrv,
+    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
+    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
+    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
+    const double *ccl4vmr, const double *emis,
+    double *taug, double *fracs, double *planklay, double *planklev, double *plankbnd, double *dplankbnd_dt);
+int rrtmg_lw_hip_gas_optics_device(int ncol, int nlay, int idrv,
+    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
+    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
+    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
+    const double *ccl4vmr, const double *emis,
+    double *taug, double *fracs, double *planklay, double *planklev, double *plankbnd, double *dplankbnd_dt, void *stream);
+/* The same for prepared columns: the arguments of rrtmg_lw_hip_run_columns up to pwvcm (src/rrtmg_lw.1col.f90:497-580, semiss in place of
+ * emis); at most one batch of columns per call, like rrtmg_lw_hip_run_columns. */
+int rrtmg_lw_hip_gas_optics_columns(int ncol, int nlayers, int idrv,
+    const double *pavel, const double *tavel, const double *pz, const double *tz, const double *tbound,
+    const double *semiss, const double *coldry, const double *wkl, const double *wbrodl, const double *wx,
+    const double *pwvcm,
+    double *taug, double *fracs, double *planklay, double *planklev, double *plankbnd, double *dplankbnd_dt);
+
 /* PMC calibration: one kernel that reads `bytes` and writes `bytes` with 16 B per lane (known HBM traffic), so that a
  * rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE pass can fix the counters' unit and scale in the same session. */
 int rrtmg_lw_hip_calibrate_stream(long long bytes);

@@ -401,6 +401,72 @@ def run_columns(cols, istart=1, iend=16, icld=None, idrv=None):
 
 
 # ---------------------------------------------------------------------------------------------------
+# Gas optics and Planck sources (include/rrtmg_lw_hip.h, "Gas optics and Planck sources")
+# ---------------------------------------------------------------------------------------------------
+_OPTICS = ("taug", "fracs", "planklay", "planklev", "plankbnd", "dplankbnd_dt")
+
+
+def _optics_shapes(ncol, nlay):
+    ng = gpoints()
+    return dict(taug=(ncol, nlay, ng), fracs=(ncol, nlay, ng), planklay=(ncol, nlay, NBND), planklev=(ncol, nlay + 1, NBND),
+                plankbnd=(ncol, NBND), dplankbnd_dt=(ncol, NBND))
+
+
+def _optics_ptrs(out, ncol, nlay, idrv):
+    """pointers to the gas-optics outputs of `out` (created there where missing; dplankbnd_dt only with idrv = 1); a Planck output the
+    caller sets to None is not formed"""
+    shapes = _optics_shapes(ncol, nlay)
+    for k in _OPTICS:
+        if k not in out and (k != "dplankbnd_dt" or idrv == 1):
+            out[k] = np.empty(shapes[k], order="F")
+    for k in ("taug", "fracs"):
+        if out[k] is None:
+            raise ValueError(f"gas optics: {k} is required")
+    return [_p(_out_ok(out[k], shapes[k], k)) if out.get(k) is not None else C.cast(None, _dp) for k in _OPTICS]
+
+
+def gas_optics(d, idrv=0, out=None):
+    """Gas optical depth and Planck fraction per g-point, Planck integrals per band (rrtmg_lw_hip_gas_optics) for the GCM inputs of
+    rrtmg_lw_from_dict (cloud and aerosol entries of `d` are not used).  Returns a dict of Fortran-ordered arrays: taug, fracs
+    (ncol, nlay, ngpt), planklay (ncol, nlay, 16), planklev (ncol, nlay+1, 16), plankbnd (ncol, 16) and, with idrv = 1, dplankbnd_dt
+    (ncol, 16).  `out` may hold preallocated arrays; a Planck output set to None there is not formed."""
+    ncol, nlay = int(d["ncol"]), int(d["nlay"])
+    a = _gcm_arrays(ncol, nlay, *[d[k] for k in ("play", "plev", "tlay", "tlev", "tsfc")],
+                    [d[k] for k in _GCM_ORDER[5:15]], d["emis"])
+    out = {} if out is None else out
+    ptrs = _optics_ptrs(out, ncol, nlay, idrv)
+    _check(lib().rrtmg_lw_hip_gas_optics(C.c_int(ncol), C.c_int(nlay), C.c_int(int(idrv)), *[_p(x) for x in a], *ptrs))
+    return out
+
+
+def gas_optics_device(d, out, stream=None, idrv=None):
+    """Device-resident gas optics (rrtmg_lw_hip_gas_optics_device): `d` as for rrtmg_lw_device (torch tensors, column fastest), `out` a
+    dict of preallocated float64 tensors laid out column fastest, g-point / band last - taug, fracs of shape (ngpt, nlay, ncol), planklay
+    (16, nlay, ncol), planklev (16, nlay+1, ncol), plankbnd, dplankbnd_dt (16, ncol); the Planck ones optional.  Enqueues on `stream`
+    and returns; call check(stream) to synchronise.  idrv: d["idrv"] unless given."""
+    idrv = d["idrv"] if idrv is None else idrv
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    args = [C.c_int(d["ncol"]), C.c_int(d["nlay"]), C.c_int(int(idrv))] + [ptr(d[k]) for k in _GCM_ORDER]
+    args += [ptr(out.get(k)) for k in _OPTICS]
+    _check(lib().rrtmg_lw_hip_gas_optics_device(*args, C.c_void_p(stream or 0)))
+
+
+def gas_optics_columns(cols, idrv=0, out=None):
+    """Gas optics for prepared columns (rrtmg_lw_hip_gas_optics_columns): `cols` as for run_columns (at most one batch).  Returns the
+    dict of gas_optics."""
+    n = len(cols)
+    nl = int(cols[0]["nlayers"])
+    st = lambda key, shape: _f(np.stack([np.asarray(c[key], dtype=np.float64).reshape(shape[1:], order="F") for c in cols]), shape)
+    a = [st("pavel", (n, nl)), st("tavel", (n, nl)), st("pz", (n, nl + 1)), st("tz", (n, nl + 1)),
+         _f(np.array([float(c["tbound"]) for c in cols]), (n,)), st("semiss", (n, NBND)), st("coldry", (n, nl)), st("wkl", (n, 7, nl)),
+         st("wbrodl", (n, nl)), st("wx", (n, 4, nl)), _f(np.array([float(c["pwvcm"]) for c in cols]), (n,))]
+    out = {} if out is None else out
+    ptrs = _optics_ptrs(out, n, nl, idrv)
+    _check(lib().rrtmg_lw_hip_gas_optics_columns(C.c_int(n), C.c_int(nl), C.c_int(int(idrv)), *[_p(x) for x in a], *ptrs))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
 # McICA flavour: reference src/rrtmg_lw_rad.f90:99-108, src/mcica_subcol_gen_lw.f90:68,183
 # ---------------------------------------------------------------------------------------------------
 def _out_arrays(ncol, nlay, idrv):

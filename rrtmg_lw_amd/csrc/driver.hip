@@ -56,8 +56,15 @@ struct State {
     size_t ws_bytes = 0;
     int ws_nlay = 0, ws_ncolb = 0;
     bool ws_cloud = false, ws_mc = false, ws_gdp = false, ws_efcl = false, ws_ovl = false;
+    // the gas-optics entries' own small workspace (k_colprep's per-column terms, k_optics' wide-window list): none of the solver's
+    // codes, partials or cloud arrays
+    void *opt_base = nullptr;
+    size_t opt_bytes = 0;
+    int opt_nlay = 0, opt_ncolb = 0;
+    double *opt_percol = nullptr;
+    int *opt_laytrop = nullptr, *opt_wide = nullptr;
     int ws_groups = 0;
-    size_t ws_slabcols = 0;      // capacity of each partial slab array (gdn1 ..) in columns x slabs: ws_groups wide slabs, or - a small batch whose bands
+    size_t ws_slabcols = 0;     // capacity of each partial slab array (gdn1 ..) in columns x slabs: ws_groups wide slabs, or - a small batch whose bands
                                  // leave a slab each (split sweeps) - sixteen narrow ones
     int *d_err = nullptr;
     // per-column / cloud-property arrays exist twice: k_colprep + k_cloudscan / k_cloudlay of batch i+1 run on `aux` while batch i is in k_layer/k_sweep
@@ -639,6 +646,25 @@ int run_prep(hipStream_t s, const Workspace &Wk, int nb, int col0, int nct, int 
     return 0;
 }
 
+// the arguments of a k_layer / k_optics launch over nb columns
+LayerArgs layer_args(int nb, int col0, int nct, int nlay, int idrv, int istart, int iend, const double *tauaer)
+{
+    LayerArgs la;
+    la.ncol = nb; la.col0 = col0; la.nct = nct; la.idrv = idrv; la.istart = istart; la.iend = iend;
+    la.ktab_bytes = (int)(G.H.ktab.size() * 8);
+    la.tauaer = tauaer;
+    const unsigned gx = (nb + LAYER_BLOCK - 1) / LAYER_BLOCK;
+    // A batch whose (window, layer) pairs do not fill the chip - 768 workgroups at three per CU - spreads the bands of a pair over two or
+    // four workgroups (k_layer: LayerArgs::partmask): a workgroup's sixteen bands are a 100 us chain, and a small call waits for ONE round
+    // of them.  The parts follow the staging passes (a workgroup stages only the passes it has a band of).
+    const auto bits = [](std::initializer_list<int> bands) { unsigned m = 0; for (int b : bands) m |= 1u << (b - 1); return m; };
+    const unsigned quarter[4] = {bits({1, 2, 11, 15, 6}), bits({8, 10, 14, 16, 12, 13}), bits({4, 9, 7}), bits({3, 5})};
+    const unsigned pairs_ = gx * (unsigned)nlay;
+    la.nparts = !g_layer_split ? 1 : (pairs_ * 4 <= 1152 ? 4 : (pairs_ * 2 <= 1152 ? 2 : 1));
+    for (int p = 0; p < 4; p++) la.partmask[p] = la.nparts == 4 ? quarter[p] : (la.nparts == 2 && p < 2 ? (quarter[2 * p] | quarter[2 * p + 1]) : 0xffffu);
+    return la;
+}
+
 // layer-local part of one batch (k_cloudmc, k_layer groups), everything device-resident.  mode: 0 clear, 1 rtrn, 2 rtrnmr,
 // 3 rtrnmc (McICA; `mc` = the sub-column arrays, or null when the sub-columns come from the generator's mask in Wk.mask)
 template <bool GCM>
@@ -652,19 +678,8 @@ int run_layer(hipStream_t s, const Workspace &Wk, int nb, int col0, int nct, int
         else LAUNCH("k_cloudmc<mask>", (k_cloudmc<true>), cgrid, block, s, G.D, Wk, McIn{}, g, nb, col0, nct, inflag, iceflag, liqflag);
         LAUNCH("k_blocksort", k_blocksort, dim3(1), dim3(256), s, Wk, (nb + 63) / 64, one_sweep(nb, mode) ? 1 : 0);
     }
-    LayerArgs la;
-    la.ncol = nb; la.col0 = col0; la.nct = nct; la.idrv = idrv; la.istart = istart; la.iend = iend;
-    la.ktab_bytes = (int)(G.H.ktab.size() * 8);
-    la.tauaer = GCM ? g.tauaer : c.taua;
+    const LayerArgs la = layer_args(nb, col0, nct, nlay, idrv, istart, iend, GCM ? g.tauaer : c.taua);
     const unsigned gx = (nb + LAYER_BLOCK - 1) / LAYER_BLOCK;
-    // A batch whose (window, layer) pairs do not fill the chip - 768 workgroups at three per CU - spreads the bands of a pair over two or
-    // four workgroups (k_layer: LayerArgs::partmask): a workgroup's sixteen bands are a 100 us chain, and a small call waits for ONE round
-    // of them.  The parts follow the staging passes (a workgroup stages only the passes it has a band of).
-    const auto bits = [](std::initializer_list<int> bands) { unsigned m = 0; for (int b : bands) m |= 1u << (b - 1); return m; };
-    const unsigned quarter[4] = {bits({1, 2, 11, 15, 6}), bits({8, 10, 14, 16, 12, 13}), bits({4, 9, 7}), bits({3, 5})};
-    const unsigned pairs_ = gx * (unsigned)nlay;
-    la.nparts = !g_layer_split ? 1 : (pairs_ * 4 <= 1152 ? 4 : (pairs_ * 2 <= 1152 ? 2 : 1));
-    for (int p = 0; p < 4; p++) la.partmask[p] = la.nparts == 4 ? quarter[p] : (la.nparts == 2 && p < 2 ? (quarter[2 * p] | quarter[2 * p + 1]) : 0xffffu);
     const dim3 lgrid(gx, nlay, la.nparts), lblock(LAYER_BLOCK);
     // the wide-window pass over the (window, layer) pairs the narrow launch could not take (GCM entry; kernels.hip: StageWin): as many
     // workgroups as fit the chip at once, which leave at once when the list is empty
@@ -867,6 +882,56 @@ int run_batch(hipStream_t s, int nb, int col0, int nct, int nlay, int mode, int 
     if (int rc = run_prep<GCM>(s, Wk, nb, col0, nct, mode, idrv, istart, g, c, inflag, iceflag, liqflag)) return rc;
     if (int rc = run_layer<GCM>(s, Wk, nb, col0, nct, nlay, mode, idrv, istart, iend, g, c, inflag, iceflag, liqflag, mc)) return rc;
     return run_sweep<GCM>(s, Wk, nb, col0, nct, nlay, mode, idrv, istart, iend, g, c, out, mc);
+}
+
+// ---- gas optics (rrtmg_lw_hip_gas_optics*) ------------------------------------------------------------------------------------------
+// The optics pipeline of a batch is k_colprep (laytrop, the surface Planck terms) and k_optics.  It needs none of the solver's workspace -
+// no cell codes, partial slabs or cloud arrays - only the per-column terms and k_optics' wide-window list, in an allocation of its own.
+int ensure_optics_ws(int nlay, int ncolb)
+{
+    if (G.opt_base && G.opt_nlay == nlay && G.opt_ncolb >= ncolb) return 0;
+    if (G.opt_base) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(G.opt_base)); G.opt_base = nullptr; G.opt_bytes = 0; }
+    ncolb = std::max(ncolb, G.opt_nlay == nlay ? G.opt_ncolb : 0);
+    const size_t n = (size_t)ncolb, L = (size_t)nlay;
+    const size_t b_pc = align_up((size_t)NPERCOL * n * 8, 256), b_lt = align_up(n * 4, 256);
+    const size_t b_wide = align_up((2 + ((n + LAYER_BLOCK - 1) / LAYER_BLOCK) * L) * 4, 256);
+    HIP_TRY(hipMalloc(&G.opt_base, b_pc + b_lt + b_wide));
+    G.opt_percol = (double *)G.opt_base;
+    G.opt_laytrop = (int *)((char *)G.opt_base + b_pc);
+    G.opt_wide = (int *)((char *)G.opt_base + b_pc + b_lt);
+    HIP_TRY(hipMemset(G.opt_wide, 0, 8));
+    G.opt_bytes = b_pc + b_lt + b_wide;
+    G.opt_nlay = nlay;
+    G.opt_ncolb = ncolb;
+    return 0;
+}
+
+// one batch of the gas-optics entries on stream s: columns col0 .. col0 + nb - 1 of arrays nct columns wide (inputs and outputs alike)
+template <bool GCM>
+int run_optics(hipStream_t s, int nb, int col0, int nct, int nlay, int idrv, const GcmIn &g, const ColIn &c, const OptOut &o)
+{
+    Workspace W{};
+    W.ncolb = G.opt_ncolb; W.pcb = G.opt_ncolb; W.nlay = nlay; W.err = G.d_err;
+    W.percol = G.opt_percol; W.laytrop = G.opt_laytrop;
+    W.wide = GCM && HAVE_WIDE && g_wide_window ? G.opt_wide : nullptr;
+    LAUNCH("k_colprep", (k_colprep<GCM>), dim3((nb + 63) / 64), dim3(64), s, G.D, W, g, c, nb, col0, nct, idrv, 1, 0);
+    const LayerArgs la = layer_args(nb, col0, nct, nlay, idrv, 1, 16, nullptr);
+    const unsigned gx = (nb + LAYER_BLOCK - 1) / LAYER_BLOCK;
+    if (W.wide) HIP_TRY(hipMemsetAsync(W.wide, 0, sizeof(int), s));
+    LAUNCH("k_optics", (k_optics<GCM, 0>), dim3(gx, nlay, la.nparts), dim3(LAYER_BLOCK), s, G.D, W, g, c, la, o);
+    if constexpr (GCM && HAVE_WIDE) {
+        if (W.wide) LAUNCH("k_optics<wide>", (k_optics<true, 1>), dim3(gx * nlay, la.nparts), dim3(LAYER_BLOCK), s, G.D, W, g, c, la, o);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int check_optics(int idrv, const OptOut &o)
+{
+    if (!o.taug || !o.fracs) return fail(RRTMG_LW_HIP_EARG, "gas optics: taug and fracs are required");
+    if (idrv == 1 && !o.dplankbnd) return fail(RRTMG_LW_HIP_EARG, "gas optics: idrv=1 needs dplankbnd_dt");
+    return 0;
 }
 
 int ensure_pipeline()
@@ -2063,6 +2128,7 @@ static void finalize_state()
     graphs_clear();
     if (G.cap) { (void)hipStreamDestroy(G.cap); G.cap = nullptr; }
     if (G.ws_base) (void)hipFree(G.ws_base);
+    if (G.opt_base) (void)hipFree(G.opt_base);
     if (G.stage_base) (void)hipFree(G.stage_base);
     if (first) {            // the queue and the generator's caches live on the first device
         if (Q.pinned) { forget_pinned(Q.pinned); (void)hipHostFree(Q.pinned); Q.pinned = nullptr; Q.pinned_doubles = 0; }
@@ -2285,7 +2351,7 @@ long long rrtmg_lw_hip_workspace_bytes(void)
     size_t tot = 0;
     for (int d = 0; d < g_ndev; d++) {
         const State &S = g_states[d];
-        tot += S.ws_bytes + S.stage_bytes + S.mask_bytes + S.rnd_bytes + (S.kiss.dev ? sizeof(KissJump) * (KJ_NGROUP + 1) : 0);
+        tot += S.ws_bytes + S.opt_bytes + S.stage_bytes + S.mask_bytes + S.rnd_bytes + (S.kiss.dev ? sizeof(KissJump) * (KJ_NGROUP + 1) : 0);
     }
     for (const MtStates &M : g_mt) tot += M.bytes();
     return (long long)tot;
@@ -2652,6 +2718,119 @@ int rrtmg_lw_hip_run_columns(
     HIP_TRY(hipStreamSynchronize(s));
     for (int k = 0; k < 10; k++) if (int rc = bounce_d2h(ho[k], o[k], n * (L + 1) * 8)) return rc;
     return read_physics_error(s);
+}
+
+// ---- gas optics and Planck sources (include/rrtmg_lw_hip.h) ---------------------------------------------------------------------------
+#define OPTICS_GCM_PARAMS                                                                                       \
+    int ncol, int nlay, int idrv,                                                                               \
+    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,         \
+    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr, \
+    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,               \
+    const double *ccl4vmr, const double *emis,                                                                 \
+    double *taug, double *fracs, double *planklay, double *planklev, double *plankbnd, double *dplankbnd_dt
+
+int rrtmg_lw_hip_gas_optics_device(OPTICS_GCM_PARAMS, void *stream)
+{
+    ENTRY_LOCK_FOR(play);
+    if (int rc = check_common(ncol, nlay)) return rc;
+    const OptOut o{taug, fracs, planklay, planklev, plankbnd, idrv == 1 ? dplankbnd_dt : nullptr};
+    if (int rc = check_optics(idrv, o)) return rc;
+    const double *in[] = {play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis};
+    for (const double *p : in) if (!p) return fail(RRTMG_LW_HIP_EARG, "gas optics: null input array");
+    if (int rc = ensure_pipeline()) return rc;
+    const int nbmax = balanced_batch(ncol, eff_batch(nlay));
+    if (int rc = ensure_optics_ws(nlay, nbmax)) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last, 0));      // an earlier call, possibly on another stream, still owns the workspace
+    const GcmIn g{play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis};
+    for (int col0 = 0; col0 < ncol; col0 += nbmax)
+        if (int rc = run_optics<true>(s, std::min(nbmax, ncol - col0), col0, ncol, nlay, idrv, g, ColIn{}, o)) return rc;
+    HIP_TRY(hipEventRecord(G.ev_last, s));
+    G.ev_last_valid = true;
+    return 0;
+}
+
+// columns [c0, c1) of a host-pointer gas-optics call on the calling thread's current device state (the fan-out's worker); no lock taken
+static int gas_optics_host_range(int c0, int c1, OPTICS_GCM_PARAMS)
+{
+    HIP_TRY(hipDeviceSynchronize());        // asynchronous device-entry work of earlier calls shares the workspace
+    const size_t L = (size_t)nlay;
+    std::vector<HostIn> ins = {
+        {play, 1, L, 0}, {plev, 1, L + 1, 0}, {tlay, 1, L, 0}, {tlev, 1, L + 1, 0}, {tsfc, 1, 1, 0},
+        {h2ovmr, 1, L, 0}, {o3vmr, 1, L, 0}, {co2vmr, 1, L, 0}, {ch4vmr, 1, L, 0}, {n2ovmr, 1, L, 0}, {o2vmr, 1, L, 0},
+        {cfc11vmr, 1, L, 0}, {cfc12vmr, 1, L, 0}, {cfc22vmr, 1, L, 0}, {ccl4vmr, 1, L, 0}, {emis, 1, 16, 0}};
+    for (size_t k = 0; k < ins.size(); k++) if (!ins[k].h) return fail(RRTMG_LW_HIP_EARG, "gas optics: null input array (argument %d)", (int)k);
+    auto out = [](double *h, size_t rows) { return HostOut{h, h ? rows : 0, nullptr, h != nullptr}; };
+    std::vector<HostOut> outs = {out(taug, (size_t)NGPT * L), out(fracs, (size_t)NGPT * L), out(planklay, NBND * L), out(planklev, NBND * (L + 1)),
+                                 out(plankbnd, NBND), out(idrv == 1 ? dplankbnd_dt : nullptr, NBND)};
+    // (the outputs are ~40 times a column's inputs: batches of at most ~256 MB of staging each)
+    size_t per_col = 0;
+    for (auto &a : ins) per_col += a.inner * a.rows * 8;
+    for (auto &a : outs) per_col += a.rows * 8;
+    const int cap = std::max(256, (int)std::min<size_t>((size_t)std::min(eff_batch(nlay), HOST_BATCH), ((size_t)256 << 20) / per_col / 256 * 256));
+    const int nbmax = balanced_batch(c1 - c0, cap);
+    if (int rc = ensure_optics_ws(nlay, nbmax)) return rc;
+    auto body = [&](hipStream_t s, int nb, int, std::vector<HostIn> &in, std::vector<HostOut> &o_) -> int {
+        const GcmIn g{in[0].d, in[1].d, in[2].d, in[3].d, in[4].d, in[5].d, in[6].d, in[7].d, in[8].d, in[9].d, in[10].d,
+                      in[11].d, in[12].d, in[13].d, in[14].d, in[15].d};
+        auto d = [&](int k) { return o_[k].active ? o_[k].d : nullptr; };
+        const OptOut o{d(0), d(1), d(2), d(3), d(4), d(5)};
+        return run_optics<true>(s, nb, 0, nb, nlay, idrv, g, ColIn{}, o);
+    };
+    return host_pipeline(ncol, c0, c1, nbmax, ins, outs, body);
+}
+
+int rrtmg_lw_hip_gas_optics(OPTICS_GCM_PARAMS)
+{
+    ENTRY_LOCK;
+    if (int rc = check_common(ncol, nlay)) return rc;
+    if (int rc = check_optics(idrv, OptOut{taug, fracs, planklay, planklev, plankbnd, dplankbnd_dt})) return rc;
+    return fan_out(ncol, [&](int c0, int c1) {
+        return gas_optics_host_range(c0, c1, ncol, nlay, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr,
+                                     cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, taug, fracs, planklay, planklev, plankbnd, dplankbnd_dt);
+    });
+}
+
+int rrtmg_lw_hip_gas_optics_columns(
+    int ncol, int nlayers, int idrv,
+    const double *pavel, const double *tavel, const double *pz, const double *tz, const double *tbound,
+    const double *semiss, const double *coldry, const double *wkl, const double *wbrodl, const double *wx,
+    const double *pwvcm,
+    double *taug, double *fracs, double *planklay, double *planklev, double *plankbnd, double *dplankbnd_dt)
+{
+    ENTRY_LOCK;
+    if (int rc = check_common(ncol, nlayers)) return rc;
+    if (int rc = check_optics(idrv, OptOut{taug, fracs, planklay, planklev, plankbnd, dplankbnd_dt})) return rc;
+    if (ncol > eff_batch(nlayers)) return fail(RRTMG_LW_HIP_EARG, "gas_optics_columns handles at most one batch (%d columns)", eff_batch(nlayers));
+    HIP_TRY(hipDeviceSynchronize());      // asynchronous device-entry work of earlier calls shares the workspace
+    if (int rc = ensure_optics_ws(nlayers, ncol)) return rc;
+    const size_t n = (size_t)ncol, L = (size_t)nlayers;
+    struct Arr { const double *h; size_t cnt; double *d; };
+    Arr ins[] = {{pavel, n * L, 0}, {tavel, n * L, 0}, {pz, n * (L + 1), 0}, {tz, n * (L + 1), 0}, {tbound, n, 0}, {semiss, 16 * n, 0},
+                 {coldry, n * L, 0}, {wkl, 7 * n * L, 0}, {wbrodl, n * L, 0}, {wx, 4 * n * L, 0}, {pwvcm, n, 0}};
+    struct Res { double *h; size_t cnt; double *d; };
+    Res outs[] = {{taug, (size_t)NGPT * n * L, 0}, {fracs, (size_t)NGPT * n * L, 0}, {planklay, NBND * n * L, 0}, {planklev, NBND * n * (L + 1), 0},
+                  {plankbnd, NBND * n, 0}, {idrv == 1 ? dplankbnd_dt : nullptr, NBND * n, 0}};
+    size_t tot = 0;
+    for (auto &i : ins) {
+        if (!i.h) return fail(RRTMG_LW_HIP_EARG, "gas optics: null input array");
+        tot += i.cnt;
+    }
+    for (auto &r : outs) tot += r.h ? r.cnt : 0;
+    if (int rc = ensure_stage(tot * 8 + 4096)) return rc;
+    double *p = (double *)G.stage_base;
+    for (auto &i : ins) {
+        i.d = p; p += i.cnt;
+        if (int rc = bounce_h2d(i.d, i.h, i.cnt * 8)) return rc;
+    }
+    for (auto &r : outs) if (r.h) { r.d = p; p += r.cnt; }
+    const ColIn c{ins[0].d, ins[1].d, ins[2].d, ins[3].d, ins[4].d, ins[5].d, ins[6].d, ins[7].d, ins[8].d, ins[9].d, ins[10].d};
+    const OptOut o{outs[0].d, outs[1].d, outs[2].d, outs[3].d, outs[4].d, outs[5].d};
+    const hipStream_t s = G.stream;
+    if (int rc = run_optics<false>(s, ncol, 0, ncol, nlayers, idrv, GcmIn{}, c, o)) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    for (auto &r : outs) if (r.h) { if (int rc = bounce_d2h(r.h, r.d, r.cnt * 8)) return rc; }
+    return 0;
 }
 
 // McICA flavour of the prepared-column entry: cldprmc -> setcoef -> taumol -> rtrnmc for `ncol` (column, sample) pairs.

@@ -220,6 +220,12 @@ struct FluxOut {
     double *fnet, *fnetc;                                                     // optional (column entry)
     double *uflxs, *dflxs, *uflxcs, *dflxcs;                                  // optional spectral outputs (ncol_total, nlay+1, 16): written by the sweeps (SweepArgs)
 };
+// Outputs of the gas-optics entries (k_optics), device pointers, column stride = ncol_total, g-point or band index last:
+// taug, fracs (ncol_total, nlay, NGPT); planklay (.., nlay, 16); planklev (.., nlay+1, 16); plankbnd, dplankbnd (.., 16).
+// taug and fracs are required, the others optional (null: not stored); dplankbnd is stored only with idrv = 1.
+struct OptOut {
+    double *taug = nullptr, *fracs = nullptr, *planklay = nullptr, *planklev = nullptr, *plankbnd = nullptr, *dplankbnd = nullptr;
+};
 
 enum ErrCode { E_NONE = 0, E_ICE_SMALL = 1, E_ICE_BOUNDS = 2, E_ICE_GEN_BOUNDS = 3, E_LIQ_BOUNDS = 4, E_BAD_FLAG = 5,
                E_MC_INFLAG1 = 6, E_KISS_PMID = 7 };
@@ -1736,6 +1742,119 @@ __device__ __forceinline__ void band_cells(const DevTables &T, const Workspace &
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_optics (k_layer's machinery with CLOUD = CL_OPTICS): what k_layer forms for a (layer, column) and then codes away, stored in the
+// caller's arrays instead - taumol's gas optical depth per g-point (rows_eval_band from tau0 = 0: no aerosol, no secdiff, no clamp) and
+// Planck fraction per g-point (src/rrtmg_lw_taumol.f90), setcoef's Planck integrals per band (src/rrtmg_lw_setcoef.f90:173-269, band 16
+// as in a broadband call).  Every value is written once: streaming stores through a descriptor whose range is the batch's part of the
+// output row, so that a thread past the last column (offset out of range) stores nothing without a branch (profiles/round5_exec_hazard.md).
+// ------------------------------------------------------------------------------------------------
+constexpr int CL_OPTICS = 4;
+
+__device__ __forceinline__ void opt_store(double *row, unsigned bytes, unsigned off8, double v)
+{
+    typedef unsigned int u32x2o __attribute__((ext_vector_type(2)));
+    u32x2o x;
+    __builtin_memcpy(&x, &v, 8);
+    __builtin_amdgcn_raw_buffer_store_b64(x, __builtin_amdgcn_make_buffer_rsrc(row, 0, (int)bytes, 0x00020000), (int)off8, 0, 2);    // (aux 2: nt)
+}
+
+// integrated Planck function of one band's totplnk row at temperature t: setcoef :190-205, in the sweeps' arithmetic (planck_at)
+__device__ __forceinline__ double planck_band(const double *tp, double t)
+{
+    const double x = t - 159.;
+    const int ind = clampi((int)x, 1, 180);
+    const double f = x - (double)ind;
+    return fma(f, tp[ind] - tp[ind - 1], tp[ind - 1]);
+}
+
+// taug and fracs of band B for one (layer, column); off8: the thread's byte offset in an output row (out of range past the last column)
+template <int B, bool LOWER, int N, bool LDS>
+__device__ __forceinline__ void optics_cells(const DevTables &T, const Workspace &W, const LayerArgs &a, const LayerCoef &C, __amdgpu_buffer_rsrc_t kt,
+                                             const double2 *lds, const Rows<N> &rw, int lay, unsigned off8, const OptOut &o)
+{
+    constexpr Region R = LOWER ? BT<B>::lo : BT<B>::up;
+    constexpr int ng = BT<B>::ng, NP = 4 * band_nquad(B), G0 = band_g0(B);
+    const size_t nct = (size_t)a.nct, gstride = nct * (size_t)W.nlay;
+    const unsigned bytes = (unsigned)a.ncol * 8u;
+    const size_t row0 = (size_t)a.col0 + nct * (size_t)(lay - 1) + gstride * (size_t)G0;
+    double od[NP];
+    rows_eval_band<B, LOWER, N, LDS>(kt, lds, rw, 0.0, od);
+#pragma unroll
+    for (int j = 0; j < ng; j++) opt_store(o.taug + row0 + gstride * (size_t)j, bytes, off8, od[j]);
+    __builtin_amdgcn_sched_barrier(0);          // (the optical depths are stored before the fraction rows are loaded)
+    // Planck fractions: the sweeps' rows (sweep_stage_band / frac_row) - fracrefa below laytrop, fracrefb above (band 6: fracrefa, bands
+    // 12 and 15: none), interpolated in the mixture where the region has a binary key (taumol :556-561, :692-693) with the weight fs in
+    // full precision (the sweeps carry it in 28 bits: Rows::fw)
+    constexpr bool FROM_A = LOWER || R.frac_from_a;
+    const BandLayout &L = T.band[B - 1];
+    const int base = FROM_A ? L.fracrefa : L.fracrefb;
+    const bool have = R.key != K_ZERO && base >= 0;         // (uniform)
+    unsigned r0 = have ? (unsigned)base : 0u;
+    double fs = 0.0;
+    if constexpr (R.key == K_BINARY) {
+        const Spec sp = spec_calc(C.f[F_COLH2O + R.a], T.refrat[B - 1][R.planck_slot], C.f[F_COLH2O + R.b], LOWER ? 8. : 4., T.oneminus);
+        r0 += (unsigned)(sp.js - 1) * (unsigned)ng;
+        fs = sp.fs;
+    }
+#pragma unroll
+    for (int p = 0; p < ng / 2; p++) {
+        double2 f = make_double2(0.0, 0.0);
+        if (have) {
+            const double2 f0 = ld2(kt, r0 + 2u * (unsigned)p);
+            f = f0;
+            if constexpr (R.key == K_BINARY) {
+                const double2 f1 = ld2(kt, r0 + (unsigned)ng + 2u * (unsigned)p);
+                f.x = fma(fs, f1.x - f0.x, f0.x);
+                f.y = fma(fs, f1.y - f0.y, f0.y);
+            }
+        }
+        opt_store(o.fracs + row0 + gstride * (size_t)(2 * p), bytes, off8, f.x);
+        opt_store(o.fracs + row0 + gstride * (size_t)(2 * p + 1), bytes, off8, f.y);
+    }
+}
+
+// band B of one (layer, column) in k_optics: layer_band's row lists and staging offsets, optics_cells in place of band_cells
+template <int B, class WN, int BASE_LO, int BASE_UP>
+__device__ __forceinline__ void optics_band(const DevTables &T, const Workspace &W, const LayerArgs &a, const LayerCoef &C, __amdgpu_buffer_rsrc_t kt,
+                                            const double2 *lds, int jp0, int im0, bool ok, bool lower, int lay, int col, bool incol, const OptOut &o)
+{
+    unsigned delta[NROLE];
+    const bool use_lds = __builtin_amdgcn_ballot_w64(!ok) == 0ull;          // wave-uniform: every cell of the wave lies in the staged window
+    const unsigned off8 = incol ? (unsigned)col * 8u : 0x80000000u;        // (a select, not a branch)
+    if (lower) {
+        constexpr int N = region_nrows(BT<B>::lo, true);
+        Rows<N> rw;
+        rows_prep<B, true, N>(T, C, rw);
+        if (use_lds) {
+            band_delta<B, true, WN, BASE_LO>(T, jp0, im0, delta);
+            rows_to_lds<B, true, N>(rw, delta);
+            optics_cells<B, true, N, true>(T, W, a, C, kt, lds, rw, lay, off8, o);
+        } else {
+            optics_cells<B, true, N, false>(T, W, a, C, kt, lds, rw, lay, off8, o);
+        }
+    } else {
+        constexpr int N = region_nrows(BT<B>::up, false);
+        Rows<N> rw;
+        rows_prep<B, false, N>(T, C, rw);
+        if constexpr (B == 16) {
+            // The reference sets nspb(16) = 0 (src/rrtmg_lw_init.f90:228), so taugb16's upper-atmosphere indices
+            // ind0 = ((jp-13)*5 + (jt-1))*nspb(16) + 1 and ind1 (src/rrtmg_lw_taumol.f90, band 16 upper loop) are 1 whatever
+            // the layer: its taug reads absb rows 1 and 2 with the layer's four weights.  This entry returns the reference's
+            // taug; the solver's k_layer indexes the table by (jp, jt) (optical depths ~1e-8 there: no flux-level difference).
+            const unsigned tab = (unsigned)T.band[B - 1].absb, ng = (unsigned)BT<B>::ng;
+            rw.off[0] = tab; rw.off[1] = tab + ng; rw.off[2] = tab; rw.off[3] = tab + ng;
+            optics_cells<B, false, N, false>(T, W, a, C, kt, lds, rw, lay, off8, o);
+        } else if (use_lds) {
+            band_delta<B, false, WN, BASE_UP>(T, jp0, im0, delta);
+            rows_to_lds<B, false, N>(rw, delta);
+            optics_cells<B, false, N, true>(T, W, a, C, kt, lds, rw, lay, off8, o);
+        } else {
+            optics_cells<B, false, N, false>(T, W, a, C, kt, lds, rw, lay, off8, o);
+        }
+    }
+}
+
 #ifndef RRLW_LAYER_WAVES
 #define RRLW_LAYER_WAVES 3        // waves per SIMD k_layer is compiled for (168 VGPRs; three workgroups of 256 threads and 53 KB of LDS per CU)
 #endif
@@ -1825,7 +1944,7 @@ using LayerPassesWide = std::tuple<BandList<1, 2, 11, 15, 6, 8, 10, 14, 16, 13>,
 template <class PL, class WN, int CLOUD, int... I>
 __device__ __forceinline__ void pass_run(std::integer_sequence<int, I...>, const DevTables &T, const Workspace &W, const LayerArgs &a,
                                          const LayerCoef &C, __amdgpu_buffer_rsrc_t kt, const LayerWg &wg, bool lower, int lay, int col, bool incol,
-                                         int cloudy, const unsigned (&mw)[MASK_WORDS], unsigned bmask)
+                                         int cloudy, const unsigned (&mw)[MASK_WORDS], unsigned bmask, const OptOut &o)
 {
     // (a workgroup that holds none of the pass's bands - the bands of a small batch spread over several - leaves the pass alone: uniform)
     constexpr unsigned passmask = ((1u << (PL::b[I] - 1)) | ...);
@@ -1838,16 +1957,22 @@ __device__ __forceinline__ void pass_run(std::integer_sequence<int, I...>, const
     else stage_pass<PL, false, WN>(T, kt, wg.lds, wg.jp0, wg.im0, wg.tid);
     lds_barrier();
     STAMP(1);
-    (((bmask >> (PL::b[I] - 1)) & 1u
-          ? layer_band<PL::b[I], CLOUD, WN, pass_base<PL, true, WN, I>(), pass_base<PL, false, WN, I>()>(T, W, a, C, kt, wg, lower, lay, col, incol, cloudy, mw)
-          : (void)0), ...);
+    if constexpr (CLOUD == CL_OPTICS) {
+        (((bmask >> (PL::b[I] - 1)) & 1u
+              ? optics_band<PL::b[I], WN, pass_base<PL, true, WN, I>(), pass_base<PL, false, WN, I>()>(T, W, a, C, kt, wg.lds, wg.jp0, wg.im0, wg.ok, lower, lay, col, incol, o)
+              : (void)0), ...);
+    } else {
+        (((bmask >> (PL::b[I] - 1)) & 1u
+              ? layer_band<PL::b[I], CLOUD, WN, pass_base<PL, true, WN, I>(), pass_base<PL, false, WN, I>()>(T, W, a, C, kt, wg, lower, lay, col, incol, cloudy, mw)
+              : (void)0), ...);
+    }
 }
 template <int CLOUD, class WN, class... PLs>
 __device__ __forceinline__ void passes_run(std::tuple<PLs...> *, const DevTables &T, const Workspace &W, const LayerArgs &a,
                                            const LayerCoef &C, __amdgpu_buffer_rsrc_t kt, const LayerWg &wg, bool lower, int lay, int col, bool incol,
-                                           int cloudy, const unsigned (&mw)[MASK_WORDS], unsigned bmask)
+                                           int cloudy, const unsigned (&mw)[MASK_WORDS], unsigned bmask, const OptOut &o)
 {
-    (pass_run<PLs, WN, CLOUD>(std::make_integer_sequence<int, PLs::n>{}, T, W, a, C, kt, wg, lower, lay, col, incol, cloudy, mw, bmask), ...);
+    (pass_run<PLs, WN, CLOUD>(std::make_integer_sequence<int, PLs::n>{}, T, W, a, C, kt, wg, lower, lay, col, incol, cloudy, mw, bmask, o), ...);
 }
 
 // One workgroup's work: the cells of window `bx` (256 consecutive positions) in layer `by` + 1.  WIDE = 0: the narrow staging window; a
@@ -1855,7 +1980,7 @@ __device__ __forceinline__ void passes_run(std::tuple<PLs...> *, const DevTables
 // that list).
 template <bool GCM, int CLOUD, int WIDE>
 __device__ __forceinline__ void layer_cells(const DevTables &T, const Workspace &W, const GcmIn &g, const ColIn &c, const LayerArgs &a, double2 *s_tab, int *s_wg,
-                                            int bx, int by, unsigned bmask, bool lists)
+                                            int bx, int by, unsigned bmask, bool lists, const OptOut &o)
 {
     const int colr = bx * LAYER_BLOCK + threadIdx.x;
     const bool incol = colr < a.ncol;
@@ -2000,7 +2125,29 @@ __device__ __forceinline__ void layer_cells(const DevTables &T, const Workspace 
     int cloudy = 0;
     // (threads past the last column never take the cloudy branches: nothing of theirs is stored, and with them no lane of a divergent
     // region skips the `if (incol)` at its end - the construct of profiles/round5_exec_hazard.md)
-    if (CLOUD) cloudy = incol ? (W.cflag[(size_t)lay * W.ncolb + col] & 1) : 0;
+    if (CLOUD >= 1 && CLOUD <= 3) cloudy = incol ? (W.cflag[(size_t)lay * W.ncolb + col] & 1) : 0;
+    if constexpr (CLOUD == CL_OPTICS) {
+        // setcoef :173-269 for the bands of this workgroup: the layer's Planck integral and that of the level above it; the layer-1 threads
+        // add level 0 and the surface terms k_colprep has formed for the sweeps (plankbnd with semiss, its d/dT with idrv = 1)
+        const size_t nlv = (size_t)W.nlay, ro = (size_t)a.col0 + (size_t)nct * (lay - 1);
+        const unsigned o8 = (unsigned)pc * 8u, off8 = incol ? (unsigned)col * 8u : 0x80000000u, bytes = (unsigned)a.ncol * 8u;
+        const double tz_up = GCM ? col_load(g.tlev + ro + nct, o8) : c.tz[gc + (size_t)nct * lay];
+        const double tz_lo = lay == 1 ? (GCM ? col_load(g.tlev + ro, o8) : c.tz[gc]) : 0.0;
+        for (int b = 0; b < NBND; b++) {
+            if (!((bmask >> b) & 1u)) continue;                                  // (uniform)
+            const double *tp = S + T.sl.totplnk + 181 * b;
+            if (o.planklay) opt_store(o.planklay + ro + (size_t)nct * nlv * b, bytes, off8, planck_band(tp, tavel));
+            if (o.planklev) {
+                const size_t lv0 = (size_t)a.col0 + (size_t)nct * (nlv + 1) * b;
+                opt_store(o.planklev + lv0 + (size_t)nct * lay, bytes, off8, planck_band(tp, tz_up));
+                if (lay == 1) opt_store(o.planklev + lv0, bytes, off8, planck_band(tp, tz_lo));
+            }
+            if (lay == 1) {
+                if (o.plankbnd) opt_store(o.plankbnd + a.col0 + (size_t)nct * b, bytes, off8, W.percol[(size_t)(PC_PLANKBND + b) * W.ncolb + col]);
+                if (o.dplankbnd && a.idrv == 1) opt_store(o.dplankbnd + a.col0 + (size_t)nct * b, bytes, off8, W.percol[(size_t)(PC_DPLANKBND + b) * W.ncolb + col]);
+            }
+        }
+    }
     // wave-uniform descriptor of the packed k tables (built from kernel arguments only)
     const __amdgpu_buffer_rsrc_t kt = __builtin_amdgcn_make_buffer_rsrc((void *)T.ktab, 0, a.ktab_bytes, 0x00020000);
     const unsigned mw[MASK_WORDS] = {};
@@ -2034,7 +2181,7 @@ __device__ __forceinline__ void layer_cells(const DevTables &T, const Workspace 
     wg.im0 = min(s_wg[2], 20 - WN::MW);                     // (the window ends with the table's last slice at the latest)
     wg.ok = lower == wg.lower && (unsigned)(jp - wg.jp0) <= (unsigned)(WN::NPL - 2) && (unsigned)(indminor - wg.im0) <= (unsigned)(WN::MW - 2);
     STAMP(5);                       // set-up of the workgroup's staging window
-    passes_run<CLOUD, WN>(static_cast<std::conditional_t<WIDE != 0, LayerPassesWide, LayerPasses> *>(nullptr), T, W, a, C, kt, wg, lower, lay, col, incol, cloudy, mw, bmask);
+    passes_run<CLOUD, WN>(static_cast<std::conditional_t<WIDE != 0, LayerPassesWide, LayerPasses> *>(nullptr), T, W, a, C, kt, wg, lower, lay, col, incol, cloudy, mw, bmask, o);
 #ifdef RRLW_LAYER_STAMPS
     STAMP(4);
     if ((threadIdx.x & 63) == 0) {
@@ -2050,22 +2197,37 @@ __device__ __forceinline__ void layer_cells(const DevTables &T, const Workspace 
 // 151 registers: everything derived from the kernel's arguments stays live round the loop).  The count is cleared on the stream in front
 // of the narrow launch (driver.hip: run_layer).
 template <bool GCM, int CLOUD, int WIDE>
-__global__ __launch_bounds__(LAYER_BLOCK, RRLW_LAYER_WAVES) void k_layer(DevTables T, Workspace W, GcmIn g, ColIn c, LayerArgs a)
+__device__ __forceinline__ void layer_grid(const DevTables &T, const Workspace &W, const GcmIn &g, const ColIn &c, const LayerArgs &a, double2 *s_tab, int *s_wg,
+                                           const OptOut &o)
 {
-    __shared__ double2 s_tab[STAGE_DOUBLES / 2];
-    __shared__ int s_wg[5];
     // the bands this workgroup takes: those of the call's range, of its part where the bands of a small batch are spread over several workgroups
     const int part = WIDE == 0 ? blockIdx.z : blockIdx.y;
     unsigned bmask = ((a.iend >= 32 ? 0u : (1u << a.iend)) - 1u) & ~((1u << (a.istart - 1)) - 1u);
     if (a.nparts > 1) bmask &= a.partmask[part];
     if constexpr (WIDE == 0) {
-        layer_cells<GCM, CLOUD, 0>(T, W, g, c, a, s_tab, s_wg, blockIdx.x, blockIdx.y, bmask, part == 0);
+        layer_cells<GCM, CLOUD, 0>(T, W, g, c, a, s_tab, s_wg, blockIdx.x, blockIdx.y, bmask, part == 0, o);
     } else {
         const int n = __builtin_amdgcn_readfirstlane(W.wide[0]), gx = (a.ncol + LAYER_BLOCK - 1) / LAYER_BLOCK;
         if ((int)blockIdx.x >= n) return;
         const int item = __builtin_amdgcn_readfirstlane(W.wide[2 + blockIdx.x]);
-        layer_cells<GCM, CLOUD, 1>(T, W, g, c, a, s_tab, s_wg, item % gx, item / gx, bmask, false);
+        layer_cells<GCM, CLOUD, 1>(T, W, g, c, a, s_tab, s_wg, item % gx, item / gx, bmask, false, o);
     }
+}
+template <bool GCM, int CLOUD, int WIDE>
+__global__ __launch_bounds__(LAYER_BLOCK, RRLW_LAYER_WAVES) void k_layer(DevTables T, Workspace W, GcmIn g, ColIn c, LayerArgs a)
+{
+    __shared__ double2 s_tab[STAGE_DOUBLES / 2];
+    __shared__ int s_wg[5];
+    layer_grid<GCM, CLOUD, WIDE>(T, W, g, c, a, s_tab, s_wg, OptOut{});
+}
+// k_optics: the gas-optics entries (rrtmg_lw_hip_gas_optics*) - k_layer's grid, windows, staging passes and table evaluation with the
+// outputs of OptOut in place of the cell codes; no cloud, no aerosol.  WIDE as for k_layer.
+template <bool GCM, int WIDE>
+__global__ __launch_bounds__(LAYER_BLOCK, RRLW_LAYER_WAVES) void k_optics(DevTables T, Workspace W, GcmIn g, ColIn c, LayerArgs a, OptOut o)
+{
+    __shared__ double2 s_tab[STAGE_DOUBLES / 2];
+    __shared__ int s_wg[5];
+    layer_grid<GCM, CL_OPTICS, WIDE>(T, W, g, c, a, s_tab, s_wg, o);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,0 +1,143 @@
+!  Gas optics and Planck sources of rrtmg_lw (this library's extension; include/rrtmg_lw_hip.h, "Gas optics and Planck sources"):
+!      use rrtmg_lw_optics, only: rrtmg_lw_gas_optics
+!      call rrtmg_lw_gas_optics(ncol, nlay, play, plev, tlay, tlev, tsfc, h2ovmr, ..., ccl4vmr, emis, taug, fracs &
+!                               [, planklay, planklev, plankbnd, dplankbnd_dt])
+!  The GCM inputs of rrtmg_lw (module rrtmg_lw_rad) without the cloud and aerosol arrays.  Outputs:
+!      taug, fracs    (ncol,nlay,ngptlw)  taumol's gas optical depth (no aerosol, no diffusivity secant) and Planck fraction per g-point
+!      planklay       (ncol,nlay,nbndlw)  setcoef's Planck integrals of the layers;  planklev (ncol,0:nlay,nbndlw) of the levels
+!      plankbnd       (ncol,nbndlw)       surface Planck integrals times emis;  dplankbnd_dt (ncol,nbndlw) their d/dT
+!  ngptlw = rrtmg_lw_hip_gpoints() (140, or 256 with librrtmg_lw_hip_g256.so).  The Planck outputs are optional; an absent one is not
+!  formed.  dplankbnd_dt present = idrv 1.  Arrays larger than the declared shapes (pcols > ncol) or strided sections are accepted as
+!  in rrtmg_lw_rad: the inputs go across as the section (1:ncol, ...), the outputs through temporaries where they are not exactly sized.
+      module rrtmg_lw_optics
+
+      use iso_c_binding
+      use parkind, only : im => kind_im, rb => kind_rb
+      use rrtmg_lw_init, only : rrtmg_lw_hip_abort
+
+      implicit none
+
+      public :: rrtmg_lw_gas_optics
+
+      interface
+         function rrtmg_lw_hip_gas_optics(ncol, nlay, idrv, play, plev, tlay, tlev, tsfc, &
+               h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, &
+               taug, fracs, planklay, planklev, plankbnd, dplankbnd_dt) bind(C, name='rrtmg_lw_hip_gas_optics') result(rc)
+            import :: c_int, c_double, c_ptr
+            integer(c_int), value :: ncol, nlay, idrv
+            real(c_double), intent(in) :: play(*), plev(*), tlay(*), tlev(*), tsfc(*), h2ovmr(*), o3vmr(*), co2vmr(*)
+            real(c_double), intent(in) :: ch4vmr(*), n2ovmr(*), o2vmr(*), cfc11vmr(*), cfc12vmr(*), cfc22vmr(*), ccl4vmr(*)
+            real(c_double), intent(in) :: emis(*)
+            type(c_ptr), value :: taug, fracs, planklay, planklev, plankbnd, dplankbnd_dt
+            integer(c_int) :: rc
+         end function rrtmg_lw_hip_gas_optics
+         function rrtmg_lw_hip_gpoints() bind(C, name='rrtmg_lw_hip_gpoints') result(n)
+            import :: c_int
+            integer(c_int) :: n
+         end function rrtmg_lw_hip_gpoints
+      end interface
+
+      contains
+
+      subroutine rrtmg_lw_gas_optics &
+            (ncol    ,nlay    , &
+             play    ,plev    ,tlay    ,tlev    ,tsfc    , &
+             h2ovmr  ,o3vmr   ,co2vmr  ,ch4vmr  ,n2ovmr  ,o2vmr , &
+             cfc11vmr,cfc12vmr,cfc22vmr,ccl4vmr ,emis    , &
+             taug    ,fracs   , &
+             planklay,planklev,plankbnd,dplankbnd_dt)
+
+      integer(kind=im), intent(in) :: ncol            ! Number of horizontal columns
+      integer(kind=im), intent(in) :: nlay            ! Number of model layers
+      real(kind=rb), intent(in) :: play(:,:)          ! Layer pressures (hPa, mb)           (ncol,nlay)
+      real(kind=rb), intent(in) :: plev(:,:)          ! Interface pressures (hPa, mb)       (ncol,nlay+1)
+      real(kind=rb), intent(in) :: tlay(:,:)          ! Layer temperatures (K)
+      real(kind=rb), intent(in) :: tlev(:,:)          ! Interface temperatures (K)
+      real(kind=rb), intent(in) :: tsfc(:)            ! Surface temperature (K)
+      real(kind=rb), intent(in) :: h2ovmr(:,:), o3vmr(:,:), co2vmr(:,:), ch4vmr(:,:), n2ovmr(:,:), o2vmr(:,:)
+      real(kind=rb), intent(in) :: cfc11vmr(:,:), cfc12vmr(:,:), cfc22vmr(:,:), ccl4vmr(:,:)
+      real(kind=rb), intent(in) :: emis(:,:)          ! Surface emissivity                  (ncol,nbndlw)
+      real(kind=rb), intent(out), target :: taug(:,:,:), fracs(:,:,:)                  ! (ncol,nlay,ngptlw)
+      real(kind=rb), intent(out), optional, target :: planklay(:,:,:)                   ! (ncol,nlay,nbndlw)
+      real(kind=rb), intent(out), optional, target :: planklev(:,:,:)                   ! (ncol,0:nlay,nbndlw)
+      real(kind=rb), intent(out), optional, target :: plankbnd(:,:), dplankbnd_dt(:,:)  ! (ncol,nbndlw)
+
+      integer(c_int) :: rc, idrv, ng
+      real(c_double), allocatable, target :: t1(:,:,:), t2(:,:,:), t3(:,:,:), t4(:,:,:), t5(:,:), t6(:,:)
+      type(c_ptr) :: p1, p2, p3, p4, p5, p6
+
+      ng = rrtmg_lw_hip_gpoints()
+      call check_extent('play', size(play,1), size(play,2), ncol, nlay)
+      call check_extent('plev', size(plev,1), size(plev,2), ncol, nlay+1)
+      call check_extent('emis', size(emis,1), size(emis,2), ncol, 16)
+      call out3('taug', taug, t1, p1, ncol, nlay, ng)
+      call out3('fracs', fracs, t2, p2, ncol, nlay, ng)
+      p3 = c_null_ptr; p4 = c_null_ptr; p5 = c_null_ptr; p6 = c_null_ptr
+      if (present(planklay)) call out3('planklay', planklay, t3, p3, ncol, nlay, 16)
+      if (present(planklev)) call out3('planklev', planklev, t4, p4, ncol, nlay+1, 16)
+      if (present(plankbnd)) call out2('plankbnd', plankbnd, t5, p5, ncol)
+      if (present(dplankbnd_dt)) call out2('dplankbnd_dt', dplankbnd_dt, t6, p6, ncol)
+      idrv = merge(1, 0, present(dplankbnd_dt))
+      rc = rrtmg_lw_hip_gas_optics(int(ncol, c_int), int(nlay, c_int), idrv, &
+            play(1:ncol,1:nlay), plev(1:ncol,1:nlay+1), tlay(1:ncol,1:nlay), tlev(1:ncol,1:nlay+1), tsfc(1:ncol), &
+            h2ovmr(1:ncol,1:nlay), o3vmr(1:ncol,1:nlay), co2vmr(1:ncol,1:nlay), ch4vmr(1:ncol,1:nlay), &
+            n2ovmr(1:ncol,1:nlay), o2vmr(1:ncol,1:nlay), cfc11vmr(1:ncol,1:nlay), cfc12vmr(1:ncol,1:nlay), &
+            cfc22vmr(1:ncol,1:nlay), ccl4vmr(1:ncol,1:nlay), emis(1:ncol,1:16), p1, p2, p3, p4, p5, p6)
+      if (rc /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_gas_optics')
+      if (allocated(t1)) taug(1:ncol, 1:nlay, 1:ng) = t1
+      if (allocated(t2)) fracs(1:ncol, 1:nlay, 1:ng) = t2
+      if (allocated(t3)) planklay(1:ncol, 1:nlay, 1:16) = t3
+      if (allocated(t4)) planklev(1:ncol, 1:nlay+1, 1:16) = t4
+      if (allocated(t5)) plankbnd(1:ncol, 1:16) = t5
+      if (allocated(t6)) dplankbnd_dt(1:ncol, 1:16) = t6
+
+      end subroutine rrtmg_lw_gas_optics
+
+      ! an output (n1,n2,n3): exactly sized, contiguous actuals go across in place; larger or strided ones through the temporary t,
+      ! copied back after the call
+      subroutine out3(name, a, t, p, n1, n2, n3)
+      character(len=*), intent(in) :: name
+      real(kind=rb), intent(inout), target :: a(:,:,:)
+      real(c_double), allocatable, target, intent(inout) :: t(:,:,:)
+      type(c_ptr), intent(out) :: p
+      integer, intent(in) :: n1, n2, n3
+      if (size(a,1) < n1 .or. size(a,2) < n2 .or. size(a,3) < n3) then
+         write(*,'(a,a,a,i0,a,i0,a,i0,a)') 'rrtmg_lw_gas_optics: ', name, ' smaller than (', n1, ',', n2, ',', n3, ')'
+         error stop 1
+      endif
+      if (size(a,1) == n1 .and. size(a,2) == n2 .and. size(a,3) == n3 .and. is_contiguous(a)) then
+         p = c_loc(a)
+      else
+         allocate(t(n1, n2, n3))
+         p = c_loc(t)
+      endif
+      end subroutine out3
+
+      ! the same for an output (ncol,16)
+      subroutine out2(name, a, t, p, ncol)
+      character(len=*), intent(in) :: name
+      real(kind=rb), intent(inout), target :: a(:,:)
+      real(c_double), allocatable, target, intent(inout) :: t(:,:)
+      type(c_ptr), intent(out) :: p
+      integer(kind=im), intent(in) :: ncol
+      call check_extent(name, size(a,1), size(a,2), ncol, 16)
+      if (size(a,1) == ncol .and. size(a,2) == 16 .and. is_contiguous(a)) then
+         p = c_loc(a)
+      else
+         allocate(t(ncol, 16))
+         p = c_loc(t)
+      endif
+      end subroutine out2
+
+      subroutine check_extent(name, n1, n2, ncol, nl)
+      character(len=*), intent(in) :: name
+      integer, intent(in) :: n1, n2
+      integer(kind=im), intent(in) :: ncol, nl
+      if (n1 < ncol .or. n2 < nl) then
+         write(*,'(a,a,a,i0,a,i0,a,i0,a,i0,a)') 'rrtmg_lw_gas_optics: ', name, ' has extents (', n1, ',', n2, &
+               '), smaller than (', ncol, ',', nl, ')'
+         error stop 1
+      endif
+      end subroutine check_extent
+
+      end module rrtmg_lw_optics

@@ -323,6 +323,11 @@ unsigned rrtmg_lw_hip_build_flags(void);
  * 36.9 GB of workspace, the 137-layer call with aerosol and d/dT 38.7 GB; set_batch(65536) brings the 72-layer call to 9.3 GB at 4 % of its
  * speed (profiles/round5_batch_sweep.md) (0.06-0.16 MB of device workspace per column at 72 layers, by call shape: see rrtmg_lw_hip_workspace_bytes). */
 int rrtmg_lw_hip_set_batch(int ncol_batch);
+/* The columns per internal batch in force for a call of `nlay` layers: the default by the call's layers, or the size named with
+ * rrtmg_lw_hip_set_batch - either one halved until the last row of the largest array the sweeps read by row offset (rtrnmr's overlap
+ * factors, (nlay + 1) x 48 bytes per column) ends inside the 0x7ffffff0 bytes their buffer descriptors span: 262144 columns up to 169
+ * layers, 131072 up to 340, 65536 up to 681. */
+int rrtmg_lw_hip_effective_batch(int nlay);
 /* on = 1: device-pointer entries run the sweeps / k_flux of column batch i on a second stream while k_layer of batch i+1 runs on the
  * caller's stream (second scratch set, +0.1 MB of workspace per column).  Default 0: a sweep workgroup owns a CU (transmittance table in
  * LDS, all vector registers), so the two do not share one (measured: 1-2 % faster on 1e6 cloudy columns).  on = 0 frees the second set at the next workspace

@@ -105,6 +105,12 @@ def set_batch(n):
     _check(lib().rrtmg_lw_hip_set_batch(C.c_int(int(n))))
 
 
+def effective_batch(nlay):
+    """columns per internal batch in force for a call of `nlay` layers (rrtmg_lw_hip_effective_batch): the default by the call's layers or
+    set_batch's size, halved until the sweeps' row offsets stay inside their buffer descriptors"""
+    return int(lib().rrtmg_lw_hip_effective_batch(C.c_int(int(nlay))))
+
+
 def host_register(a):
     """Pin a numpy array that will be passed to the host-pointer entries repeatedly (rrtmg_lw_hip_host_register)."""
     _check(lib().rrtmg_lw_hip_host_register(C.c_void_p(a.ctypes.data), C.c_longlong(a.nbytes)))

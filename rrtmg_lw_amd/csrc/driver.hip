@@ -120,6 +120,7 @@ struct State {
     unsigned long long graph_clock = 0;
     hipStream_t cap = nullptr;         // the stream the launches of such a call are captured on (the caller's may be the null stream)
     long long graph_replays = 0, graph_captures = 0;
+    unsigned long long init_gen = 0;   // which initialisation (init_state) the state's tables come from: part of every graph's key
     struct ProfRec { const char *name; hipEvent_t a, b; };
     std::vector<ProfRec> prof;
     std::vector<hipEvent_t> evpool;
@@ -243,13 +244,20 @@ int auto_batch(int nlay)
     while (b > 16384 && (long long)b * nlay > (long long)DEFAULT_BATCH * 72) b >>= 1;
     return b;
 }
+// The sweeps address the rows of a workspace array through a buffer descriptor built from the array's start (kernels.hip: sweep_rsrc,
+// num_records = SWEEP_RANGE bytes) with the level's row as a 32-bit scalar byte offset (bload_*'s soff) and the column as the per-lane
+// offset.  Every byte a sweep touches must lie inside the descriptor's range whatever the hardware's range check counts - the per-lane
+// offset alone or the scalar offset with it (profiles/lifecycle_tests.md) - so a batch is halved until the END of the last row of
+// the array with the largest rows does: rtrnmr's overlap factors, 3 rows of 16 bytes per column for each of the levels 0 .. nlay, i.e.
+// (nlay + 1) x 48 bytes per column (262 144 columns: beyond 169 layers).  The other arrays read this way stay below it in every mode: the
+// sub-column cloud fractions / emissivities of rtrnmc nlay x 32 bytes per column, the cell codes nlay x 16, rtrn's emissivity term
+// nlay x 8, the cloud flags (nlay + 2) x 4, the binary-key words nlay x 4.  The default batches (auto_batch) are far inside:
+// 72 layers x 262 144 columns end at 0.43 of the range, 137 x 131 072 at 0.40, 200 x 65 536 at 0.29.
+constexpr unsigned long long SWEEP_RANGE = 0x7ffffff0ull;
 int eff_batch(int nlay)
 {
     int b = G.batch_set ? G.batch : auto_batch(nlay);
-    // the sweeps address the rows of a workspace array by 32-bit byte offsets (kernels.hip: bload_*'s soff); the largest is that of
-    // rtrnmr's overlap factors, (nlay + 1) x 3 rows of 16 bytes per column: a batch that would carry it past 2^32 is halved (262 144
-    // columns: beyond 170 layers)
-    while (b > 64 && (unsigned long long)(nlay + 2) * 3ull * 16ull * (unsigned long long)b >= (1ull << 32)) b >>= 1;
+    while (b > 64 && (unsigned long long)(nlay + 1) * 48ull * (unsigned long long)b > SWEEP_RANGE) b >>= 1;
     return b;
 }
 // columns per batch: the fewest batches that respect G.batch, of (nearly) equal size - a short last batch would leave the
@@ -1013,6 +1021,8 @@ int run_pipelined(hipStream_t s, int ncol, int nlay, int mode, int idrv, const G
                               out.uflxs, out.dflxs, out.uflxcs, out.dflxcs};
         key_put(key, gp);
         // (what else decides which kernels run with which arguments: the workspace, the tuning switches)
+        // (what the kernel nodes carry BY VALUE: the tables of this initialisation - DevTables with heatfac and the table pointers - on its device)
+        key_put(key, G.init_gen); key_put(key, G.device);
         key_put(key, G.ws_base); key_put(key, G.ws_bytes); key_put(key, g_colsort); key_put(key, g_colsort_min); key_put(key, g_one_sweep_max);
         key_put(key, g_wide_window); key_put(key, g_layer_split); key_put(key, g_prep_fork); key_put(key, G.sweep_fanout); key_put(key, eff_batch(nlay)); key_put(key, g_split_max);
         for (auto &e : G.graphs) if (e.key == key) { gent = &e; break; }
@@ -2023,6 +2033,16 @@ static int init_state(const char *static_tables_path, const char *kdata_path, do
     if (!static_tables_path || !kdata_path) return fail(RRTMG_LW_HIP_EARG, "null table path");
     std::string err;
     if (!build_tables(static_tables_path, kdata_path, cpdair, G.H, err)) return fail(RRTMG_LW_HIP_EDATA, "%s", err.c_str());
+    if (G.init) {
+        // a re-initialisation: the graphs of small calls hold the tables of the previous one by value (heatfac, the pointers to d_ktab /
+        // d_stat freed below) and the workspace freed below - none survives, whatever addresses the allocations that follow come back with
+        (void)hipSetDevice(G.device);
+        (void)hipDeviceSynchronize();
+        graphs_clear();
+        if (G.device != device && G.cap) { (void)hipStreamDestroy(G.cap); G.cap = nullptr; }       // (the capture stream belongs to the device it was made on)
+    }
+    static unsigned long long init_count = 0;
+    G.init_gen = ++init_count;
     HIP_TRY(hipSetDevice(device));
     G.device = device;                  // (from here on the state owns resources on this device: finalize_state releases them there)
     G.sweep_attrs = false;
@@ -2172,6 +2192,18 @@ static void finalize_state()
         if (hs.fill) (void)hipHostFree(hs.fill);
     }
     G = State();
+}
+
+// the columns per internal batch in force for a call of nlay layers (first state): the default by the call's layers or the size named
+// with rrtmg_lw_hip_set_batch, halved until the sweeps' row offsets stay inside their buffer descriptors (eff_batch)
+int rrtmg_lw_hip_effective_batch(int nlay)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    State *keep = g_cur;
+    g_cur = &g_states[0];
+    const int b = eff_batch(nlay < 1 ? 1 : nlay);
+    g_cur = keep;
+    return b;
 }
 
 int rrtmg_lw_hip_set_batch(int ncol_batch)

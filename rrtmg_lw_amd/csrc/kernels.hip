@@ -2971,8 +2971,8 @@ constexpr int SWEEP_PL_BYTES = 2 * 184 * 8, SWEEP_FR_BYTES = 16 * 16 * 8;
 // three waves per SIMD: 100 scalar instructions more per level cost the sweeps 10 % (knock-in, profiles/round5_instruction_diet.md).
 // Now the descriptor is built from the array's start (the compiler keeps it across the level loop) and a level costs the workspace arrays
 // one multiply for the row and a shift per element size; the rows of the caller's arrays, whose column stride is the whole call's column
-// count, keep a 64-bit address, formed from an unsigned 32 x 32 -> 64 bit product (row_ptr).  The driver keeps every row offset below
-// 2^32 bytes (driver.hip: eff_batch).
+// count, keep a 64-bit address, formed from an unsigned 32 x 32 -> 64 bit product (row_ptr).  The driver keeps the end of every row inside
+// the descriptor's 0x7ffffff0 bytes (driver.hip: eff_batch, SWEEP_RANGE).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t sweep_rsrc(const void *base)
 {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0x7ffffff0, 0x00020000);

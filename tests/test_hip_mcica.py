@@ -194,7 +194,7 @@ def test_mcica_entry_ignores_subcolumn_arrays_where_no_subcolumn_has_cloud(hip, 
         a = hip.rrtmg_lw_mcica_from_dict(dd, icld=2)
         b = hip.rrtmg_lw_mcica_from_dict(dj, icld=2)
     finally:
-        hip.set_batch(262144)
+        hip.set_batch(0)
     for k in ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc"):
         assert np.array_equal(a[k], b[k]), k
     ref = oracle.rrtmg_lw(ncol, nlay, 2, d["idrv"], dj, mcica=True)
@@ -314,12 +314,15 @@ def test_mcica_batching_is_transparent(hip, oracle):
     d = make_gcm_inputs(600, 40, "cloudy", col0=5)
     dd = _with_subcolumns(oracle, d, 2)
     hip.set_batch(131072)
-    one = hip.rrtmg_lw_mcica_from_dict(dd)
-    hip.set_batch(256)
-    many = hip.rrtmg_lw_mcica_from_dict(dd)
-    fused_many = hip.rrtmg_lw_mcica_subcol_from_dict(d, 140, 0)
-    hip.set_batch(131072)
-    fused_one = hip.rrtmg_lw_mcica_subcol_from_dict(d, 140, 0)
+    try:
+        one = hip.rrtmg_lw_mcica_from_dict(dd)
+        hip.set_batch(256)
+        many = hip.rrtmg_lw_mcica_from_dict(dd)
+        fused_many = hip.rrtmg_lw_mcica_subcol_from_dict(d, 140, 0)
+        hip.set_batch(131072)
+        fused_one = hip.rrtmg_lw_mcica_subcol_from_dict(d, 140, 0)
+    finally:
+        hip.set_batch(0)
     for k in ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc"):
         assert np.array_equal(one[k], many[k]), k
         assert np.array_equal(fused_one[k], fused_many[k]), k

@@ -55,10 +55,12 @@ def test_batching_is_transparent(hip, oracle):
     """Results must not depend on how the driver splits the columns into batches."""
     d = make_gcm_inputs(700, 72, "cloudy", col0=5)
     hip.set_batch(131072)
-    one = hip.rrtmg_lw_from_dict(d)
-    hip.set_batch(256)
-    many = hip.rrtmg_lw_from_dict(d)
-    hip.set_batch(131072)
+    try:
+        one = hip.rrtmg_lw_from_dict(d)
+        hip.set_batch(256)
+        many = hip.rrtmg_lw_from_dict(d)
+    finally:
+        hip.set_batch(0)
     for k in ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc"):
         assert np.array_equal(one[k], many[k]), k
 
@@ -204,7 +206,7 @@ def test_device_entry_with_caller_stream(hip, oracle):
             hip.rrtmg_lw_device(d, out, stream=side.cuda_stream)        # back to back: prep sets are reused safely
         hip.check(side.cuda_stream)
     finally:
-        hip.set_batch(131072)
+        hip.set_batch(0)
     dn = make_gcm_inputs(ncol, nlay, "aer_idrv", col0=9)
     ref = oracle.rrtmg_lw(ncol, nlay, dn["icld"], dn["idrv"], dn)
     got = {k: out[k].T.cpu().numpy() for k in ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc", "duflx_dt", "duflxc_dt")}
@@ -320,7 +322,7 @@ def test_pinned_host_arrays_and_pipelined_batches(hip, oracle):
         for v in pinned:
             hip.host_unregister(v)
     finally:
-        hip.set_batch(131072)
+        hip.set_batch(0)
     for k in ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc"):
         assert np.array_equal(got[k], plain[k]), k
     ref = oracle.rrtmg_lw(1100, 51, d["icld"], d["idrv"], d)
@@ -503,7 +505,7 @@ def test_host_entry_skips_zero_rows_and_sums_taucld(hip, oracle):
             ref = oracle.rrtmg_lw(ncol, nlay, 2, d["idrv"], d)
             _compare(got, ref, d["idrv"], f"host entry, zero rows, inflag {inflag}")
     finally:
-        hip.set_batch(262144)
+        hip.set_batch(0)
 
 
 def test_host_entry_rows_that_do_not_travel(hip, oracle):
@@ -545,7 +547,7 @@ def test_host_entry_rows_that_do_not_travel(hip, oracle):
         hip.rrtmg_lw_device(dd, oview)
         hip.check()
     finally:
-        hip.set_batch(131072)
+        hip.set_batch(0)
     names = ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc", "duflx_dt", "duflxc_dt")
     for k in names:
         assert np.array_equal(got[k], plain[k]), k
@@ -595,7 +597,7 @@ def test_host_entry_ignores_cloud_arrays_where_no_column_has_cloud(hip, oracle):
             ref = oracle.rrtmg_lw(ncol, nlay, 2, d["idrv"], db)          # the oracle reads the junk the way the reference does: not at all
             _compare(b, ref, d["idrv"], f"junk in cloud-free layers, inflag {inflag}")
     finally:
-        hip.set_batch(262144)
+        hip.set_batch(0)
 
 
 def test_several_devices_from_one_process(hip, oracle):
@@ -739,7 +741,7 @@ def test_device_entry_from_two_streams(hip, oracle):
         hip.check(sa.cuda_stream)
         hip.check(sb.cuda_stream)
     finally:
-        hip.set_batch(131072)
+        hip.set_batch(0)
     for d0, o in ((0, oa), (50_000, ob)):
         dn = make_gcm_inputs(200, nlay, "cloudy", col0=d0)
         ref = oracle.rrtmg_lw(200, nlay, dn["icld"], dn["idrv"], dn)
@@ -791,7 +793,7 @@ def test_overlap_and_cu_partition_are_transparent(hip, config, mcica):
     finally:
         hip.set_cu_partition(0)
         hip.set_overlap(False)
-        hip.set_batch(131072)
+        hip.set_batch(0)
     assert hip.cu_partition() == 0
     for other in (over, part0, part1, part2):
         assert np.array_equal(plain, other)
@@ -992,7 +994,7 @@ def test_static_arrays_are_scanned_once(hip, oracle):
                 hip.host_changed(a, keep=False)
             except hip.RrtmgLwError:
                 pass
-        hip.set_batch(131072)
+        hip.set_batch(0)
     for k in ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc", "duflx_dt", "duflxc_dt"):
         assert np.array_equal(want[k], first[k]) and np.array_equal(want[k], second[k]), k
     assert np.abs(changed["uflx"] - want["uflx"]).max() > 0.1
@@ -1250,7 +1252,7 @@ def test_large_sample_parity(hip, oracle, config, nlay, icld, ncol):
     try:
         got = hip.rrtmg_lw_from_dict(d, icld=icld)
     finally:
-        hip.set_batch(262144)
+        hip.set_batch(0)
     ref = oracle.rrtmg_lw(ncol, nlay, icld, d["idrv"], d)
     dflux = max(np.abs(got[k] - ref[k]).max() for k in ("uflx", "dflx", "uflxc", "dflxc"))
     dhr = max(np.abs(got[k] - ref[k]).max() for k in ("hr", "hrc"))

@@ -196,7 +196,7 @@ def test_band_fluxes_do_not_depend_on_the_schedule(hip):
                 runs[name] = hip.rrtmg_lw_from_dict(d, icld=2, out=_nan_out(ncol, nlay), spectral=True)
             finally:
                 if batch:
-                    hip.set_batch(131072)
+                    hip.set_batch(0)
     finally:
         hip.set_one_sweep_max(prev_one)
         hip.set_column_sort(prev_sort, prev_min)
@@ -302,7 +302,7 @@ def test_device_entries_on_a_caller_stream(hip, oracle, entry):
                 ref = hip.rrtmg_lw_mcica_subcol_from_dict(dn, 140, 0, icld=2, spectral=True, out=_spec_only(ncol, nlay))
         hip.check(side.cuda_stream)
     finally:
-        hip.set_batch(131072)
+        hip.set_batch(0)
     got = _host_view(o)
     for k in BROAD + SPEC:
         assert np.array_equal(got[k], ref[k]), (entry, k)

@@ -136,8 +136,70 @@ thread_local State *g_cur = &g_states[0];
 #define G (*g_cur)
 std::mutex g_mu;
 
+// ---- a GCM call below the C entry points --------------------------------------------------------------------------------------------
+// An extern "C" entry fills these once and everything beneath takes them.  The arrays travel in the structs of kernels.hip - GcmIn (the
+// McICA entries: its six cloud members null, McIn beside it), FluxOut with the spectral four, the generator's alpha as a plain pointer
+// beside them - whether they hold the caller's host pointers (above the staging layer) or device pointers.
+struct CallDesc {
+    int ncol, nlay;
+    int *icld;                                    // in / out: the entries write back the value they clamp it to
+    int idrv, inflg, iceflg, liqflg;
+    int permuteseed = 0; int *irng = nullptr;     // the fused generator + solver entries
+    bool spectral = false;                        // a *_spectral entry: uflxs and dflxs are required (check_spec)
+};
+CallDesc spectral(CallDesc d) { d.spectral = true; return d; }
+
+// The arrays of a call by position: the inputs in rrtmg_lw's order (what "argument %d" of a refusal counts), the generator's alpha, the
+// outputs.  A list of a call's pointers (gcm_pointers, flux_pointers) is indexed by these and by nothing else.
+enum ArrayPos {
+    A_PLAY, A_PLEV, A_TLAY, A_TLEV, A_TSFC, A_H2OVMR, A_O3VMR, A_CO2VMR, A_CH4VMR, A_N2OVMR, A_O2VMR, A_CFC11VMR, A_CFC12VMR, A_CFC22VMR,
+    A_CCL4VMR, A_EMIS, A_CLDFR, A_TAUCLD, A_CICEWP, A_CLIQWP, A_REICE, A_RELIQ, A_TAUAER, A_ALPHA,
+    A_UFLX, A_DFLX, A_HR, A_UFLXC, A_DFLXC, A_HRC, A_DUFLX_DT, A_DUFLXC_DT, A_UFLXS, A_DFLXS, A_UFLXCS, A_DFLXCS, NA_CALL,
+    NA_GCM = A_ALPHA,       // rrtmg_lw's input arrays
+    NA_IN = A_UFLX          // ... and alpha
+};
+// every array is [rows][ncol][inner] with rows = per_layer x nlay + extra; cloud: inatm reads it only when icld >= 1 (:893-910)
+struct ArrayShape { size_t inner, per_layer, extra; bool cloud; };
+constexpr ArrayShape CALL_ARRAYS[NA_CALL] = {
+    {1, 1, 0, false}, {1, 1, 1, false}, {1, 1, 0, false}, {1, 1, 1, false}, {1, 0, 1, false},                      // play plev tlay tlev tsfc
+    {1, 1, 0, false}, {1, 1, 0, false}, {1, 1, 0, false}, {1, 1, 0, false}, {1, 1, 0, false}, {1, 1, 0, false},  // h2o o3 co2 ch4 n2o o2
+    {1, 1, 0, false}, {1, 1, 0, false}, {1, 1, 0, false}, {1, 1, 0, false}, {1, 0, 16, false},                     // cfc11 cfc12 cfc22 ccl4, emis (ncol,16)
+    {1, 1, 0, true}, {NBND, 1, 0, true}, {1, 1, 0, true}, {1, 1, 0, true}, {1, 1, 0, true}, {1, 1, 0, true},     // cldfr taucld (16,ncol,nlay) cicewp cliqwp reice reliq
+    {1, 16, 0, false}, {1, 1, 0, true},                                                                            // tauaer (ncol,nlay,16), alpha
+    {1, 1, 1, false}, {1, 1, 1, false}, {1, 1, 0, false}, {1, 1, 1, false}, {1, 1, 1, false}, {1, 1, 0, false},  // uflx dflx hr uflxc dflxc hrc
+    {1, 1, 1, false}, {1, 1, 1, false},                                                                            // duflx_dt duflxc_dt
+    {1, 16, 16, false}, {1, 16, 16, false}, {1, 16, 16, false}, {1, 16, 16, false}};                               // the spectral four (ncol,nlay+1,16)
+size_t rows_of(int a, size_t L) { return CALL_ARRAYS[a].per_layer * L + CALL_ARRAYS[a].extra; }
+
+void gcm_pointers(const GcmIn &g, const double *alpha, const double *(&p)[NA_IN])
+{
+    p[A_PLAY] = g.play; p[A_PLEV] = g.plev; p[A_TLAY] = g.tlay; p[A_TLEV] = g.tlev; p[A_TSFC] = g.tsfc; p[A_H2OVMR] = g.h2ovmr;
+    p[A_O3VMR] = g.o3vmr; p[A_CO2VMR] = g.co2vmr; p[A_CH4VMR] = g.ch4vmr; p[A_N2OVMR] = g.n2ovmr; p[A_O2VMR] = g.o2vmr;
+    p[A_CFC11VMR] = g.cfc11vmr; p[A_CFC12VMR] = g.cfc12vmr; p[A_CFC22VMR] = g.cfc22vmr; p[A_CCL4VMR] = g.ccl4vmr; p[A_EMIS] = g.emis;
+    p[A_CLDFR] = g.cldfr; p[A_TAUCLD] = g.taucld; p[A_CICEWP] = g.cicewp; p[A_CLIQWP] = g.cliqwp; p[A_REICE] = g.reice;
+    p[A_RELIQ] = g.reliq; p[A_TAUAER] = g.tauaer; p[A_ALPHA] = alpha;
+}
+GcmIn gcm_from(const double *const *p)          // p[A_PLAY .. A_TAUAER]
+{
+    return GcmIn{p[A_PLAY], p[A_PLEV], p[A_TLAY], p[A_TLEV], p[A_TSFC], p[A_H2OVMR], p[A_O3VMR], p[A_CO2VMR], p[A_CH4VMR], p[A_N2OVMR],
+                 p[A_O2VMR], p[A_CFC11VMR], p[A_CFC12VMR], p[A_CFC22VMR], p[A_CCL4VMR], p[A_EMIS], p[A_CLDFR], p[A_TAUCLD], p[A_CICEWP],
+                 p[A_CLIQWP], p[A_REICE], p[A_RELIQ], p[A_TAUAER]};
+}
+void flux_pointers(const FluxOut &o, double *(&p)[NA_CALL])          // fills p[A_UFLX .. A_DFLXCS]
+{
+    p[A_UFLX] = o.uflx; p[A_DFLX] = o.dflx; p[A_HR] = o.hr; p[A_UFLXC] = o.uflxc; p[A_DFLXC] = o.dflxc; p[A_HRC] = o.hrc;
+    p[A_DUFLX_DT] = o.duflx_dt; p[A_DUFLXC_DT] = o.duflxc_dt;
+    p[A_UFLXS] = o.uflxs; p[A_DFLXS] = o.dflxs; p[A_UFLXCS] = o.uflxcs; p[A_DFLXCS] = o.dflxcs;
+}
+FluxOut flux_from(double *const *p)
+{
+    return FluxOut{p[A_UFLX], p[A_DFLX], p[A_HR], p[A_UFLXC], p[A_DFLXC], p[A_HRC], p[A_DUFLX_DT], p[A_DUFLXC_DT], nullptr, nullptr,
+                   p[A_UFLXS], p[A_DFLXS], p[A_UFLXCS], p[A_DFLXCS]};
+}
+bool have_outs(const FluxOut &o) { return o.uflx && o.dflx && o.hr && o.uflxc && o.dflxc && o.hrc; }
+
 // aggregation of small calls (rrtmg_lw_hip_queue_*): recorded chunks and the pinned staging set they are packed into
-struct QueuedChunk { int ncol; int *icld; const double *in[24]; double *out[8]; };       // in[23]: alpha of the generator (fused McICA calls; optional)
+struct QueuedChunk { CallDesc d; GcmIn in; const double *alpha; FluxOut out; };       // alpha: the generator's (fused McICA calls; optional)
 struct ChunkQueue {
     bool open = false;
     int nlay = 0, icld = 0, idrv = 0, inflg = 0, iceflg = 0, liqflg = 0;
@@ -1185,19 +1247,22 @@ int check_common(int ncol, int nlay)
 
 // Spectral outputs of the *_spectral entries: per band the flux the band adds to the broadband one (ncol,nlay+1,16), uflxs and dflxs
 // required, the clear-sky pair both null or both set.  They reach the sweeps through FluxOut (run_sweep: the SPEC instantiations).
-struct SpecOut { double *uflxs = nullptr, *dflxs = nullptr, *uflxcs = nullptr, *dflxcs = nullptr; };
-int check_spec(const SpecOut &sp)
+int check_spec(const FluxOut &o)
 {
-    if (!sp.uflxs || !sp.dflxs) return fail(RRTMG_LW_HIP_EARG, "spectral entry: uflxs and dflxs are required");
-    if (!sp.uflxcs != !sp.dflxcs) return fail(RRTMG_LW_HIP_EARG, "spectral entry: uflxcs and dflxcs must be both null or both set");
+    if (!o.uflxs || !o.dflxs) return fail(RRTMG_LW_HIP_EARG, "spectral entry: uflxs and dflxs are required");
+    if (!o.uflxcs != !o.dflxcs) return fail(RRTMG_LW_HIP_EARG, "spectral entry: uflxcs and dflxcs must be both null or both set");
     return 0;
 }
-void put_spec(FluxOut &o, const SpecOut *sp)
+// what the rrtmg_lw entries check first; an icld out of range comes back as 2 (src/rrtmg_lw_rad.nomcica.f90:456, src/rrtmg_lw_rad.f90:469)
+int check_call(const CallDesc &d, const FluxOut &out)
 {
-    if (!sp) return;
-    o.uflxs = sp->uflxs; o.dflxs = sp->dflxs; o.uflxcs = sp->uflxcs; o.dflxcs = sp->dflxcs;
+    if (int rc = check_common(d.ncol, d.nlay)) return rc;
+    if (d.spectral) if (int rc = check_spec(out)) return rc;
+    if (!d.icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
+    if (*d.icld < 0 || *d.icld > 3) *d.icld = 2;
+    if (d.idrv == 1 && (!out.duflx_dt || !out.duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
+    return 0;
 }
-
 
 // ---- host-pointer staging ---------------------------------------------------------------------------
 // Every array of the interface is [rows][ncol][inner] with `inner` fastest (inner = 1 for (ncol,nlay) arrays,
@@ -1214,16 +1279,56 @@ struct HostIn {
     unsigned long long static_gen = 0;                    // != 0: the caller declared the array static (rrtmg_lw_hip_host_static): row scans are cached per batch
 };
 struct HostOut { double *h; size_t rows; double *d; bool active; bool pinned = false; };
-// the spectral outputs of a host-pointer call as staged arrays of 16 (nlay + 1) rows, after the eight broadband ones (no rows when absent)
-void add_spec_outs(std::vector<HostOut> &outs, const SpecOut *sp, size_t L)
+// Where input `a` stands in a call's staged list: tauaer before the cloud arrays (the order of the rows in the device buffer and of the copies)
+constexpr int staged_at(int a) { return a < A_CLDFR ? a : a == A_TAUAER ? (int)A_CLDFR : a + 1; }
+
+// The staged inputs of a host-pointer call, the first n of rrtmg_lw's arrays (gas optics: the 16 up to emis), and their null checks.
+// The cloud arrays travel only with `cloud` - the McICA entry's sub-column arrays `m` in their places - and taucld with tau_inner values
+// per (column, layer).
+int host_ins(std::vector<HostIn> &ins, const GcmIn &g, const McIn *m, size_t L, bool cloud, size_t tau_inner, int n = NA_GCM, const char *who = "")
 {
-    const SpecOut so = sp ? *sp : SpecOut{};
-    for (double *h : {so.uflxs, so.dflxs, so.uflxcs, so.dflxcs}) outs.push_back({h, h ? (size_t)NBND * (L + 1) : 0, nullptr, h != nullptr});
+    const double *p[NA_IN];
+    gcm_pointers(g, nullptr, p);
+    if (m) { p[A_CLDFR] = m->cldfmcl; p[A_TAUCLD] = m->taucmcl; p[A_CICEWP] = m->ciwpmcl; p[A_CLIQWP] = m->clwpmcl; p[A_REICE] = m->reicmcl; p[A_RELIQ] = m->relqmcl; }
+    ins.assign((size_t)n, HostIn{});
+    for (int a = 0; a < n; a++) {
+        // (McICA: cldfmcl, taucmcl, ciwpmcl, clwpmcl are (ngpt,ncol,nlay); reicmcl and relqmcl (ncol,nlay) like reice and reliq)
+        const size_t inner = m && a >= A_CLDFR && a <= A_CLIQWP ? (size_t)NGPT : a == A_TAUCLD ? tau_inner : CALL_ARRAYS[a].inner;
+        ins[staged_at(a)] = HostIn{CALL_ARRAYS[a].cloud && !cloud ? nullptr : p[a], inner, rows_of(a, L), nullptr};
+    }
+    for (int a = 0; a < n; a++) if (!CALL_ARRAYS[a].cloud && !p[a]) return fail(RRTMG_LW_HIP_EARG, "%snull input array (argument %d)", who, a);
+    for (int a = 0; a < n; a++) if (cloud && CALL_ARRAYS[a].cloud && !p[a]) return fail(RRTMG_LW_HIP_EARG, m ? "null McICA cloud array" : "null cloud array");
+    return 0;
 }
-void put_spec_staged(FluxOut &o, const std::vector<HostOut> &v)
+// ... and a batch's staged device arrays as run_batch takes them
+GcmIn staged_gcm(const std::vector<HostIn> &in)
 {
-    o.uflxs = v[8].active ? v[8].d : nullptr; o.dflxs = v[9].active ? v[9].d : nullptr;
-    o.uflxcs = v[10].active ? v[10].d : nullptr; o.dflxcs = v[11].active ? v[11].d : nullptr;
+    const double *p[NA_IN] = {};
+    for (int a = 0; a < (int)in.size(); a++) p[a] = in[staged_at(a)].d;
+    return gcm_from(p);
+}
+// a batch's layers without cloud, found by rows_below on the cloud fraction: those rows of it have just been read to their end, the
+// other cloud arrays are not read there (nor summed, nor scanned, nor copied)
+void skip_cloudfree(std::vector<HostIn> &ins, const unsigned char *cloudfree, const unsigned char *uniform, const uint64_t *bits)
+{
+    ins[staged_at(A_CLDFR)].known = uniform; ins[staged_at(A_CLDFR)].known_bits = bits;
+    for (int a = A_TAUCLD; a <= A_RELIQ; a++) ins[staged_at(a)].skip = cloudfree;
+}
+// The staged outputs: the eight broadband arrays (the derivatives active with idrv = 1), then the spectral four (no rows when absent)
+std::vector<HostOut> host_outs(const FluxOut &o, size_t L, int idrv)
+{
+    double *p[NA_CALL];
+    flux_pointers(o, p);
+    std::vector<HostOut> outs;
+    for (int a = A_UFLX; a < A_UFLXS; a++) outs.push_back({p[a], rows_of(a, L), nullptr, a < A_DUFLX_DT || idrv == 1});
+    for (int a = A_UFLXS; a < NA_CALL; a++) outs.push_back({p[a], p[a] ? rows_of(a, L) : 0, nullptr, p[a] != nullptr});
+    return outs;
+}
+FluxOut staged_flux(const std::vector<HostOut> &v)
+{
+    double *p[NA_CALL];
+    for (int a = A_UFLX; a < NA_CALL; a++) p[a] = a < A_UFLXS || v[a - A_UFLX].active ? v[a - A_UFLX].d : nullptr;
+    return flux_from(p);
 }
 int bounce_h2d(void *dst, const void *src, size_t bytes);
 int bounce_d2h(void *dst, const void *src, size_t bytes);
@@ -2459,73 +2564,50 @@ int rrtmg_lw_hip_check(void *stream)
 // the state (index into the devices of rrtmg_lw_hip_init_devices) this thread's last device-pointer entry ran on
 int rrtmg_lw_hip_last_device_state(void) { return tl_dev_state; }
 
-static int nomcica_device(
-    int ncol, int nlay, int *icld, int idrv,
-    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
-    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
-    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
-    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
-    const double *reice, const double *reliq, const double *tauaer,
-    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
-    double *duflx_dt, double *duflxc_dt, const SpecOut *sp, void *stream)
+static int nomcica_device(const CallDesc &d, const GcmIn &g, const FluxOut &out, void *stream)
 {
-    ENTRY_LOCK_FOR(play);
-    if (int rc = check_common(ncol, nlay)) return rc;
-    if (sp) if (int rc = check_spec(*sp)) return rc;
-    if (!icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
-    if (*icld < 0 || *icld > 3) *icld = 2;                       // src/rrtmg_lw_rad.nomcica.f90:456
-    if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
-    const int mode = *icld == 0 ? 0 : (*icld == 1 ? 1 : 2);      // :546-560 (icld=0 -> rtrnmr clear branch)
-    const int nbmax = balanced_batch(ncol, eff_batch(nlay));
-    if (int rc = ensure_workspace(nlay, nbmax, mode != 0, false, idrv, mode)) return rc;
-    GcmIn g{play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr,
-            ccl4vmr, emis, cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer};
-    FluxOut out{uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt, nullptr, nullptr};
-    put_spec(out, sp);
-    return run_pipelined((hipStream_t)stream, ncol, nlay, mode, idrv, g, inflglw, iceflglw, liqflglw, out, nullptr);
+    ENTRY_LOCK_FOR(g.play);
+    if (int rc = check_call(d, out)) return rc;
+    const int mode = *d.icld == 0 ? 0 : (*d.icld == 1 ? 1 : 2);      // :546-560 (icld=0 -> rtrnmr clear branch)
+    const int nbmax = balanced_batch(d.ncol, eff_batch(d.nlay));
+    if (int rc = ensure_workspace(d.nlay, nbmax, mode != 0, false, d.idrv, mode)) return rc;
+    return run_pipelined((hipStream_t)stream, d.ncol, d.nlay, mode, d.idrv, g, d.inflg, d.iceflg, d.liqflg, out, nullptr);
 }
 
-#define NOMCICA_PARAMS                                                                                          \
-    int ncol, int nlay, int *icld, int idrv,                                                                    \
+#define GCM_PARAMS                                                                                              \
     const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,         \
     const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr, \
     const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,               \
-    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,                        \
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,                     \
-    const double *reice, const double *reliq, const double *tauaer,                                            \
-    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,                         \
-    double *duflx_dt, double *duflxc_dt
-#define NOMCICA_ARGS                                                                                            \
-    ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, \
-    cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, \
-    tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt
+    const double *ccl4vmr, const double *emis
+#define OUT_PARAMS                                                                                              \
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc, double *duflx_dt, double *duflxc_dt
+#define CLOUD_PARAMS                                                                                            \
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp, const double *reice, const double *reliq
+#define NOMCICA_PARAMS                                                                                          \
+    int ncol, int nlay, int *icld, int idrv, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw, CLOUD_PARAMS, const double *tauaer, OUT_PARAMS
 #define SPEC_PARAMS double *uflxs, double *dflxs, double *uflxcs, double *dflxcs
+// ... and the same names as initialisers of GcmIn{GCM_NAMES, CLOUD_NAMES, tauaer} and FluxOut{OUT_NAMES[, SPEC_NAMES]}: an entry fills them once
+#define GCM_NAMES play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis
+#define CLOUD_NAMES cldfr, taucld, cicewp, cliqwp, reice, reliq
+#define OUT_NAMES uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt
+#define SPEC_NAMES nullptr, nullptr, uflxs, dflxs, uflxcs, dflxcs          /* (fnet, fnetc: the column entry's) */
 
 int rrtmg_lw_hip_run_nomcica_device(NOMCICA_PARAMS, void *stream)
 {
-    return nomcica_device(NOMCICA_ARGS, nullptr, stream);
+    return nomcica_device({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw}, {GCM_NAMES, CLOUD_NAMES, tauaer}, {OUT_NAMES}, stream);
 }
 int rrtmg_lw_hip_run_nomcica_spectral_device(NOMCICA_PARAMS, SPEC_PARAMS, void *stream)
 {
-    const SpecOut sp{uflxs, dflxs, uflxcs, dflxcs};
-    return nomcica_device(NOMCICA_ARGS, &sp, stream);
+    return nomcica_device(spectral({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw}), {GCM_NAMES, CLOUD_NAMES, tauaer}, {OUT_NAMES, SPEC_NAMES}, stream);
 }
 
 }   // extern "C"
 
 namespace {
 // columns [c0, c1) of the caller's host arrays (ncol columns wide) on the calling thread's current device state; no lock taken
-int nomcica_host_range(int ncol, int c0, int c1, int nlay, int icld, int idrv,
-    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
-    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
-    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
-    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
-    const double *reice, const double *reliq, const double *tauaer,
-    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
-    double *duflx_dt, double *duflxc_dt, const SpecOut *sp)
+int nomcica_host_range(const CallDesc &d, int icld, int c0, int c1, const GcmIn &g, const FluxOut &o)
 {
+    const int ncol = d.ncol, nlay = d.nlay, idrv = d.idrv;
     if (int rc = check_common(ncol, nlay)) return rc;
     HIP_TRY(hipDeviceSynchronize());        // asynchronous device-entry work of earlier calls shares the workspace
     const int mode = icld == 0 ? 0 : (icld == 1 ? 1 : 2);
@@ -2539,15 +2621,9 @@ int nomcica_host_range(int ncol, int c0, int c1, int nlay, int icld, int idrv,
     //  * with inflglw >= 1 cldprop reads taucld only through the sum over the bands, tauctot (src/rrtmg_lw_cldprop.f90:173-186): the sum is
     //    formed here, in the reference's order, on the host threads - one value per (column, layer) travels instead of sixteen;
     //  * rows that hold one value for all columns of a batch - zero aerosol / cloud rows, well-mixed gases - are not copied (stage_rows).
-    const bool use_tot = cloud && inflglw != 0;
-    std::vector<HostIn> ins = {
-        {play, 1, L, 0}, {plev, 1, L + 1, 0}, {tlay, 1, L, 0}, {tlev, 1, L + 1, 0}, {tsfc, 1, 1, 0},
-        {h2ovmr, 1, L, 0}, {o3vmr, 1, L, 0}, {co2vmr, 1, L, 0}, {ch4vmr, 1, L, 0}, {n2ovmr, 1, L, 0}, {o2vmr, 1, L, 0},
-        {cfc11vmr, 1, L, 0}, {cfc12vmr, 1, L, 0}, {cfc22vmr, 1, L, 0}, {ccl4vmr, 1, L, 0}, {emis, 1, 16, 0}, {tauaer, 1, 16 * L, 0},
-        {cloud ? cldfr : nullptr, 1, L, 0}, {cloud ? taucld : nullptr, (size_t)(use_tot ? 1 : NBND), L, 0}, {cloud ? cicewp : nullptr, 1, L, 0},
-        {cloud ? cliqwp : nullptr, 1, L, 0}, {cloud ? reice : nullptr, 1, L, 0}, {cloud ? reliq : nullptr, 1, L, 0}};
-    for (size_t k = 0; k < 17; k++) if (!ins[k].h) return fail(RRTMG_LW_HIP_EARG, "null input array (argument %d)", (int)k);
-    if (cloud) for (size_t k = 17; k < ins.size(); k++) if (!ins[k].h) return fail(RRTMG_LW_HIP_EARG, "null cloud array");
+    const bool use_tot = cloud && d.inflg != 0;
+    std::vector<HostIn> ins;
+    if (int rc = host_ins(ins, g, nullptr, L, cloud, use_tot ? 1 : NBND)) return rc;
     if (use_tot && G.h_tot_doubles < HOST_SETS * L * (size_t)nbmax) {
         if (G.h_tot) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipHostFree(G.h_tot)); G.h_tot = nullptr; G.h_tot_doubles = 0; }
         HIP_TRY(hipHostMalloc((void **)&G.h_tot, HOST_SETS * L * (size_t)nbmax * sizeof(double), hipHostMallocDefault));
@@ -2557,10 +2633,8 @@ int nomcica_host_range(int ncol, int c0, int c1, int nlay, int icld, int idrv,
     std::vector<uint64_t> cf_bits(L, 0);
     auto prep = [&](int k, int col0, int nb, hipStream_t) -> int {
         if (!cloud) return 0;
-        // layers without cloud in any column of the batch: the other five cloud arrays are not read there (nor summed, nor scanned, nor copied)
-        rows_below(cldfr, 1, L, (size_t)ncol, (size_t)col0, (size_t)nb, 1.e-20, cloudfree.data(), cf_uni.data(), cf_bits.data());
-        ins[17].known = cf_uni.data(); ins[17].known_bits = cf_bits.data();        // (those layers of cldfr have just been read to their end)
-        for (size_t a = 18; a < ins.size(); a++) ins[a].skip = cloudfree.data();
+        rows_below(g.cldfr, 1, L, (size_t)ncol, (size_t)col0, (size_t)nb, 1.e-20, cloudfree.data(), cf_uni.data(), cf_bits.data());
+        skip_cloudfree(ins, cloudfree.data(), cf_uni.data(), cf_bits.data());
         if (!use_tot) return 0;
         double *tot = G.h_tot + (size_t)k * L * (size_t)nbmax;        // (the pipeline has waited for the copies that read scratch set k last)
         size_t cloudy_layers = 0;
@@ -2575,7 +2649,7 @@ int nomcica_host_range(int ncol, int c0, int c1, int nlay, int icld, int idrv,
                     if (task % (size_t)nt != (size_t)t) continue;
                     const size_t c1 = std::min((size_t)nb, (pc + 1) * piece);
                     for (size_t c = pc * piece; c < c1; c++) {
-                        const double *p = taucld + (size_t)NBND * ((size_t)col0 + c + (size_t)ncol * lay);
+                        const double *p = g.taucld + (size_t)NBND * ((size_t)col0 + c + (size_t)ncol * lay);
                         double sum = 0.0;
                         for (int ib = 0; ib < NBND; ib++) sum = sum + p[ib];
                         tot[lay * (size_t)nb + c] = sum;
@@ -2583,21 +2657,16 @@ int nomcica_host_range(int ncol, int c0, int c1, int nlay, int icld, int idrv,
                 }
             }
         });
-        ins[18].src = tot; ins[18].src_ncol = (size_t)nb; ins[18].src_col0 = 0; ins[18].src_pinned = true;      // rows of nb sums, from the pinned scratch
+        HostIn &tc = ins[staged_at(A_TAUCLD)];
+        tc.src = tot; tc.src_ncol = (size_t)nb; tc.src_col0 = 0; tc.src_pinned = true;      // rows of nb sums, from the pinned scratch
         return 0;
     };
-    std::vector<HostOut> outs = {{uflx, L + 1, 0, true}, {dflx, L + 1, 0, true}, {hr, L, 0, true}, {uflxc, L + 1, 0, true},
-                                 {dflxc, L + 1, 0, true}, {hrc, L, 0, true}, {duflx_dt, L + 1, 0, idrv == 1}, {duflxc_dt, L + 1, 0, idrv == 1}};
-    for (size_t k = 0; k < 6; k++) if (!outs[k].h) return fail(RRTMG_LW_HIP_EARG, "null output array");
-    add_spec_outs(outs, sp, L);
+    if (!have_outs(o)) return fail(RRTMG_LW_HIP_EARG, "null output array");
+    std::vector<HostOut> outs = host_outs(o, L, idrv);
     auto body = [&](hipStream_t s, int nb, int, std::vector<HostIn> &in, std::vector<HostOut> &out_) -> int {
-        GcmIn g{in[0].d, in[1].d, in[2].d, in[3].d, in[4].d, in[5].d, in[6].d, in[7].d, in[8].d, in[9].d, in[10].d,
-                in[11].d, in[12].d, in[13].d, in[14].d, in[15].d, in[17].d, use_tot ? nullptr : in[18].d, in[19].d, in[20].d, in[21].d, in[22].d, in[16].d,
-                use_tot ? in[18].d : nullptr};
-        ColIn c{};
-        FluxOut out{out_[0].d, out_[1].d, out_[2].d, out_[3].d, out_[4].d, out_[5].d, out_[6].d, out_[7].d, nullptr, nullptr};
-        put_spec_staged(out, out_);
-        return run_batch<true>(s, nb, 0, nb, nlay, mode, idrv, 1, 16, g, c, inflglw, iceflglw, liqflglw, out);
+        GcmIn gd = staged_gcm(in);
+        if (use_tot) { gd.tauctot = gd.taucld; gd.taucld = nullptr; }
+        return run_batch<true>(s, nb, 0, nb, nlay, mode, idrv, 1, 16, gd, ColIn{}, d.inflg, d.iceflg, d.liqflg, staged_flux(out_));
     };
     if (int rc = host_pipeline(ncol, c0, c1, nbmax, ins, outs, body, prep)) return rc;
     hipStream_t s = G.stream;
@@ -2631,68 +2700,36 @@ int fan_out(int ncol, RangeFn range)
     return 0;
 }
 
-int nomcica_host(int ncol, int nlay, int *icld, int idrv,
-    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
-    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
-    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
-    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
-    const double *reice, const double *reliq, const double *tauaer,
-    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
-    double *duflx_dt, double *duflxc_dt, const SpecOut *sp = nullptr)
+int nomcica_host(const CallDesc &d, const GcmIn &g, const FluxOut &out)
 {
-    if (int rc = check_common(ncol, nlay)) return rc;
-    if (sp) if (int rc = check_spec(*sp)) return rc;
-    if (!icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
-    if (*icld < 0 || *icld > 3) *icld = 2;
-    if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
-    const int ic = *icld;
-    return fan_out(ncol, [&](int c0, int c1) {
-        return nomcica_host_range(ncol, c0, c1, nlay, ic, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis,
-                              inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt, sp);
-    });
+    if (int rc = check_call(d, out)) return rc;
+    const int ic = *d.icld;
+    return fan_out(d.ncol, [&](int c0, int c1) { return nomcica_host_range(d, ic, c0, c1, g, out); });
 }
 bool comb_enabled();
 int comb_max();
 long long comb_calls_total();
 long long comb_passes_total();
-int nomcica_combined(int ncol, int nlay, int *icld, int idrv,
-    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
-    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
-    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
-    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
-    const double *reice, const double *reliq, const double *tauaer,
-    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
-    double *duflx_dt, double *duflxc_dt);
+int nomcica_combined(const CallDesc &d, const GcmIn &g, const FluxOut &out);
 }   // namespace
 
 extern "C" {
 
-int rrtmg_lw_hip_run_nomcica(
-    int ncol, int nlay, int *icld, int idrv,
-    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
-    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
-    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
-    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
-    const double *reice, const double *reliq, const double *tauaer,
-    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
-    double *duflx_dt, double *duflxc_dt)
+int rrtmg_lw_hip_run_nomcica(NOMCICA_PARAMS)
 {
-    if (ncol >= 1 && ncol <= comb_max() && icld && comb_enabled()) return nomcica_combined(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis,
-                              inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt);
+    const CallDesc d{ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw};
+    const GcmIn g{GCM_NAMES, CLOUD_NAMES, tauaer};
+    const FluxOut out{OUT_NAMES};
+    if (ncol >= 1 && ncol <= comb_max() && icld && comb_enabled()) return nomcica_combined(d, g, out);
     ENTRY_LOCK;
-    return nomcica_host(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis,
-                              inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt);
+    return nomcica_host(d, g, out);
 }
 
 // the same with spectral outputs; such a call does not join the combining entry (it takes the entry lock like any other call)
 int rrtmg_lw_hip_run_nomcica_spectral(NOMCICA_PARAMS, SPEC_PARAMS)
 {
     ENTRY_LOCK;
-    const SpecOut sp{uflxs, dflxs, uflxcs, dflxcs};
-    return nomcica_host(NOMCICA_ARGS, &sp);
+    return nomcica_host(spectral({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw}), {GCM_NAMES, CLOUD_NAMES, tauaer}, {OUT_NAMES, SPEC_NAMES});
 }
 
 // calls and device passes of the combining entry since the library was loaded (a pass serves one or more calls)
@@ -2754,11 +2791,7 @@ int rrtmg_lw_hip_run_columns(
 
 // ---- gas optics and Planck sources (include/rrtmg_lw_hip.h) ---------------------------------------------------------------------------
 #define OPTICS_GCM_PARAMS                                                                                       \
-    int ncol, int nlay, int idrv,                                                                               \
-    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,         \
-    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr, \
-    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,               \
-    const double *ccl4vmr, const double *emis,                                                                 \
+    int ncol, int nlay, int idrv, GCM_PARAMS,                                                                   \
     double *taug, double *fracs, double *planklay, double *planklev, double *plankbnd, double *dplankbnd_dt
 
 int rrtmg_lw_hip_gas_optics_device(OPTICS_GCM_PARAMS, void *stream)
@@ -2767,14 +2800,15 @@ int rrtmg_lw_hip_gas_optics_device(OPTICS_GCM_PARAMS, void *stream)
     if (int rc = check_common(ncol, nlay)) return rc;
     const OptOut o{taug, fracs, planklay, planklev, plankbnd, idrv == 1 ? dplankbnd_dt : nullptr};
     if (int rc = check_optics(idrv, o)) return rc;
-    const double *in[] = {play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis};
-    for (const double *p : in) if (!p) return fail(RRTMG_LW_HIP_EARG, "gas optics: null input array");
+    const GcmIn g{GCM_NAMES};
+    const double *in[NA_IN];
+    gcm_pointers(g, nullptr, in);
+    for (int a = 0; a <= A_EMIS; a++) if (!in[a]) return fail(RRTMG_LW_HIP_EARG, "gas optics: null input array");
     if (int rc = ensure_pipeline()) return rc;
     const int nbmax = balanced_batch(ncol, eff_batch(nlay));
     if (int rc = ensure_optics_ws(nlay, nbmax)) return rc;
     const hipStream_t s = (hipStream_t)stream;
     if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last, 0));      // an earlier call, possibly on another stream, still owns the workspace
-    const GcmIn g{play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis};
     for (int col0 = 0; col0 < ncol; col0 += nbmax)
         if (int rc = run_optics<true>(s, std::min(nbmax, ncol - col0), col0, ncol, nlay, idrv, g, ColIn{}, o)) return rc;
     HIP_TRY(hipEventRecord(G.ev_last, s));
@@ -2783,18 +2817,15 @@ int rrtmg_lw_hip_gas_optics_device(OPTICS_GCM_PARAMS, void *stream)
 }
 
 // columns [c0, c1) of a host-pointer gas-optics call on the calling thread's current device state (the fan-out's worker); no lock taken
-static int gas_optics_host_range(int c0, int c1, OPTICS_GCM_PARAMS)
+static int gas_optics_host_range(int ncol, int c0, int c1, int nlay, int idrv, const GcmIn &g, const OptOut &h)
 {
     HIP_TRY(hipDeviceSynchronize());        // asynchronous device-entry work of earlier calls shares the workspace
     const size_t L = (size_t)nlay;
-    std::vector<HostIn> ins = {
-        {play, 1, L, 0}, {plev, 1, L + 1, 0}, {tlay, 1, L, 0}, {tlev, 1, L + 1, 0}, {tsfc, 1, 1, 0},
-        {h2ovmr, 1, L, 0}, {o3vmr, 1, L, 0}, {co2vmr, 1, L, 0}, {ch4vmr, 1, L, 0}, {n2ovmr, 1, L, 0}, {o2vmr, 1, L, 0},
-        {cfc11vmr, 1, L, 0}, {cfc12vmr, 1, L, 0}, {cfc22vmr, 1, L, 0}, {ccl4vmr, 1, L, 0}, {emis, 1, 16, 0}};
-    for (size_t k = 0; k < ins.size(); k++) if (!ins[k].h) return fail(RRTMG_LW_HIP_EARG, "gas optics: null input array (argument %d)", (int)k);
-    auto out = [](double *h, size_t rows) { return HostOut{h, h ? rows : 0, nullptr, h != nullptr}; };
-    std::vector<HostOut> outs = {out(taug, (size_t)NGPT * L), out(fracs, (size_t)NGPT * L), out(planklay, NBND * L), out(planklev, NBND * (L + 1)),
-                                 out(plankbnd, NBND), out(idrv == 1 ? dplankbnd_dt : nullptr, NBND)};
+    std::vector<HostIn> ins;
+    if (int rc = host_ins(ins, g, nullptr, L, false, 0, A_EMIS + 1, "gas optics: ")) return rc;
+    auto out = [](double *p, size_t rows) { return HostOut{p, p ? rows : 0, nullptr, p != nullptr}; };
+    std::vector<HostOut> outs = {out(h.taug, (size_t)NGPT * L), out(h.fracs, (size_t)NGPT * L), out(h.planklay, NBND * L), out(h.planklev, NBND * (L + 1)),
+                                 out(h.plankbnd, NBND), out(idrv == 1 ? h.dplankbnd : nullptr, NBND)};
     // (the outputs are ~40 times a column's inputs: batches of at most ~256 MB of staging each)
     size_t per_col = 0;
     for (auto &a : ins) per_col += a.inner * a.rows * 8;
@@ -2803,11 +2834,9 @@ static int gas_optics_host_range(int c0, int c1, OPTICS_GCM_PARAMS)
     const int nbmax = balanced_batch(c1 - c0, cap);
     if (int rc = ensure_optics_ws(nlay, nbmax)) return rc;
     auto body = [&](hipStream_t s, int nb, int, std::vector<HostIn> &in, std::vector<HostOut> &o_) -> int {
-        const GcmIn g{in[0].d, in[1].d, in[2].d, in[3].d, in[4].d, in[5].d, in[6].d, in[7].d, in[8].d, in[9].d, in[10].d,
-                      in[11].d, in[12].d, in[13].d, in[14].d, in[15].d};
         auto d = [&](int k) { return o_[k].active ? o_[k].d : nullptr; };
         const OptOut o{d(0), d(1), d(2), d(3), d(4), d(5)};
-        return run_optics<true>(s, nb, 0, nb, nlay, idrv, g, ColIn{}, o);
+        return run_optics<true>(s, nb, 0, nb, nlay, idrv, staged_gcm(in), ColIn{}, o);
     };
     return host_pipeline(ncol, c0, c1, nbmax, ins, outs, body);
 }
@@ -2816,11 +2845,10 @@ int rrtmg_lw_hip_gas_optics(OPTICS_GCM_PARAMS)
 {
     ENTRY_LOCK;
     if (int rc = check_common(ncol, nlay)) return rc;
-    if (int rc = check_optics(idrv, OptOut{taug, fracs, planklay, planklev, plankbnd, dplankbnd_dt})) return rc;
-    return fan_out(ncol, [&](int c0, int c1) {
-        return gas_optics_host_range(c0, c1, ncol, nlay, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr,
-                                     cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, taug, fracs, planklay, planklev, plankbnd, dplankbnd_dt);
-    });
+    const OptOut o{taug, fracs, planklay, planklev, plankbnd, dplankbnd_dt};
+    if (int rc = check_optics(idrv, o)) return rc;
+    const GcmIn g{GCM_NAMES};
+    return fan_out(ncol, [&](int c0, int c1) { return gas_optics_host_range(ncol, c0, c1, nlay, idrv, g, o); });
 }
 
 int rrtmg_lw_hip_gas_optics_columns(
@@ -3000,23 +3028,6 @@ int rrtmg_lw_hip_calibrate_stream(long long bytes)
 // Aggregation of small calls (include/rrtmg_lw_hip.h): chunks are recorded, packed column-wise into one pinned staging set and
 // solved in one pass through the host-pointer entry.
 // ---------------------------------------------------------------------------------------------------
-}   // extern "C"
-
-namespace {
-// inner extent and number of rows of the 23 inputs ([rows][ncol][inner], run_nomcica's order with tauaer last) and 8 outputs
-void queue_shapes(int nlay, size_t (&in_inner)[23], size_t (&in_rows)[23], size_t (&out_rows)[8])
-{
-    const size_t L = (size_t)nlay;
-    const size_t rows[23] = {L, L + 1, L, L + 1, 1, L, L, L, L, L, L, L, L, L, L, 16, L, L, L, L, L, L, 16 * L};
-    for (int k = 0; k < 23; k++) { in_inner[k] = 1; in_rows[k] = rows[k]; }
-    in_inner[17] = NBND;                      // taucld (16, ncol, nlay)
-    const size_t orows[8] = {L + 1, L + 1, L, L + 1, L + 1, L, L + 1, L + 1};
-    for (int k = 0; k < 8; k++) out_rows[k] = orows[k];
-}
-}   // namespace
-
-extern "C" {
-
 int rrtmg_lw_hip_queue_begin(int nlay, int icld, int idrv, int inflglw, int iceflglw, int liqflglw)
 {
     ENTRY_LOCK;
@@ -3031,31 +3042,19 @@ int rrtmg_lw_hip_queue_begin(int nlay, int icld, int idrv, int inflglw, int icef
 
 int rrtmg_lw_hip_queue_columns(void) { std::lock_guard<std::mutex> lk(g_mu); return (int)Q.ncol; }
 
-int rrtmg_lw_hip_queue_add(
-    int ncol, int *icld,
-    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
-    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
-    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
-    const double *ccl4vmr, const double *emis,
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
-    const double *reice, const double *reliq, const double *tauaer,
-    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
-    double *duflx_dt, double *duflxc_dt)
+int rrtmg_lw_hip_queue_add(int ncol, int *icld, GCM_PARAMS, CLOUD_PARAMS, const double *tauaer, OUT_PARAMS)
 {
     ENTRY_LOCK;
     if (!Q.open) return fail(RRTMG_LW_HIP_EARG, "rrtmg_lw_hip_queue_begin has not been called");
     if (ncol < 1) return fail(RRTMG_LW_HIP_EARG, "bad chunk size %d", ncol);
     if (icld && *icld != Q.icld) return fail(RRTMG_LW_HIP_EARG, "chunk icld %d differs from the queue's %d", *icld, Q.icld);
-    QueuedChunk c{ncol, icld,
-                  {play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis,
-                   cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer},
-                  {uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt}};
+    const QueuedChunk c{{ncol, Q.nlay, icld, Q.idrv, Q.inflg, Q.iceflg, Q.liqflg}, {GCM_NAMES, CLOUD_NAMES, tauaer}, nullptr, {OUT_NAMES}};
     const int icld_eff = (Q.icld < 0 || Q.icld > 3) ? 2 : Q.icld;
-    for (int k = 0; k < 23; k++) {
-        const bool cloud_arr = k >= 16 && k <= 21;              // inatm reads the cloud arrays only when icld >= 1
-        if (!c.in[k] && !(cloud_arr && icld_eff == 0)) return fail(RRTMG_LW_HIP_EARG, "null input array (argument %d)", k);
-    }
-    for (int k = 0; k < 6; k++) if (!c.out[k]) return fail(RRTMG_LW_HIP_EARG, "null output array");
+    const double *in[NA_IN];
+    gcm_pointers(c.in, nullptr, in);
+    for (int a = 0; a < NA_GCM; a++)              // inatm reads the cloud arrays only when icld >= 1
+        if (!in[a] && !(CALL_ARRAYS[a].cloud && icld_eff == 0)) return fail(RRTMG_LW_HIP_EARG, "null input array (argument %d)", a);
+    if (!have_outs(c.out)) return fail(RRTMG_LW_HIP_EARG, "null output array");
     if (Q.idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
     if (Q.ncol + ncol > 0x7fffffffLL) return fail(RRTMG_LW_HIP_EARG, "too many queued columns");
     Q.chunks.push_back(c);
@@ -3077,73 +3076,58 @@ static void queue_parallel(size_t n, F f)
 
 // The chunks as ONE call: every array is [rows][columns][inner] - row r of a chunk goes to row r of the packed array at the chunk's column
 // offset (pinned set Q.pinned) - then nomcica_host on the packed arrays, then the outputs back to every chunk.  Caller holds the entry lock.
-// kind 0: rrtmg_lw (non-McICA); kind 1: the fused sub-column generator + McICA solver with the kissvec generator (a stream per column:
-// the columns of a packed call draw what they draw on their own), permuteseed and - has_alpha - the generator's alpha array as input 23
-static int mcica_subcol_host(int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng,
-    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
-    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
-    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
-    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp, const double *reice,
-    const double *reliq, const double *alpha, const double *tauaer,
-    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc, double *duflx_dt, double *duflxc_dt,
-    const SpecOut *sp = nullptr);
-static int solve_chunks(const std::vector<QueuedChunk> &chunks, long long N, int nlay, int icld_in, int idrv, int inflg, int iceflg, int liqflg,
-                        int kind = 0, int permuteseed = 0, bool has_alpha = false)
+// d: what the chunks share (nlay, idrv, the cloud flags, permuteseed), icld_in: their icld.  kind 0: rrtmg_lw (non-McICA); kind 1: the
+// fused sub-column generator + McICA solver with the kissvec generator (a stream per column: the columns of a packed call draw what they
+// draw on their own) and - has_alpha - the generator's alpha array
+static int mcica_subcol_host(const CallDesc &d, const GcmIn &g, const double *alpha, const FluxOut &out);
+static int solve_chunks(const std::vector<QueuedChunk> &chunks, long long N, CallDesc d, int icld_in, int kind = 0, bool has_alpha = false)
 {
-    size_t in_inner[23], in_rows[23], out_rows[8];
-    double *in_p[23], *out_p[8];
-    queue_shapes(nlay, in_inner, in_rows, out_rows);
-    size_t tot = 0;
-    for (int k = 0; k < 23; k++) tot += in_inner[k] * in_rows[k] * (size_t)N;
-    for (int k = 0; k < 8; k++) tot += out_rows[k] * (size_t)N;
-    if (has_alpha) tot += (size_t)nlay * (size_t)N;
+    const size_t L = (size_t)d.nlay;
+    auto doubles = [&](int a) { return CALL_ARRAYS[a].inner * rows_of(a, L) * (size_t)N; };
+    size_t tot = has_alpha ? doubles(A_ALPHA) : 0;
+    for (int a = 0; a < NA_GCM; a++) tot += doubles(a);
+    for (int a = A_UFLX; a < A_UFLXS; a++) tot += doubles(a);
     if (Q.pinned_doubles < tot) {
         if (Q.pinned) { forget_pinned(Q.pinned); (void)hipHostFree(Q.pinned); Q.pinned = nullptr; Q.pinned_doubles = 0; }
         HIP_TRY(hipHostMalloc((void **)&Q.pinned, tot * sizeof(double), hipHostMallocDefault));
         Q.pinned_doubles = tot;
         g_pinned.emplace_back((const char *)Q.pinned, tot * sizeof(double));
     }
+    double *in_p[NA_IN] = {}, *out_p[NA_CALL] = {};
     double *p = Q.pinned;
-    for (int k = 0; k < 23; k++) { in_p[k] = p; p += in_inner[k] * in_rows[k] * (size_t)N; }
-    for (int k = 0; k < 8; k++) { out_p[k] = p; p += out_rows[k] * (size_t)N; }
-    double *alpha_p = has_alpha ? p : nullptr;
+    for (int a = 0; a < NA_GCM; a++) { in_p[a] = p; p += doubles(a); }
+    for (int a = A_UFLX; a < A_UFLXS; a++) { out_p[a] = p; p += doubles(a); }
+    if (has_alpha) in_p[A_ALPHA] = p;
     const bool cloud = !(icld_in == 0);
     std::vector<size_t> offs(chunks.size());
-    { size_t off = 0; for (size_t i = 0; i < chunks.size(); i++) { offs[i] = off; off += (size_t)chunks[i].ncol; } }
+    { size_t off = 0; for (size_t i = 0; i < chunks.size(); i++) { offs[i] = off; off += (size_t)chunks[i].d.ncol; } }
     queue_parallel(chunks.size(), [&](size_t i) {          // (the copies are many short rows: host-bound, spread over a few threads)
         const QueuedChunk &c = chunks[i];
-        for (int k = 0; k < 23; k++) {
-            const bool cloud_arr = k >= 16 && k <= 21;
-            if (cloud_arr && !cloud) continue;
-            const size_t w = in_inner[k] * (size_t)c.ncol;
-            for (size_t r = 0; r < in_rows[k]; r++)
-                memcpy(in_p[k] + (r * (size_t)N + offs[i]) * in_inner[k], c.in[k] + r * w, w * sizeof(double));
+        const double *src[NA_IN];
+        gcm_pointers(c.in, c.alpha, src);
+        for (int a = 0; a < NA_IN; a++) {
+            if (!in_p[a] || (CALL_ARRAYS[a].cloud && !cloud)) continue;
+            const size_t inner = CALL_ARRAYS[a].inner, w = inner * (size_t)c.d.ncol;
+            for (size_t r = 0; r < rows_of(a, L); r++)
+                memcpy(in_p[a] + (r * (size_t)N + offs[i]) * inner, src[a] + r * w, w * sizeof(double));
         }
-        if (has_alpha && cloud)
-            for (size_t r = 0; r < (size_t)nlay; r++) memcpy(alpha_p + r * (size_t)N + offs[i], c.in[23] + r * (size_t)c.ncol, (size_t)c.ncol * sizeof(double));
     });
     int icld = icld_in, irng = 0;
-    const int rc = kind == 1
-        ? mcica_subcol_host((int)N, nlay, &icld, idrv, permuteseed, &irng, in_p[0], in_p[1], in_p[2], in_p[3], in_p[4], in_p[5], in_p[6], in_p[7],
-                            in_p[8], in_p[9], in_p[10], in_p[11], in_p[12], in_p[13], in_p[14], in_p[15], inflg, iceflg, liqflg,
-                            in_p[16], in_p[17], in_p[18], in_p[19], in_p[20], in_p[21], alpha_p, in_p[22],
-                            out_p[0], out_p[1], out_p[2], out_p[3], out_p[4], out_p[5], idrv == 1 ? out_p[6] : nullptr, idrv == 1 ? out_p[7] : nullptr)
-        : nomcica_host((int)N, nlay, &icld, idrv, in_p[0], in_p[1], in_p[2], in_p[3], in_p[4], in_p[5], in_p[6], in_p[7],
-                                            in_p[8], in_p[9], in_p[10], in_p[11], in_p[12], in_p[13], in_p[14], in_p[15], inflg, iceflg, liqflg,
-                                            cloud ? in_p[16] : nullptr, cloud ? in_p[17] : nullptr, cloud ? in_p[18] : nullptr, cloud ? in_p[19] : nullptr,
-                                            cloud ? in_p[20] : nullptr, cloud ? in_p[21] : nullptr, in_p[22],
-                                            out_p[0], out_p[1], out_p[2], out_p[3], out_p[4], out_p[5],
-                                            idrv == 1 ? out_p[6] : nullptr, idrv == 1 ? out_p[7] : nullptr);
+    d.ncol = (int)N; d.icld = &icld; d.irng = &irng;
+    FluxOut out = flux_from(out_p);
+    if (d.idrv != 1) out.duflx_dt = out.duflxc_dt = nullptr;
+    const int rc = kind == 1 ? mcica_subcol_host(d, gcm_from(in_p), in_p[A_ALPHA], out) : nomcica_host(d, gcm_from(in_p), out);
     if (rc == 0) {
         queue_parallel(chunks.size(), [&](size_t i) {
             const QueuedChunk &c = chunks[i];
-            for (int k = 0; k < 8; k++) {
-                if (!c.out[k] || (k >= 6 && idrv != 1)) continue;
-                for (size_t r = 0; r < out_rows[k]; r++)
-                    memcpy(c.out[k] + r * (size_t)c.ncol, out_p[k] + r * (size_t)N + offs[i], (size_t)c.ncol * sizeof(double));
+            double *dst[NA_CALL];
+            flux_pointers(c.out, dst);
+            for (int a = A_UFLX; a < A_UFLXS; a++) {
+                if (!dst[a] || (a >= A_DUFLX_DT && d.idrv != 1)) continue;
+                for (size_t r = 0; r < rows_of(a, L); r++)
+                    memcpy(dst[a] + r * (size_t)c.d.ncol, out_p[a] + r * (size_t)N + offs[i], (size_t)c.d.ncol * sizeof(double));
             }
-            if (c.icld) *c.icld = icld;
+            if (c.d.icld) *c.d.icld = icld;
         });
     }
     return rc;
@@ -3154,7 +3138,7 @@ extern "C" int rrtmg_lw_hip_queue_flush(void)
     ENTRY_LOCK;             // held over pack, solve and scatter: another thread's queue_add / queue_begin / finalize must not touch the chunk list or the pinned set in between
     if (!Q.open) return fail(RRTMG_LW_HIP_EARG, "rrtmg_lw_hip_queue_begin has not been called");
     if (Q.ncol == 0) return 0;
-    const int rc = solve_chunks(Q.chunks, Q.ncol, Q.nlay, Q.icld, Q.idrv, Q.inflg, Q.iceflg, Q.liqflg);
+    const int rc = solve_chunks(Q.chunks, Q.ncol, CallDesc{0, Q.nlay, nullptr, Q.idrv, Q.inflg, Q.iceflg, Q.liqflg}, Q.icld);
     Q.chunks.clear();
     Q.ncol = 0;
     return rc;
@@ -3171,8 +3155,8 @@ extern "C" int rrtmg_lw_hip_queue_flush(void)
 namespace {
 struct CallReq {
     QueuedChunk c;
-    int nlay, icld, idrv, inflg, iceflg, liqflg;
-    int kind = 0, permuteseed = 0;             // kind 1: the fused generator + McICA entry (kissvec); see solve_chunks
+    int icld = 0;                              // *c.d.icld when the call came in
+    int kind = 0;                              // kind 1: the fused generator + McICA entry (kissvec); see solve_chunks
     int rc = 0;
     bool done = false, lead = false;
     std::string err;                           // the text of rc != 0, handed to the owner's thread
@@ -3200,23 +3184,18 @@ void comb_serve(std::vector<CallReq *> &batch)
         long long N = 0;
         for (size_t j = i; j < batch.size(); j++) {
             const CallReq &b = *batch[j];
-            if (!served[j] && b.nlay == a.nlay && b.icld == a.icld && b.idrv == a.idrv && b.inflg == a.inflg && b.iceflg == a.iceflg && b.liqflg == a.liqflg &&
-                b.kind == a.kind && b.permuteseed == a.permuteseed && (b.c.in[23] != nullptr) == (a.c.in[23] != nullptr) &&
-                N + b.c.ncol <= 0x7fffffffLL) { grp.push_back(j); N += b.c.ncol; }
+            const CallDesc &x = a.c.d, &y = b.c.d;
+            if (!served[j] && y.nlay == x.nlay && b.icld == a.icld && y.idrv == x.idrv && y.inflg == x.inflg && y.iceflg == x.iceflg && y.liqflg == x.liqflg &&
+                b.kind == a.kind && y.permuteseed == x.permuteseed && (b.c.alpha != nullptr) == (a.c.alpha != nullptr) &&
+                N + y.ncol <= 0x7fffffffLL) { grp.push_back(j); N += y.ncol; }
         }
         auto alone = [&](CallReq &r) {
-            const QueuedChunk &c = r.c;
             int icld = r.icld, irng = 0;
+            CallDesc d = r.c.d;
+            d.icld = &icld; d.irng = &irng;
             g_comb_passes++;
-            if (r.kind == 1)
-                r.rc = mcica_subcol_host(c.ncol, r.nlay, &icld, r.idrv, r.permuteseed, &irng, c.in[0], c.in[1], c.in[2], c.in[3], c.in[4], c.in[5], c.in[6], c.in[7],
-                                         c.in[8], c.in[9], c.in[10], c.in[11], c.in[12], c.in[13], c.in[14], c.in[15], r.inflg, r.iceflg, r.liqflg, c.in[16], c.in[17],
-                                         c.in[18], c.in[19], c.in[20], c.in[21], c.in[23], c.in[22], c.out[0], c.out[1], c.out[2], c.out[3], c.out[4], c.out[5], c.out[6], c.out[7]);
-            else
-            r.rc = nomcica_host(c.ncol, r.nlay, &icld, r.idrv, c.in[0], c.in[1], c.in[2], c.in[3], c.in[4], c.in[5], c.in[6], c.in[7], c.in[8], c.in[9], c.in[10],
-                                c.in[11], c.in[12], c.in[13], c.in[14], c.in[15], r.inflg, r.iceflg, r.liqflg, c.in[16], c.in[17], c.in[18], c.in[19], c.in[20], c.in[21],
-                                c.in[22], c.out[0], c.out[1], c.out[2], c.out[3], c.out[4], c.out[5], c.out[6], c.out[7]);
-            if (c.icld) *c.icld = icld;
+            r.rc = r.kind == 1 ? mcica_subcol_host(d, r.c.in, r.c.alpha, r.c.out) : nomcica_host(d, r.c.in, r.c.out);
+            if (r.c.d.icld) *r.c.d.icld = icld;
             if (r.rc != 0) r.err = G.err;
         };
         if (grp.size() == 1) alone(a);
@@ -3224,7 +3203,7 @@ void comb_serve(std::vector<CallReq *> &batch)
             std::vector<QueuedChunk> chunks;
             for (size_t j : grp) chunks.push_back(batch[j]->c);
             g_comb_passes++;
-            const int rc = solve_chunks(chunks, N, a.nlay, a.icld, a.idrv, a.inflg, a.iceflg, a.liqflg, a.kind, a.permuteseed, a.c.in[23] != nullptr);
+            const int rc = solve_chunks(chunks, N, a.c.d, a.icld, a.kind, a.c.alpha != nullptr);
             if (rc == 0) { for (size_t j : grp) batch[j]->rc = 0; }
             else { for (size_t j : grp) alone(*batch[j]); }      // an error (one caller's bad particle size ...) belongs to the call that caused it: each chunk again, on its own
         }
@@ -3283,34 +3262,26 @@ bool comb_enabled() { static const bool on = []() { const char *e = getenv("RRTM
 long long comb_calls_total() { return g_comb_calls.load(); }
 long long comb_passes_total() { return g_comb_passes.load(); }
 
-int nomcica_combined(int ncol, int nlay, int *icld, int idrv,
-    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
-    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
-    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
-    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
-    const double *reice, const double *reliq, const double *tauaer,
-    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
-    double *duflx_dt, double *duflxc_dt)
+// what a packed call could not report per chunk is checked per call, before it joins one: null arrays (the packing would read them), nlay
+bool packable(const CallDesc &d, const GcmIn &g, const FluxOut &out, bool need_cloud)
 {
-    CallReq me;
-    me.c = QueuedChunk{ncol, icld,
-                       {play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis,
-                        cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer},
-                       {uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt}};
-    me.nlay = nlay; me.icld = *icld; me.idrv = idrv; me.inflg = inflglw; me.iceflg = iceflglw; me.liqflg = liqflglw;
-    // what a packed call could not report per chunk is checked here, per call: null arrays (the packing would read them)
-    const int icld_eff = (me.icld < 0 || me.icld > 3) ? 2 : me.icld;
-    bool bad = !uflx || !dflx || !hr || !uflxc || !dflxc || !hrc || (idrv == 1 && (!duflx_dt || !duflxc_dt)) || nlay < 1 || nlay > 603;
-    for (int k = 0; k < 23; k++) {
-        const bool cloud_arr = k >= 16 && k <= 21;
-        if (!me.c.in[k] && !(cloud_arr && icld_eff == 0)) bad = true;
-    }
-    if (bad) {          // let the plain entry say what is wrong
+    if (!have_outs(out) || (d.idrv == 1 && (!out.duflx_dt || !out.duflxc_dt)) || d.nlay < 1 || d.nlay > 603) return false;
+    const double *in[NA_IN];
+    gcm_pointers(g, nullptr, in);
+    for (int a = 0; a < NA_GCM; a++) if (!in[a] && (need_cloud || !CALL_ARRAYS[a].cloud)) return false;
+    return true;
+}
+
+int nomcica_combined(const CallDesc &d, const GcmIn &g, const FluxOut &out)
+{
+    const int icld_eff = (*d.icld < 0 || *d.icld > 3) ? 2 : *d.icld;
+    if (!packable(d, g, out, icld_eff != 0)) {          // let the plain entry say what is wrong
         ENTRY_LOCK;
-        return nomcica_host(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis,
-                            inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt);
+        return nomcica_host(d, g, out);
     }
+    CallReq me;
+    me.c = QueuedChunk{d, g, nullptr, out};
+    me.icld = *d.icld;
     return comb_call(me);
 }
 }   // namespace
@@ -3320,62 +3291,37 @@ extern "C" {
 // ---------------------------------------------------------------------------------------------------
 // McICA flavour
 // ---------------------------------------------------------------------------------------------------
-#define GCM_PARAMS                                                                                              \
-    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,         \
-    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr, \
-    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,               \
-    const double *ccl4vmr, const double *emis
-#define OUT_PARAMS                                                                                              \
-    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc, double *duflx_dt, double *duflxc_dt
-
 #define MCICA_PARAMS                                                                                            \
     int ncol, int nlay, int *icld, int idrv, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw,               \
     const double *cldfmcl, const double *taucmcl, const double *ciwpmcl, const double *clwpmcl,                 \
     const double *reicmcl, const double *relqmcl, const double *tauaer, OUT_PARAMS
-#define MCICA_ARGS                                                                                              \
-    ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, \
-    cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfmcl, taucmcl, ciwpmcl, clwpmcl, reicmcl, \
-    relqmcl, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt
 
-static int mcica_device(MCICA_PARAMS, const SpecOut *sp, void *stream)
+static int mcica_device(const CallDesc &d, const GcmIn &g, const McIn &m, const FluxOut &out, void *stream)
 {
-    ENTRY_LOCK_FOR(play);
+    ENTRY_LOCK_FOR(g.play);
     if (int rc = check_mcica_build()) return rc;
-    if (int rc = check_common(ncol, nlay)) return rc;
-    if (sp) if (int rc = check_spec(*sp)) return rc;
-    if (!icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
-    if (*icld < 0 || *icld > 3) *icld = 2;                       // src/rrtmg_lw_rad.f90:469
-    if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
-    const int mode = *icld == 0 ? 0 : 3;                         // inatm leaves the cloud arrays zero when icld = 0 (:899-911)
-    const int nbmax = balanced_batch(ncol, eff_batch(nlay));
-    if (int rc = ensure_workspace(nlay, nbmax, mode != 0, mode == 3, idrv, mode)) return rc;
-    GcmIn g{play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr,
-            ccl4vmr, emis, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tauaer};
-    McIn m{cldfmcl, taucmcl, ciwpmcl, clwpmcl, reicmcl, relqmcl};
-    FluxOut out{uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt, nullptr, nullptr};
-    put_spec(out, sp);
-    return run_pipelined((hipStream_t)stream, ncol, nlay, mode, idrv, g, inflglw, iceflglw, liqflglw, out, &m);
+    if (int rc = check_call(d, out)) return rc;
+    const int mode = *d.icld == 0 ? 0 : 3;                       // inatm leaves the cloud arrays zero when icld = 0 (:899-911)
+    const int nbmax = balanced_batch(d.ncol, eff_batch(d.nlay));
+    if (int rc = ensure_workspace(d.nlay, nbmax, mode != 0, mode == 3, d.idrv, mode)) return rc;
+    return run_pipelined((hipStream_t)stream, d.ncol, d.nlay, mode, d.idrv, g, d.inflg, d.iceflg, d.liqflg, out, &m);
 }
 int rrtmg_lw_hip_run_mcica_device(MCICA_PARAMS, void *stream)
 {
-    return mcica_device(MCICA_ARGS, nullptr, stream);
+    return mcica_device({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw}, {GCM_NAMES, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tauaer}, {cldfmcl, taucmcl, ciwpmcl, clwpmcl, reicmcl, relqmcl}, {OUT_NAMES}, stream);
 }
 int rrtmg_lw_hip_run_mcica_spectral_device(MCICA_PARAMS, SPEC_PARAMS, void *stream)
 {
-    const SpecOut sp{uflxs, dflxs, uflxcs, dflxcs};
-    return mcica_device(MCICA_ARGS, &sp, stream);
+    return mcica_device(spectral({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw}), {GCM_NAMES, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tauaer}, {cldfmcl, taucmcl, ciwpmcl, clwpmcl, reicmcl, relqmcl}, {OUT_NAMES, SPEC_NAMES}, stream);
 }
 
-static int mcica_host(MCICA_PARAMS, const SpecOut *sp)
+static int mcica_host(const CallDesc &d, const GcmIn &g, const McIn &m, const FluxOut &out)
 {
     ENTRY_LOCK;
     if (int rc = check_mcica_build()) return rc;
-    if (int rc = check_common(ncol, nlay)) return rc;
-    if (sp) if (int rc = check_spec(*sp)) return rc;
-    if (!icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
-    if (*icld < 0 || *icld > 3) *icld = 2;
-    if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
-    const int mode = *icld == 0 ? 0 : 3;
+    if (int rc = check_call(d, out)) return rc;
+    const int ncol = d.ncol, nlay = d.nlay, idrv = d.idrv;
+    const int mode = *d.icld == 0 ? 0 : 3;
     const bool cloud = mode == 3;
     return fan_out(ncol, [&](int c0, int c1) -> int {     // (one block of columns per device of rrtmg_lw_hip_init_devices)
     if (int rc = check_common(ncol, nlay)) return rc;
@@ -3385,34 +3331,22 @@ static int mcica_host(MCICA_PARAMS, const SpecOut *sp)
     const int nbmax = balanced_batch(c1 - c0, std::min(std::min(eff_batch(nlay), HOST_BATCH), cloud ? mcmax : HOST_BATCH));
     if (int rc = ensure_workspace(nlay, nbmax, cloud, cloud, idrv, mode)) return rc;
     const size_t L = (size_t)nlay;
-    std::vector<HostIn> ins = {
-        {play, 1, L, 0}, {plev, 1, L + 1, 0}, {tlay, 1, L, 0}, {tlev, 1, L + 1, 0}, {tsfc, 1, 1, 0},
-        {h2ovmr, 1, L, 0}, {o3vmr, 1, L, 0}, {co2vmr, 1, L, 0}, {ch4vmr, 1, L, 0}, {n2ovmr, 1, L, 0}, {o2vmr, 1, L, 0},
-        {cfc11vmr, 1, L, 0}, {cfc12vmr, 1, L, 0}, {cfc22vmr, 1, L, 0}, {ccl4vmr, 1, L, 0}, {emis, 1, 16, 0}, {tauaer, 1, 16 * L, 0},
-        {cloud ? cldfmcl : nullptr, NGPT, L, 0}, {cloud ? taucmcl : nullptr, NGPT, L, 0}, {cloud ? ciwpmcl : nullptr, NGPT, L, 0},
-        {cloud ? clwpmcl : nullptr, NGPT, L, 0}, {cloud ? reicmcl : nullptr, 1, L, 0}, {cloud ? relqmcl : nullptr, 1, L, 0}};
-    for (size_t k = 0; k < 17; k++) if (!ins[k].h) return fail(RRTMG_LW_HIP_EARG, "null input array (argument %d)", (int)k);
-    if (cloud) for (size_t k = 17; k < ins.size(); k++) if (!ins[k].h) return fail(RRTMG_LW_HIP_EARG, "null McICA cloud array");
-    std::vector<HostOut> outs = {{uflx, L + 1, 0, true}, {dflx, L + 1, 0, true}, {hr, L, 0, true}, {uflxc, L + 1, 0, true},
-                                 {dflxc, L + 1, 0, true}, {hrc, L, 0, true}, {duflx_dt, L + 1, 0, idrv == 1}, {duflxc_dt, L + 1, 0, idrv == 1}};
-    add_spec_outs(outs, sp, L);
+    std::vector<HostIn> ins;
+    if (int rc = host_ins(ins, g, &m, L, cloud, NGPT)) return rc;
+    std::vector<HostOut> outs = host_outs(out, L, idrv);
     auto body = [&](hipStream_t s, int nb, int, std::vector<HostIn> &in, std::vector<HostOut> &out_) -> int {
-        GcmIn g{in[0].d, in[1].d, in[2].d, in[3].d, in[4].d, in[5].d, in[6].d, in[7].d, in[8].d, in[9].d, in[10].d,
-                in[11].d, in[12].d, in[13].d, in[14].d, in[15].d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, in[16].d};
-        McIn m{in[17].d, in[18].d, in[19].d, in[20].d, in[21].d, in[22].d};
-        ColIn c{};
-        FluxOut out{out_[0].d, out_[1].d, out_[2].d, out_[3].d, out_[4].d, out_[5].d, out_[6].d, out_[7].d, nullptr, nullptr};
-        put_spec_staged(out, out_);
-        return run_batch<true>(s, nb, 0, nb, nlay, mode, idrv, 1, 16, g, c, inflglw, iceflglw, liqflglw, out, &m);
+        GcmIn gd = staged_gcm(in);          // (the sub-column arrays stand in the cloud arrays' places)
+        const McIn md{gd.cldfr, gd.taucld, gd.cicewp, gd.cliqwp, gd.reice, gd.reliq};
+        gd.cldfr = gd.taucld = gd.cicewp = gd.cliqwp = gd.reice = gd.reliq = nullptr;
+        return run_batch<true>(s, nb, 0, nb, nlay, mode, idrv, 1, 16, gd, ColIn{}, d.inflg, d.iceflg, d.liqflg, staged_flux(out_), &md);
     };
     // layers whose sub-column cloud fractions are all below cldmin for the batch: cldprmc reads nothing else of them (src/rrtmg_lw_cldprmc.f90:182-183)
     std::vector<unsigned char> cloudfree(L, 0), cf_uni(L, 0);
     std::vector<uint64_t> cf_bits(L, 0);
     auto prep = [&](int, int col0, int nb, hipStream_t) -> int {
         if (!cloud) return 0;
-        rows_below(cldfmcl, NGPT, L, (size_t)ncol, (size_t)col0, (size_t)nb, 1.e-20, cloudfree.data(), cf_uni.data(), cf_bits.data());
-        ins[17].known = cf_uni.data(); ins[17].known_bits = cf_bits.data();        // (the cloud-free layers of cldfmcl have just been read to their end)
-        for (size_t a = 18; a < ins.size(); a++) ins[a].skip = cloudfree.data();
+        rows_below(m.cldfmcl, NGPT, L, (size_t)ncol, (size_t)col0, (size_t)nb, 1.e-20, cloudfree.data(), cf_uni.data(), cf_bits.data());
+        skip_cloudfree(ins, cloudfree.data(), cf_uni.data(), cf_bits.data());
         return 0;
     };
     if (int rc = host_pipeline(ncol, c0, c1, nbmax, ins, outs, body, prep)) return rc;
@@ -3422,12 +3356,11 @@ static int mcica_host(MCICA_PARAMS, const SpecOut *sp)
 }
 int rrtmg_lw_hip_run_mcica(MCICA_PARAMS)
 {
-    return mcica_host(MCICA_ARGS, nullptr);
+    return mcica_host({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw}, {GCM_NAMES, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tauaer}, {cldfmcl, taucmcl, ciwpmcl, clwpmcl, reicmcl, relqmcl}, {OUT_NAMES});
 }
 int rrtmg_lw_hip_run_mcica_spectral(MCICA_PARAMS, SPEC_PARAMS)
 {
-    const SpecOut sp{uflxs, dflxs, uflxcs, dflxcs};
-    return mcica_host(MCICA_ARGS, &sp);
+    return mcica_host(spectral({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw}), {GCM_NAMES, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tauaer}, {cldfmcl, taucmcl, ciwpmcl, clwpmcl, reicmcl, relqmcl}, {OUT_NAMES, SPEC_NAMES});
 }
 
 int rrtmg_lw_hip_get_alpha(int ncol, int nlay, int icld, int idcor, double decorr_con, const double *dz, const double *lat,
@@ -3545,57 +3478,45 @@ int rrtmg_lw_hip_mcica_subcol(
 // sub-column arrays (they are implied by the mask and the grid-mean cloud properties).  DEVICE pointers.
 #define SUBCOL_PARAMS                                                                                                       \
     int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw, \
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp, const double *reice,             \
-    const double *reliq, const double *alpha, const double *tauaer, OUT_PARAMS
-#define SUBCOL_ARGS                                                                                                         \
-    ncol, nlay, icld, idrv, permuteseed, irng, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr,    \
-    cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq,  \
-    alpha, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt
-static int mcica_subcol_device(SUBCOL_PARAMS, const SpecOut *sp, void *stream)
+    CLOUD_PARAMS, const double *alpha, const double *tauaer, OUT_PARAMS
+static int mcica_subcol_device(const CallDesc &d, const GcmIn &g, const double *alpha, const FluxOut &out, void *stream)
 {
-    ENTRY_LOCK_FOR(play, irng && *irng != 0);
+    ENTRY_LOCK_FOR(g.play, d.irng && *d.irng != 0);
     if (int rc = check_mcica_build()) return rc;
-    if (sp) if (int rc = check_spec(*sp)) return rc;
-    if (!icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
-    if (int rc = check_subcol_args(ncol, nlay, *icld, irng)) return rc;
-    if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
-    const int icld_gen = *icld;
-    if (*icld > 3) *icld = 2;                                     // what rrtmg_lw does to the generator's icld (src/rrtmg_lw_rad.f90:469)
+    if (d.spectral) if (int rc = check_spec(out)) return rc;
+    if (!d.icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
+    if (int rc = check_subcol_args(d.ncol, d.nlay, *d.icld, d.irng)) return rc;
+    if (d.idrv == 1 && (!out.duflx_dt || !out.duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
+    const int icld_gen = *d.icld;
+    if (*d.icld > 3) *d.icld = 2;                                 // what rrtmg_lw does to the generator's icld (src/rrtmg_lw_rad.f90:469)
     const int mode = icld_gen == 0 ? 0 : 3;
     hipStream_t s = (hipStream_t)stream;
-    const int nbmax = balanced_batch(ncol, eff_batch(nlay));
-    if (int rc = ensure_workspace(nlay, nbmax, mode != 0, false, idrv, mode)) return rc;      // mask path: no per-g-point cloud arrays
-    KissGen gen{false, icld_gen, permuteseed, alpha};
+    const int nbmax = balanced_batch(d.ncol, eff_batch(d.nlay));
+    if (int rc = ensure_workspace(d.nlay, nbmax, mode != 0, false, d.idrv, mode)) return rc;      // mask path: no per-g-point cloud arrays
+    KissGen gen{false, icld_gen, d.permuteseed, alpha};
     if (mode == 3) {
-        if (*irng == 0) {          // kissvec: every column owns its stream -> generated batch by batch on the auxiliary stream
-            if (int rc = prepare_mask(ncol, nlay, icld_gen, 0, alpha)) return rc;
+        if (*d.irng == 0) {          // kissvec: every column owns its stream -> generated batch by batch on the auxiliary stream
+            if (int rc = prepare_mask(d.ncol, d.nlay, icld_gen, 0, alpha)) return rc;
             gen.on = true;
-        } else if (int rc = generate_mask(s, ncol, nlay, icld_gen, permuteseed, *irng, play, cldfr, alpha)) return rc;
+        } else if (int rc = generate_mask(s, d.ncol, d.nlay, icld_gen, d.permuteseed, *d.irng, g.play, g.cldfr, alpha)) return rc;
     }
-    GcmIn g{play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr,
-            ccl4vmr, emis, cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer};
-    FluxOut out{uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt, nullptr, nullptr};
-    put_spec(out, sp);
-    return run_pipelined(s, ncol, nlay, mode, idrv, g, inflglw, iceflglw, liqflglw, out, nullptr, gen);
+    return run_pipelined(s, d.ncol, d.nlay, mode, d.idrv, g, d.inflg, d.iceflg, d.liqflg, out, nullptr, gen);
 }
 int rrtmg_lw_hip_run_mcica_subcol_device(SUBCOL_PARAMS, void *stream)
 {
-    return mcica_subcol_device(SUBCOL_ARGS, nullptr, stream);
+    return mcica_subcol_device({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng}, {GCM_NAMES, CLOUD_NAMES, tauaer}, alpha, {OUT_NAMES}, stream);
 }
 int rrtmg_lw_hip_run_mcica_subcol_spectral_device(SUBCOL_PARAMS, SPEC_PARAMS, void *stream)
 {
-    const SpecOut sp{uflxs, dflxs, uflxcs, dflxcs};
-    return mcica_subcol_device(SUBCOL_ARGS, &sp, stream);
+    return mcica_subcol_device(spectral({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng}), {GCM_NAMES, CLOUD_NAMES, tauaer}, alpha, {OUT_NAMES, SPEC_NAMES}, stream);
 }
 
 // columns [c0, c1) of the fused generator + solver call on the calling thread's current device state (kissvec seeds its stream per
 // column, src/mcica_subcol_gen_lw.f90:463-474: a block of columns is generated and solved on its own; the Mersenne-Twister stream is one
 // sequence over all columns of a call, :497-503, and is drawn with c0 = 0, c1 = ncol only)
-static int mcica_subcol_host_range(
-    int ncol, int c0, int c1, int nlay, int icld_gen, int idrv, int permuteseed, int irng, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw,
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp, const double *reice,
-    const double *reliq, const double *alpha, const double *tauaer, OUT_PARAMS, const SpecOut *sp)
+static int mcica_subcol_host_range(const CallDesc &d, int icld_gen, int irng, int c0, int c1, const GcmIn &g, const double *alpha, const FluxOut &out)
 {
+    const int ncol = d.ncol, nlay = d.nlay, idrv = d.idrv;
     if (int rc = check_common(ncol, nlay)) return rc;
     HIP_TRY(hipDeviceSynchronize());      // asynchronous device-entry work of earlier calls shares the workspace
     const int mode = icld_gen == 0 ? 0 : 3;
@@ -3608,38 +3529,25 @@ static int mcica_subcol_host_range(
     // 1. masks of the block's columns: needs play, cldfr, alpha of every one of them
     double *d_gen = nullptr;
     if (cloud) {
-        if (!play || !cldfr || (two && !alpha)) return fail(RRTMG_LW_HIP_EARG, "null generator input");
+        if (!g.play || !g.cldfr || (two && !alpha)) return fail(RRTMG_LW_HIP_EARG, "null generator input");
         HIP_TRY(hipMalloc((void **)&d_gen, nl * L * 8 * 3));
         // (through the library's own pinned buffer: see bounce_h2d)
-        int rc = bounce_h2d_rows(d_gen, play + c0, nl * 8, n * 8, L);
-        if (rc == 0) rc = bounce_h2d_rows(d_gen + nl * L, cldfr + c0, nl * 8, n * 8, L);
+        int rc = bounce_h2d_rows(d_gen, g.play + c0, nl * 8, n * 8, L);
+        if (rc == 0) rc = bounce_h2d_rows(d_gen + nl * L, g.cldfr + c0, nl * 8, n * 8, L);
         if (rc == 0 && two) rc = bounce_h2d_rows(d_gen + 2 * nl * L, alpha + c0, nl * 8, n * 8, L);
-        if (rc == 0) rc = generate_mask(s, nloc, nlay, icld_gen, permuteseed, irng, d_gen, d_gen + nl * L, two ? d_gen + 2 * nl * L : nullptr);
+        if (rc == 0) rc = generate_mask(s, nloc, nlay, icld_gen, d.permuteseed, irng, d_gen, d_gen + nl * L, two ? d_gen + 2 * nl * L : nullptr);
         if (rc == 0 && hipStreamSynchronize(s) != hipSuccess) rc = fail(RRTMG_LW_HIP_EHIP, "generator failed");
         (void)hipFree(d_gen);
         if (rc) return rc;
     }
     // 2. column batches
-    std::vector<HostIn> ins = {
-        {play, 1, L, 0}, {plev, 1, L + 1, 0}, {tlay, 1, L, 0}, {tlev, 1, L + 1, 0}, {tsfc, 1, 1, 0},
-        {h2ovmr, 1, L, 0}, {o3vmr, 1, L, 0}, {co2vmr, 1, L, 0}, {ch4vmr, 1, L, 0}, {n2ovmr, 1, L, 0}, {o2vmr, 1, L, 0},
-        {cfc11vmr, 1, L, 0}, {cfc12vmr, 1, L, 0}, {cfc22vmr, 1, L, 0}, {ccl4vmr, 1, L, 0}, {emis, 1, 16, 0}, {tauaer, 1, 16 * L, 0},
-        {cloud ? cldfr : nullptr, 1, L, 0}, {cloud ? taucld : nullptr, NBND, L, 0}, {cloud ? cicewp : nullptr, 1, L, 0},
-        {cloud ? cliqwp : nullptr, 1, L, 0}, {cloud ? reice : nullptr, 1, L, 0}, {cloud ? reliq : nullptr, 1, L, 0}};
-    for (size_t k = 0; k < 17; k++) if (!ins[k].h) return fail(RRTMG_LW_HIP_EARG, "null input array (argument %d)", (int)k);
-    if (cloud) for (size_t k = 17; k < ins.size(); k++) if (!ins[k].h) return fail(RRTMG_LW_HIP_EARG, "null cloud array");
-    std::vector<HostOut> outs = {{uflx, L + 1, 0, true}, {dflx, L + 1, 0, true}, {hr, L, 0, true}, {uflxc, L + 1, 0, true},
-                                 {dflxc, L + 1, 0, true}, {hrc, L, 0, true}, {duflx_dt, L + 1, 0, idrv == 1}, {duflxc_dt, L + 1, 0, idrv == 1}};
-    for (size_t k = 0; k < 6; k++) if (!outs[k].h) return fail(RRTMG_LW_HIP_EARG, "null output array");
-    add_spec_outs(outs, sp, L);
+    std::vector<HostIn> ins;
+    if (int rc = host_ins(ins, g, nullptr, L, cloud, NBND)) return rc;
+    if (!have_outs(out)) return fail(RRTMG_LW_HIP_EARG, "null output array");
+    std::vector<HostOut> outs = host_outs(out, L, idrv);
     auto body = [&](hipStream_t bs, int nb, int col0, std::vector<HostIn> &in, std::vector<HostOut> &out_) -> int {
-        GcmIn g{in[0].d, in[1].d, in[2].d, in[3].d, in[4].d, in[5].d, in[6].d, in[7].d, in[8].d, in[9].d, in[10].d,
-                in[11].d, in[12].d, in[13].d, in[14].d, in[15].d, in[17].d, in[18].d, in[19].d, in[20].d, in[21].d, in[22].d, in[16].d};
-        ColIn c{};
-        FluxOut out{out_[0].d, out_[1].d, out_[2].d, out_[3].d, out_[4].d, out_[5].d, out_[6].d, out_[7].d, nullptr, nullptr};
-        put_spec_staged(out, out_);
         G.W.mask_col0 = (size_t)(col0 - c0);                      // staged arrays start at column 0, the mask holds the block's columns
-        return run_batch<true>(bs, nb, 0, nb, nlay, mode, idrv, 1, 16, g, c, inflglw, iceflglw, liqflglw, out, nullptr);
+        return run_batch<true>(bs, nb, 0, nb, nlay, mode, idrv, 1, 16, staged_gcm(in), ColIn{}, d.inflg, d.iceflg, d.liqflg, staged_flux(out_), nullptr);
     };
     {
         const int rc = host_pipeline(ncol, c0, c1, nbmax, ins, outs, body);
@@ -3651,62 +3559,47 @@ static int mcica_subcol_host_range(
 
 }   // extern "C"
 // the fused entry behind the lock (the caller holds it): argument checks, the columns over the devices
-static int mcica_subcol_host(int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw,
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp, const double *reice,
-    const double *reliq, const double *alpha, const double *tauaer, OUT_PARAMS, const SpecOut *sp)
+static int mcica_subcol_host(const CallDesc &d, const GcmIn &g, const double *alpha, const FluxOut &out)
 {
     if (int rc = check_mcica_build()) return rc;
-    if (sp) if (int rc = check_spec(*sp)) return rc;
-    if (!icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
-    if (int rc = check_subcol_args(ncol, nlay, *icld, irng)) return rc;
-    if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
-    const int icld_gen = *icld, rng = *irng;
-    if (*icld > 3) *icld = 2;
-    auto range = [&](int c0, int c1) -> int {
-        return mcica_subcol_host_range(ncol, c0, c1, nlay, icld_gen, idrv, permuteseed, rng, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr,
-                                       n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp,
-                                       reice, reliq, alpha, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt, sp);
-    };
+    if (d.spectral) if (int rc = check_spec(out)) return rc;
+    if (!d.icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
+    if (int rc = check_subcol_args(d.ncol, d.nlay, *d.icld, d.irng)) return rc;
+    if (d.idrv == 1 && (!out.duflx_dt || !out.duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
+    const int icld_gen = *d.icld, rng = *d.irng;
+    if (*d.icld > 3) *d.icld = 2;
+    auto range = [&](int c0, int c1) -> int { return mcica_subcol_host_range(d, icld_gen, rng, c0, c1, g, alpha, out); };
     // the Mersenne-Twister stream (irng = 1) is ONE sequence over the (sub-column, column, layer) draws of the call
     // (src/mcica_subcol_gen_lw.f90:497-503): a column's deviates depend on every column before it, so the call stays on the first device
-    if (rng != 0 && icld_gen != 0) return range(0, ncol);
-    return fan_out(ncol, range);
+    if (rng != 0 && icld_gen != 0) return range(0, d.ncol);
+    return fan_out(d.ncol, range);
 }
 extern "C" {
-int rrtmg_lw_hip_run_mcica_subcol(
-    int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw,
-    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp, const double *reice,
-    const double *reliq, const double *alpha, const double *tauaer, OUT_PARAMS)
+int rrtmg_lw_hip_run_mcica_subcol(SUBCOL_PARAMS)
 {
+    const CallDesc d{ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng};
+    const GcmIn g{GCM_NAMES, CLOUD_NAMES, tauaer};
+    const FluxOut out{OUT_NAMES};
     // a small call with the kissvec generator (every column draws from its own stream: src/mcica_subcol_gen_lw.f90:463-474) that finds
     // another in flight is solved together with it in one pass, like the non-McICA entry (comb_call); the Mersenne Twister - one stream
     // over the columns of a call - and calls that are wrong on their face take the lock and say so themselves
-    const bool plain = ncol >= 1 && ncol <= comb_max() && comb_enabled() && icld && irng && *irng == 0 && *icld >= 0 && *icld <= 5 && nlay >= 1 && nlay <= 603 &&
-                       uflx && dflx && hr && uflxc && dflxc && hrc && (idrv != 1 || (duflx_dt && duflxc_dt)) &&
-                       play && plev && tlay && tlev && tsfc && h2ovmr && o3vmr && co2vmr && ch4vmr && n2ovmr && o2vmr && cfc11vmr && cfc12vmr && cfc22vmr && ccl4vmr &&
-                       emis && cldfr && taucld && cicewp && cliqwp && reice && reliq && tauaer;
+    const bool plain = ncol >= 1 && ncol <= comb_max() && comb_enabled() && icld && irng && *irng == 0 && *icld >= 0 && *icld <= 5 && packable(d, g, out, true);
     if (plain) {
         CallReq me;
-        me.c = QueuedChunk{ncol, icld,
-                           {play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis,
-                            cldfr, taucld, cicewp, cliqwp, reice, reliq, tauaer, alpha},
-                           {uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt}};
-        me.nlay = nlay; me.icld = *icld; me.idrv = idrv; me.inflg = inflglw; me.iceflg = iceflglw; me.liqflg = liqflglw;
-        me.kind = 1; me.permuteseed = permuteseed;
+        me.c = QueuedChunk{d, g, alpha, out};
+        me.icld = *icld;
+        me.kind = 1;
         return comb_call(me);
     }
     ENTRY_LOCK;
-    return mcica_subcol_host(ncol, nlay, icld, idrv, permuteseed, irng, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr,
-                             cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, alpha, tauaer,
-                             uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt);
+    return mcica_subcol_host(d, g, alpha, out);
 }
 
 // the same with spectral outputs: does not join the combining entry (the entry lock, like any other call)
 int rrtmg_lw_hip_run_mcica_subcol_spectral(SUBCOL_PARAMS, SPEC_PARAMS)
 {
     ENTRY_LOCK;
-    const SpecOut sp{uflxs, dflxs, uflxcs, dflxcs};
-    return mcica_subcol_host(SUBCOL_ARGS, &sp);
+    return mcica_subcol_host(spectral({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng}), {GCM_NAMES, CLOUD_NAMES, tauaer}, alpha, {OUT_NAMES, SPEC_NAMES});
 }
 
 }  // extern "C"

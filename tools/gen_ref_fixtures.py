@@ -100,7 +100,37 @@ def rrtatm():
     print("wrote RRTATM fixtures to", G)
 
 
+def gasstate():
+    """ref_gasstate_L52.npz: the reference on columns of the designed gas states (tests/gas_states.py) that span its ledger - fluxes and
+    heating rates of the GCM entry, and taug / fracs of the converted columns in two layers each (a whole column of them is as large as
+    the largest fixture)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import gas_states as gs
+    from test_hip_spectral import inatm
+    nlay, seed = 52, 0
+    d = gs.make_gas_states(nlay, seed, "shuffled")
+    cols = gs.span_columns(d)
+    sub = gs.take(d, cols)
+    ref = Reference("nomcica")
+    o = ref.rrtmg_lw(sub["ncol"], nlay, 0, 1, sub)
+    assert all(np.isfinite(o[k]).all() for k in OUT_KEYS)
+    lower = gs.decisions(sub)["lower"]
+    lays, taug, fracs = [], [], []
+    for n, i in enumerate(cols):
+        nlow = int(lower[n].sum())                      # one layer in the middle of each region (of the one region where there is one)
+        pair = [nlow // 2, nlow + (nlay - nlow) // 3] if 0 < nlow < nlay else [nlay // 4, 3 * nlay // 4]
+        c = ref.column(inatm(d, int(i), 0))
+        lays.append(pair)
+        taug.append(c["taug"][pair])
+        fracs.append(c["fracs"][pair])
+    np.savez_compressed(os.path.join(G, f"ref_gasstate_L{nlay}.npz"), nlay=nlay, seed=seed, cols=cols, labels=np.array(sub["labels"]),
+                        lays=np.array(lays), taug=np.array(taug), fracs=np.array(fracs), **{k: o[k] for k in OUT_KEYS})
+    print("wrote the gas-state fixture to", G)
+
+
 def main():
+    if "--gasstate" in sys.argv:    # only the designed gas states' fixture
+        return gasstate()
     if "--rrtatm" in sys.argv:      # only the IATM = 1 layering fixtures
         return rrtatm()
     if "--g256" in sys.argv:        # only the 256-g-point fixtures (the others are left untouched)

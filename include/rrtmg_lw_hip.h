@@ -466,6 +466,68 @@ int rrtmg_lw_hip_gas_optics_columns(int ncol, int nlayers, int idrv,
     const double *pwvcm,
     double *taug, double *fracs, double *planklay, double *planklev, double *plankbnd, double *dplankbnd_dt);
 
+/* ---- Device arrays in the host model's own form --------------------------------------------------------------------------------------
+ * The device-pointer entries above take the reference's array form only: float64, columns fastest, layer 1 at the surface.  A
+ * device-resident caller that holds float32 values, C-order (column, level) storage or a top-down vertical index describes its arrays
+ * once and hands them over as they lie; the library converts them on the device, in one kernel per column batch in front of the solver
+ * and one behind it, and returns the results in the same form.
+ *   real_bytes      8: float64.  4: float32 - EVERY floating-point array of the call, inputs and outputs.  Inputs are widened (exact),
+ *                   outputs are the float64 results rounded to nearest, (float)x.
+ *   layer_fastest   0: each array as the plain entry declares it (taucld (16,ncol,nlay) and tauaer (ncol,nlay,16) included).
+ *                   1: every array in C order with the column index FIRST (slowest) and everything else behind it:
+ *                        play, tlay, the gases, cldfr, cicewp, cliqwp, reice, reliq, alpha, hr, hrc      (ncol, nlay)
+ *                        plev, tlev, uflx, dflx, uflxc, dflxc, duflx_dt, duflxc_dt                       (ncol, nlay+1)
+ *                        emis, plankbnd, dplankbnd_dt                                                    (ncol, 16)
+ *                        taucld, tauaer, planklay                                                        (ncol, nlay, 16)
+ *                        planklev                                                                        (ncol, nlay+1, 16)
+ *                        taug, fracs                                                                     (ncol, nlay, NG), NG = rrtmg_lw_hip_gpoints()
+ *                        tsfc                                                                            (ncol)
+ *   top_first       0: index 0 of the vertical axis at the surface.  1: at the top of the atmosphere - layer k of the reference lies at
+ *                   nlay-1-k, level k at nlay-k; inputs and outputs, in both layouts.
+ * Each entry takes the argument list of the entry it is named after behind `form`, its arrays as const void * / void *: icld and irng
+ * in / out, the flags, the NULL rules of optional outputs (a NULL output is neither formed nor touched), `stream`, no synchronisation,
+ * errors through rrtmg_lw_hip_check(stream) and rrtmg_lw_hip_last_error() with the same texts.  The device is chosen from `play`.
+ * Results: what the plain entry gives on the same values brought into the reference form - float32 inputs widened, float32 outputs
+ * rounded - bit for bit.  The form {8, 0, 0} forwards to the plain entry.  RRTMG_LW_HIP_EARG: a null `form`, real_bytes other than 4 or 8,
+ * a flag other than 0 or 1, a null required array.  The output arrays must not overlap the inputs.
+ * The batch's arrays are staged in device memory the library owns (counted in rrtmg_lw_hip_workspace_bytes; per column of a batch the
+ * float64 reference form of the call's arrays, taucld as one band sum per cell where inflglw >= 1; the fused McICA entry also holds play,
+ * cldfr and alpha of the whole call for its generator).  The batches run one after the other on `stream`; such calls are not replayed as
+ * graphs.  Out of scope: the host-pointer entries (their row scans compare 8-byte patterns; Fortran hosts are column-fastest anyway),
+ * the explicit-sub-column McICA entries, the spectral outputs and the queue. */
+typedef struct {
+    int real_bytes;
+    int layer_fastest;
+    int top_first;
+} rrtmg_lw_hip_array_form;
+
+int rrtmg_lw_hip_run_nomcica_device_as(const rrtmg_lw_hip_array_form *form,
+    int ncol, int nlay, int *icld, int idrv,
+    const void *play, const void *plev, const void *tlay, const void *tlev, const void *tsfc,
+    const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *n2ovmr,
+    const void *o2vmr, const void *cfc11vmr, const void *cfc12vmr, const void *cfc22vmr,
+    const void *ccl4vmr, const void *emis, int inflglw, int iceflglw, int liqflglw,
+    const void *cldfr, const void *taucld, const void *cicewp, const void *cliqwp,
+    const void *reice, const void *reliq, const void *tauaer,
+    void *uflx, void *dflx, void *hr, void *uflxc, void *dflxc, void *hrc,
+    void *duflx_dt, void *duflxc_dt, void *stream);
+int rrtmg_lw_hip_run_mcica_subcol_device_as(const rrtmg_lw_hip_array_form *form,
+    int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng,
+    const void *play, const void *plev, const void *tlay, const void *tlev, const void *tsfc,
+    const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *n2ovmr,
+    const void *o2vmr, const void *cfc11vmr, const void *cfc12vmr, const void *cfc22vmr,
+    const void *ccl4vmr, const void *emis, int inflglw, int iceflglw, int liqflglw,
+    const void *cldfr, const void *taucld, const void *cicewp, const void *cliqwp,
+    const void *reice, const void *reliq, const void *alpha, const void *tauaer,
+    void *uflx, void *dflx, void *hr, void *uflxc, void *dflxc, void *hrc,
+    void *duflx_dt, void *duflxc_dt, void *stream);
+int rrtmg_lw_hip_gas_optics_device_as(const rrtmg_lw_hip_array_form *form, int ncol, int nlay, int idrv,
+    const void *play, const void *plev, const void *tlay, const void *tlev, const void *tsfc,
+    const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *n2ovmr,
+    const void *o2vmr, const void *cfc11vmr, const void *cfc12vmr, const void *cfc22vmr,
+    const void *ccl4vmr, const void *emis,
+    void *taug, void *fracs, void *planklay, void *planklev, void *plankbnd, void *dplankbnd_dt, void *stream);
+
 /* PMC calibration: one kernel that reads `bytes` and writes `bytes` with 16 B per lane (known HBM traffic), so that a
  * rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE pass can fix the counters' unit and scale in the same session. */
 int rrtmg_lw_hip_calibrate_stream(long long bytes);

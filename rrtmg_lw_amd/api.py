@@ -308,6 +308,7 @@ def rrtmg_lw(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr
 _GCM_ORDER = ("play", "plev", "tlay", "tlev", "tsfc", "h2ovmr", "o3vmr", "co2vmr", "ch4vmr", "n2ovmr", "o2vmr",
               "cfc11vmr", "cfc12vmr", "cfc22vmr", "ccl4vmr", "emis")
 _CLD_ORDER = ("cldfr", "taucld", "cicewp", "cliqwp", "reice", "reliq", "tauaer")
+_FLUX_OUT = ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc", "duflx_dt", "duflxc_dt")
 
 
 def rrtmg_lw_from_dict(d, icld=None, idrv=None, out=None, spectral=False):
@@ -318,17 +319,43 @@ def rrtmg_lw_from_dict(d, icld=None, idrv=None, out=None, spectral=False):
                     d["liqflglw"], *[d[k] for k in _CLD_ORDER], out=out, spectral=spectral)
 
 
-def rrtmg_lw_device(d, out, icld=None, idrv=None, stream=None):
+class _ArrayFormC(C.Structure):
+    """rrtmg_lw_hip_array_form"""
+    _fields_ = [("real_bytes", C.c_int), ("layer_fastest", C.c_int), ("top_first", C.c_int)]
+
+
+def _form_arg(form, d, out, in_names, out_names):
+    """The `form` argument of a *_as entry (rrtmg_lw_amd.arrays.ArrayForm), after checking every tensor the call hands over against it:
+    dtype (TypeError), number of elements and dense storage (ValueError)."""
+    from . import arrays
+    form = arrays.ArrayForm(*form)
+    if form.real_bytes not in (4, 8) or form.layer_fastest not in (0, 1) or form.top_first not in (0, 1):
+        raise ValueError(f"bad array form {tuple(form)}")
+    ncol, nlay = int(d["ncol"]), int(d["nlay"])
+    for src, names in ((d, in_names), (out, out_names)):
+        for k in names:
+            if src.get(k) is not None:
+                arrays.check_tensor(k, src[k], ncol, nlay, form, gpoints())
+    return C.byref(_ArrayFormC(*form))
+
+
+def rrtmg_lw_device(d, out, icld=None, idrv=None, stream=None, form=None):
     """Device-resident call: `d` holds torch CUDA tensors laid out column-fastest (synth.make_gcm_inputs(backend="torch")),
     `out` a dict of preallocated output tensors (uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt).
     Enqueues on `stream` (an integer hipStream_t handle, e.g. torch.cuda.current_stream().cuda_stream) and returns
     immediately; call check(stream) to synchronise and collect physics errors.  When `out` holds uflxs (and dflxs, optionally
-    uflxcs / dflxcs: (ncol, nlay+1, 16) laid out column-fastest, band last) the spectral entry fills them as well."""
+    uflxcs / dflxcs: (ncol, nlay+1, 16) laid out column-fastest, band last) the spectral entry fills them as well.
+    form: an rrtmg_lw_amd.arrays.ArrayForm - the tensors of `d` and `out` then lie in that form (float32, (ncol, nlay) C order, top
+    first: see arrays.py) and rrtmg_lw_hip_run_nomcica_device_as takes them as they are; no spectral outputs."""
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     icld_c = C.c_int(int(icld))
     ptr = lambda t: C.c_void_p(t.data_ptr())
     args = [C.c_int(d["ncol"]), C.c_int(d["nlay"]), C.byref(icld_c), C.c_int(int(idrv))]
+    if form is not None:
+        if "uflxs" in out:
+            raise ValueError("the spectral outputs are not available with an array form")
+        args.insert(0, _form_arg(form, d, out, _GCM_ORDER + _CLD_ORDER, _FLUX_OUT))
     args += [ptr(d[k]) for k in _GCM_ORDER]
     args += [C.c_int(int(d["inflglw"])), C.c_int(int(d["iceflglw"])), C.c_int(int(d["liqflglw"]))]
     args += [ptr(d[k]) for k in _CLD_ORDER]
@@ -338,6 +365,9 @@ def rrtmg_lw_device(d, out, icld=None, idrv=None, stream=None):
         _check(lib().rrtmg_lw_hip_run_nomcica_spectral_device(*args, *_spec_dev(out), C.c_void_p(stream or 0)))
         return icld_c.value
     args.append(C.c_void_p(stream or 0))
+    if form is not None:
+        _check(lib().rrtmg_lw_hip_run_nomcica_device_as(*args))
+        return icld_c.value
     _check(lib().rrtmg_lw_hip_run_nomcica_device(*args))
     return icld_c.value
 
@@ -445,15 +475,19 @@ def gas_optics(d, idrv=0, out=None):
     return out
 
 
-def gas_optics_device(d, out, stream=None, idrv=None):
+def gas_optics_device(d, out, stream=None, idrv=None, form=None):
     """Device-resident gas optics (rrtmg_lw_hip_gas_optics_device): `d` as for rrtmg_lw_device (torch tensors, column fastest), `out` a
     dict of preallocated float64 tensors laid out column fastest, g-point / band last - taug, fracs of shape (ngpt, nlay, ncol), planklay
     (16, nlay, ncol), planklev (16, nlay+1, ncol), plankbnd, dplankbnd_dt (16, ncol); the Planck ones optional.  Enqueues on `stream`
-    and returns; call check(stream) to synchronise.  idrv: d["idrv"] unless given."""
+    and returns; call check(stream) to synchronise.  idrv: d["idrv"] unless given.  form: as for rrtmg_lw_device - with layer_fastest
+    taug and fracs are (ncol, nlay, ngpt) C-contiguous, planklay (ncol, nlay, 16), planklev (ncol, nlay+1, 16), plankbnd (ncol, 16)."""
     idrv = d["idrv"] if idrv is None else idrv
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
     args = [C.c_int(d["ncol"]), C.c_int(d["nlay"]), C.c_int(int(idrv))] + [ptr(d[k]) for k in _GCM_ORDER]
     args += [ptr(out.get(k)) for k in _OPTICS]
+    if form is not None:
+        _check(lib().rrtmg_lw_hip_gas_optics_device_as(_form_arg(form, d, out, _GCM_ORDER, _OPTICS), *args, C.c_void_p(stream or 0)))
+        return
     _check(lib().rrtmg_lw_hip_gas_optics_device(*args, C.c_void_p(stream or 0)))
 
 
@@ -592,13 +626,18 @@ def rrtmg_lw_mcica_subcol_from_dict(d, permuteseed, irng, alpha=None, icld=None,
                                  d["reliq"], alpha, d["tauaer"], spectral=spectral, out=out)
 
 
-def rrtmg_lw_mcica_subcol_device(d, out, permuteseed, irng, alpha=None, icld=None, idrv=None, stream=None):
-    """Device-resident fused generator + solver (torch CUDA tensors, column-fastest); see rrtmg_lw_device."""
+def rrtmg_lw_mcica_subcol_device(d, out, permuteseed, irng, alpha=None, icld=None, idrv=None, stream=None, form=None):
+    """Device-resident fused generator + solver (torch CUDA tensors, column-fastest); see rrtmg_lw_device (`form` as there: `alpha` lies
+    in that form as well)."""
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     icld_c, irng_c = C.c_int(int(icld)), C.c_int(int(irng))
     ptr = lambda t: C.c_void_p(t.data_ptr())
     args = [C.c_int(d["ncol"]), C.c_int(d["nlay"]), C.byref(icld_c), C.c_int(int(idrv)), C.c_int(int(permuteseed)), C.byref(irng_c)]
+    if form is not None:
+        if "uflxs" in out:
+            raise ValueError("the spectral outputs are not available with an array form")
+        args.insert(0, _form_arg(form, dict(d, alpha=alpha), out, _GCM_ORDER + _CLD_ORDER + ("alpha",), _FLUX_OUT))
     args += [ptr(d[k]) for k in _GCM_ORDER]
     args += [C.c_int(int(d["inflglw"])), C.c_int(int(d["iceflglw"])), C.c_int(int(d["liqflglw"]))]
     args += [ptr(d[k]) for k in ("cldfr", "taucld", "cicewp", "cliqwp", "reice", "reliq")]
@@ -609,6 +648,9 @@ def rrtmg_lw_mcica_subcol_device(d, out, permuteseed, irng, alpha=None, icld=Non
         _check(lib().rrtmg_lw_hip_run_mcica_subcol_spectral_device(*args, *_spec_dev(out), C.c_void_p(stream or 0)))
         return icld_c.value
     args.append(C.c_void_p(stream or 0))
+    if form is not None:
+        _check(lib().rrtmg_lw_hip_run_mcica_subcol_device_as(*args))
+        return icld_c.value
     _check(lib().rrtmg_lw_hip_run_mcica_subcol_device(*args))
     return icld_c.value
 

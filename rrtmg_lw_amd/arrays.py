@@ -1,0 +1,189 @@
+"""Array forms of the device entries (include/rrtmg_lw_hip.h, rrtmg_lw_hip_array_form).
+
+The reference form is what rrtmg_lw_amd.synth.make_gcm_inputs produces and the plain device entries take: float64, stored with the
+column index fastest, vertical index 0 at the surface, logical shapes as the Fortran interface declares them:
+
+    play, tlay, the gases, cldfr, cicewp, cliqwp, reice, reliq, alpha, hr, hrc      (ncol, nlay)
+    plev, tlev, uflx, dflx, uflxc, dflxc, duflx_dt, duflxc_dt                       (ncol, nlay+1)
+    emis, plankbnd, dplankbnd_dt                                                    (ncol, 16)
+    taucld                                                                          (16, ncol, nlay)
+    tauaer, planklay                                                                (ncol, nlay, 16)
+    planklev                                                                        (ncol, nlay+1, 16)
+    taug, fracs                                                                     (ncol, nlay, NG)
+    tsfc                                                                            (ncol,)
+
+An ArrayForm(real_bytes, layer_fastest, top_first) describes what a device-resident caller holds instead:
+
+    real_bytes      8 = float64, 4 = float32, for every floating-point array of a call
+    layer_fastest   0: the logical shapes and the column-fastest storage above.
+                    1: every array C-contiguous with the column index first; the shapes above as they stand, except taucld, which
+                       becomes (ncol, nlay, 16).  Element (i, k) of a (ncol, nlay) array lies at i * nlay + k, element (i, k, b) of
+                       taucld or tauaer at (i * nlay + k) * 16 + b.
+    top_first       1: the vertical index runs from the top of the atmosphere: layer k of the reference lies at nlay-1-k, level k at
+                       nlay-k (both layouts; inputs and outputs).
+
+from_reference / to_reference convert a dict of call arrays (numpy arrays or torch tensors; other entries - ncol, nlay, the flags -
+pass through) between the two.  A float32 form rounds on the way out of the reference form and widens, exactly, on the way back.
+"""
+from collections import namedtuple
+
+import numpy as np
+
+NBND = 16
+
+LAYER_ARRAYS = ("play", "tlay", "h2ovmr", "o3vmr", "co2vmr", "ch4vmr", "n2ovmr", "o2vmr", "cfc11vmr", "cfc12vmr", "cfc22vmr",
+                "ccl4vmr", "cldfr", "cicewp", "cliqwp", "reice", "reliq", "alpha", "hr", "hrc")
+LEVEL_ARRAYS = ("plev", "tlev", "uflx", "dflx", "uflxc", "dflxc", "duflx_dt", "duflxc_dt")
+BAND_ARRAYS = ("emis", "plankbnd", "dplankbnd_dt")                      # (ncol, 16): no vertical axis
+LAYER_X_ARRAYS = ("tauaer", "planklay", "taug", "fracs")                # (ncol, nlay, 16 | NG)
+LEVEL_X_ARRAYS = ("planklev",)                                          # (ncol, nlay+1, 16)
+COLUMN_ARRAYS = ("tsfc",)
+ALL_ARRAYS = LAYER_ARRAYS + LEVEL_ARRAYS + BAND_ARRAYS + LAYER_X_ARRAYS + LEVEL_X_ARRAYS + COLUMN_ARRAYS + ("taucld",)
+
+
+class ArrayForm(namedtuple("ArrayForm", "real_bytes layer_fastest top_first")):
+    __slots__ = ()
+
+    def __new__(cls, real_bytes=8, layer_fastest=0, top_first=0):
+        return super().__new__(cls, int(real_bytes), int(layer_fastest), int(top_first))
+
+    @property
+    def is_reference(self):
+        return self == (8, 0, 0)
+
+
+REFERENCE = ArrayForm(8, 0, 0)
+ALL_FORMS = tuple(ArrayForm(r, l, t) for r in (8, 4) for l in (0, 1) for t in (0, 1))
+
+
+def reference_shape(name, ncol, nlay, ng=140):
+    """logical shape of array `name` in the reference form"""
+    if name in LAYER_ARRAYS:
+        return (ncol, nlay)
+    if name in LEVEL_ARRAYS:
+        return (ncol, nlay + 1)
+    if name in BAND_ARRAYS:
+        return (ncol, NBND)
+    if name == "taucld":
+        return (NBND, ncol, nlay)
+    if name in ("tauaer", "planklay"):
+        return (ncol, nlay, NBND)
+    if name in ("taug", "fracs"):
+        return (ncol, nlay, ng)
+    if name == "planklev":
+        return (ncol, nlay + 1, NBND)
+    if name in COLUMN_ARRAYS:
+        return (ncol,)
+    raise KeyError(name)
+
+
+def form_shape(name, ncol, nlay, form, ng=140):
+    """logical shape of array `name` in `form` (taucld moves its band index behind the layers when the layers are fastest)"""
+    if name == "taucld" and form.layer_fastest:
+        return (ncol, nlay, NBND)
+    return reference_shape(name, ncol, nlay, ng)
+
+
+def form_size(name, ncol, nlay, form, ng=140):
+    return int(np.prod(form_shape(name, ncol, nlay, form, ng)))
+
+
+def _vertical_axis(name, shape_is_reference):
+    """the axis of the vertical index, or None"""
+    if name in BAND_ARRAYS or name in COLUMN_ARRAYS:
+        return None
+    if name == "taucld":
+        return 2 if shape_is_reference else 1
+    return 1
+
+
+def _is_torch(a):
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+def _store(a, dtype_bytes, c_order):
+    """`a` with its logical shape kept, stored C-contiguous or with the first index fastest, as float64 / float32"""
+    if _is_torch(a):
+        import torch
+        a = a.to(torch.float64 if dtype_bytes == 8 else torch.float32)
+        if c_order or a.dim() <= 1:
+            return a.contiguous()
+        rev = tuple(reversed(range(a.dim())))
+        return a.permute(*rev).contiguous().permute(*rev)
+    a = np.asarray(a).astype(np.float64 if dtype_bytes == 8 else np.float32, copy=False)
+    return np.ascontiguousarray(a) if c_order else np.asfortranarray(a)
+
+
+def _flip(a, axis):
+    return a.flip(axis) if _is_torch(a) else np.flip(a, axis)
+
+
+def _move_axis(a, src, dst):
+    return a.movedim(src, dst) if _is_torch(a) else np.moveaxis(a, src, dst)
+
+
+def from_reference(d, form):
+    """The call arrays of `d` (reference form) in `form`; a new dict, the arrays are copies."""
+    form = ArrayForm(*form)
+    out = {}
+    for k, a in d.items():
+        if k not in ALL_ARRAYS or a is None:
+            out[k] = a
+            continue
+        ax = _vertical_axis(k, True)
+        if form.top_first and ax is not None:
+            a = _flip(a, ax)
+        if form.layer_fastest and k == "taucld":
+            a = _move_axis(a, 0, 2)                       # (16, ncol, nlay) -> (ncol, nlay, 16)
+        out[k] = _store(a, form.real_bytes, bool(form.layer_fastest))
+    return out
+
+
+def to_reference(d, form):
+    """The inverse: the call arrays of `d`, which lie in `form`, as float64 in the reference form (float32 values widened)."""
+    form = ArrayForm(*form)
+    out = {}
+    for k, a in d.items():
+        if k not in ALL_ARRAYS or a is None:
+            out[k] = a
+            continue
+        if form.layer_fastest and k == "taucld":
+            a = _move_axis(a, 2, 0)
+        ax = _vertical_axis(k, True)
+        if form.top_first and ax is not None:
+            a = _flip(a, ax)
+        out[k] = _store(a, 8, False)
+    return out
+
+
+def empty_like_form(names, ncol, nlay, form, ng=140, device=None, fill=None):
+    """Preallocated torch tensors for the arrays `names` in `form` on `device` (outputs of the device entries)."""
+    import torch
+    form = ArrayForm(*form)
+    dt = torch.float64 if form.real_bytes == 8 else torch.float32
+    out = {}
+    for k in names:
+        shape = form_shape(k, ncol, nlay, form, ng)
+        if form.layer_fastest or len(shape) == 1:
+            t = torch.empty(shape, dtype=dt, device=device)
+        else:
+            t = torch.empty(tuple(reversed(shape)), dtype=dt, device=device).permute(*reversed(range(len(shape))))
+        if fill is not None:
+            t.fill_(fill)
+        out[k] = t
+    return out
+
+
+def check_tensor(name, t, ncol, nlay, form, ng=140):
+    """TypeError / ValueError unless tensor `t` can be array `name` of a call in `form`: its dtype, its number of elements, and dense
+    storage (a form fixes where every element lies; a strided view does not have that layout)."""
+    import torch
+    form = ArrayForm(*form)
+    want = torch.float64 if form.real_bytes == 8 else torch.float32
+    if t.dtype != want:
+        raise TypeError(f"'{name}' is {t.dtype}, the array form (real_bytes={form.real_bytes}) needs {want}")
+    n = form_size(name, ncol, nlay, form, ng)
+    if t.numel() != n:
+        raise ValueError(f"'{name}' holds {t.numel()} elements, the array form needs {n} ({form_shape(name, ncol, nlay, form, ng)})")
+    if form.layer_fastest and not t.is_contiguous():
+        raise ValueError(f"'{name}' is not contiguous: layer_fastest=1 means C order with the column index first")

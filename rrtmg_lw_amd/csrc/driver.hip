@@ -101,6 +101,9 @@ struct State {
     // host-entry staging
     void *stage_base = nullptr;
     size_t stage_bytes = 0;
+    // the *_as entries' staging: a batch's arrays in float64 reference form; play, cldfr, alpha of a whole fused McICA call for the generator
+    void *form_base = nullptr, *form_gen = nullptr;
+    size_t form_bytes = 0, form_gen_bytes = 0;
     hipStream_t stream = nullptr;
     hipStream_t cp_in = nullptr, cp_out = nullptr;      // host-pointer entries: H2D and D2H copy streams
     double *h_tot = nullptr;                            // pinned host scratch of the non-McICA host entry: tauctot of HOST_SETS column batches
@@ -2144,6 +2147,9 @@ static int init_state(const char *static_tables_path, const char *kdata_path, do
         (void)hipSetDevice(G.device);
         (void)hipDeviceSynchronize();
         graphs_clear();
+        // (the *_as entries' staging is rebuilt by the next such call, on the device of this initialisation)
+        if (G.form_base) { (void)hipFree(G.form_base); G.form_base = nullptr; G.form_bytes = 0; }
+        if (G.form_gen) { (void)hipFree(G.form_gen); G.form_gen = nullptr; G.form_gen_bytes = 0; }
         if (G.device != device && G.cap) { (void)hipStreamDestroy(G.cap); G.cap = nullptr; }       // (the capture stream belongs to the device it was made on)
     }
     static unsigned long long init_count = 0;
@@ -2255,6 +2261,8 @@ static void finalize_state()
     if (G.ws_base) (void)hipFree(G.ws_base);
     if (G.opt_base) (void)hipFree(G.opt_base);
     if (G.stage_base) (void)hipFree(G.stage_base);
+    if (G.form_base) (void)hipFree(G.form_base);
+    if (G.form_gen) (void)hipFree(G.form_gen);
     if (first) {            // the queue and the generator's caches live on the first device
         if (Q.pinned) { forget_pinned(Q.pinned); (void)hipHostFree(Q.pinned); Q.pinned = nullptr; Q.pinned_doubles = 0; }
         Q.chunks.clear(); Q.ncol = 0; Q.open = false;
@@ -2488,7 +2496,7 @@ long long rrtmg_lw_hip_workspace_bytes(void)
     size_t tot = 0;
     for (int d = 0; d < g_ndev; d++) {
         const State &S = g_states[d];
-        tot += S.ws_bytes + S.opt_bytes + S.stage_bytes + S.mask_bytes + S.rnd_bytes + (S.kiss.dev ? sizeof(KissJump) * (KJ_NGROUP + 1) : 0);
+        tot += S.ws_bytes + S.opt_bytes + S.stage_bytes + S.form_bytes + S.form_gen_bytes + S.mask_bytes + S.rnd_bytes + (S.kiss.dev ? sizeof(KissJump) * (KJ_NGROUP + 1) : 0);
     }
     for (const MtStates &M : g_mt) tot += M.bytes();
     return (long long)tot;
@@ -3600,6 +3608,289 @@ int rrtmg_lw_hip_run_mcica_subcol_spectral(SUBCOL_PARAMS, SPEC_PARAMS)
 {
     ENTRY_LOCK;
     return mcica_subcol_host(spectral({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng}), {GCM_NAMES, CLOUD_NAMES, tauaer}, alpha, {OUT_NAMES, SPEC_NAMES});
+}
+
+}  // extern "C"
+
+// ---- device arrays in the caller's own form (rrtmg_lw_hip_*_as) ------------------------------------------------------------------------
+// The shape of the host-pointer entries (nomcica_host_range, mcica_subcol_host_range, gas_optics_host_range) with kernels where those have
+// copies: per batch of columns, on the caller's stream, k_form_in brings the caller's arrays into staged float64 reference-form arrays nb
+// columns wide, the solver runs on those (run_batch<true> / run_optics<true>, column 0 of nb), k_form_out takes the staged outputs back.
+// Below the entries the caller's arrays travel in GcmIn / FluxOut / OptOut like everywhere else - as addresses only: what they point to
+// has the form's element type and layout, and nothing but the two kernels reads or writes through them.
+namespace {
+
+struct FormItem { const void *user; int pos; int V, inner, kind; bool vertical; };
+// an array of the call by its position (CALL_ARRAYS): the vertical extent, the trailing index of the column-slowest form
+FormItem form_item(const void *user, int a, size_t L, int kind = FA_PLANE)
+{
+    const ArrayShape &sh = CALL_ARRAYS[a];
+    if (sh.per_layer == 0) return FormItem{user, a, (int)sh.extra, 1, kind, false};                       // tsfc, emis: no vertical axis
+    if (sh.per_layer == 16) return FormItem{user, a, (int)(L + sh.extra / 16), 16, kind, true};          // tauaer
+    return FormItem{user, a, (int)(L + sh.extra), kind == FA_PLANE ? 1 : NBND, kind, true};
+}
+size_t form_doubles(const FormItem &it, size_t nb)
+{
+    return nb * (size_t)it.V * (size_t)(it.kind == FA_TAUCTOT ? 1 : it.inner);
+}
+size_t form_tiles(const FormItem &it, size_t nb)
+{
+    const size_t nct = (nb + FORM_TILE - 1) / FORM_TILE;
+    if (it.kind == FA_TAUCLD) return nct * (size_t)it.V;
+    const size_t R = (size_t)it.V * (size_t)(it.kind == FA_TAUCTOT ? 1 : it.inner);
+    return nct * ((R + FORM_TILE - 1) / FORM_TILE);
+}
+// staged arrays of the items, packed from `base` for a batch nb columns wide (arrays whose size is a multiple of 16 values first: the rows
+// of taucld stay 128-byte aligned); staged[item] = its place.  Returns the doubles used.
+size_t form_place(const std::vector<FormItem> &items, size_t nb, double *base, std::vector<double *> &staged)
+{
+    staged.assign(items.size(), nullptr);
+    size_t off = 0;
+    for (int pass = 0; pass < 2; pass++)
+        for (size_t k = 0; k < items.size(); k++) {
+            const bool wide = items[k].kind == FA_TAUCLD || (items[k].kind == FA_PLANE && items[k].inner == 16);
+            if (wide != (pass == 0)) continue;
+            staged[k] = base ? base + off : nullptr;
+            off += form_doubles(items[k], nb);
+        }
+    return off;
+}
+// one launch of k_form_in (in = true) or k_form_out over the items
+int form_launch(hipStream_t s, bool in, const rrtmg_lw_hip_array_form &f, const std::vector<FormItem> &items, const std::vector<double *> &staged,
+                size_t ncol, size_t col0, size_t nb)
+{
+    if (items.empty()) return 0;
+    if (items.size() > (size_t)FORM_MAX) return fail(RRTMG_LW_HIP_EARG, "internal: %d arrays in one conversion table", (int)items.size());
+    FormTable t{};
+    size_t tiles = 0;
+    for (size_t k = 0; k < items.size(); k++) {
+        FormArray &e = t.a[k];
+        e.user = const_cast<void *>(items[k].user);
+        e.staged = staged[k];
+        e.V = items[k].V; e.inner = items[k].inner; e.kind = items[k].kind;
+        e.flip = items[k].vertical && f.top_first ? 1 : 0;
+        e.tile0 = (unsigned)tiles;
+        tiles += form_tiles(items[k], nb);
+    }
+    if (tiles > 0x7fffffffull) return fail(RRTMG_LW_HIP_EARG, "internal: conversion grid of %zu workgroups", tiles);
+    t.n = (int)items.size(); t.nb = (int)nb; t.layer_fastest = f.layer_fastest; t.ncol = ncol; t.col0 = col0;
+    const dim3 grid((unsigned)tiles), block(256);
+    if (in) {
+        if (f.real_bytes == 4) LAUNCH("k_form_in<f32>", (k_form_in<float>), grid, block, s, t);
+        else LAUNCH("k_form_in<f64>", (k_form_in<double>), grid, block, s, t);
+    } else {
+        if (f.real_bytes == 4) LAUNCH("k_form_out<f32>", (k_form_out<float>), grid, block, s, t);
+        else LAUNCH("k_form_out<f64>", (k_form_out<double>), grid, block, s, t);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+// the staging of a batch / of the generator's call-wide arrays: grows like the workspace, freed by finalize and by a re-initialisation
+int ensure_form(void **base, size_t *have, size_t bytes)
+{
+    if (*have >= bytes) return 0;
+    if (*base) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(*base)); *base = nullptr; *have = 0; }
+    HIP_TRY(hipMalloc(base, bytes));
+    *have = bytes;
+    return 0;
+}
+
+// what the three entries check first; 1 = the plain form (the entry forwards)
+int form_check(const rrtmg_lw_hip_array_form *f, bool *plain)
+{
+    const char *bad = !f ? "array form is null"
+                    : (f->real_bytes != 4 && f->real_bytes != 8) ? "array form: real_bytes must be 4 or 8"
+                    : (f->layer_fastest != 0 && f->layer_fastest != 1) ? "array form: layer_fastest must be 0 or 1"
+                    : (f->top_first != 0 && f->top_first != 1) ? "array form: top_first must be 0 or 1" : nullptr;
+    if (bad) { ENTRY_LOCK; return fail(RRTMG_LW_HIP_EARG, "%s", bad); }
+    *plain = f->real_bytes == 8 && !f->layer_fastest && !f->top_first;
+    return 0;
+}
+
+// The batches of a solver call (non-McICA: mode 0 - 2; fused McICA: mode 0 or 3 with the masks of the whole call in G.mask) on stream s.
+// u / uo: the caller's arrays.  Caller holds the entry lock, the workspace stands.
+int form_solve(const rrtmg_lw_hip_array_form &f, const CallDesc &d, int mode, const GcmIn &u, const FluxOut &uo, hipStream_t s)
+{
+    const size_t L = (size_t)d.nlay, ncol = (size_t)d.ncol;
+    const bool cloud = mode != 0;
+    // with inflglw >= 1 cldprop reads taucld only through its band sum (nomcica_host_range): one staged value per cell instead of sixteen
+    const bool use_tot = cloud && mode != 3 && d.inflg != 0;
+    const double *up[NA_IN];
+    gcm_pointers(u, nullptr, up);
+    std::vector<FormItem> ins, outs;
+    for (int a = 0; a < NA_GCM; a++) {
+        if (CALL_ARRAYS[a].cloud && !cloud) continue;
+        if (!up[a]) return fail(RRTMG_LW_HIP_EARG, "null input array (argument %d of rrtmg_lw's arrays)", a + 1);
+        ins.push_back(form_item(up[a], a, L, a == A_TAUCLD ? (use_tot ? FA_TAUCTOT : FA_TAUCLD) : FA_PLANE));
+    }
+    if (!have_outs(uo)) return fail(RRTMG_LW_HIP_EARG, "null output array");
+    double *uop[NA_CALL];
+    flux_pointers(uo, uop);
+    for (int a = A_UFLX; a < A_UFLXS; a++) if (a < A_DUFLX_DT || d.idrv == 1) outs.push_back(form_item(uop[a], a, L));
+    const size_t nbmax = (size_t)balanced_batch(d.ncol, eff_batch(d.nlay));
+    std::vector<double *> si, so;
+    const size_t n_in = form_place(ins, nbmax, nullptr, si), n_out = form_place(outs, nbmax, nullptr, so);
+    if (int rc = ensure_form(&G.form_base, &G.form_bytes, (n_in + n_out) * 8)) return rc;
+    if (int rc = ensure_pipeline()) return rc;
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last, 0));      // an earlier call, possibly on another stream, still owns the workspace and the staging
+    int rc = 0;
+    for (size_t col0 = 0; col0 < ncol && rc == 0; col0 += nbmax) {
+        const size_t nb = std::min(nbmax, ncol - col0);
+        const size_t used = form_place(ins, nb, (double *)G.form_base, si);
+        form_place(outs, nb, (double *)G.form_base + used, so);
+        const double *sp[NA_IN] = {};
+        for (size_t k = 0; k < ins.size(); k++) sp[ins[k].pos] = si[k];
+        GcmIn g = gcm_from(sp);
+        if (use_tot) { g.tauctot = g.taucld; g.taucld = nullptr; }
+        double *op[NA_CALL] = {};
+        for (size_t k = 0; k < outs.size(); k++) op[outs[k].pos] = so[k];
+        rc = form_launch(s, true, f, ins, si, ncol, col0, nb);
+        G.W.mask_col0 = mode == 3 ? col0 : 0;             // staged arrays start at column 0, the mask holds the call's columns
+        if (rc == 0) rc = run_batch<true>(s, (int)nb, 0, (int)nb, d.nlay, mode, d.idrv, 1, 16, g, ColIn{}, d.inflg, d.iceflg, d.liqflg, flux_from(op), nullptr);
+        if (rc == 0) rc = form_launch(s, false, f, outs, so, ncol, col0, nb);
+    }
+    G.W.mask_col0 = 0;
+    HIP_TRY(hipEventRecord(G.ev_last, s));
+    G.ev_last_valid = true;
+    return rc;
+}
+
+int nomcica_device_as(const rrtmg_lw_hip_array_form &f, const CallDesc &d, const GcmIn &u, const FluxOut &uo, void *stream)
+{
+    ENTRY_LOCK_FOR(u.play);
+    if (int rc = check_call(d, uo)) return rc;
+    const int mode = *d.icld == 0 ? 0 : (*d.icld == 1 ? 1 : 2);
+    const int nbmax = balanced_batch(d.ncol, eff_batch(d.nlay));
+    if (int rc = ensure_workspace(d.nlay, nbmax, mode != 0, false, d.idrv, mode)) return rc;
+    return form_solve(f, d, mode, u, uo, (hipStream_t)stream);
+}
+
+// fused generator + solver (mcica_subcol_host_range): the masks of the whole call first - from play, cldfr and alpha of every column,
+// staged call-wide - then the batches
+int mcica_subcol_device_as(const rrtmg_lw_hip_array_form &f, const CallDesc &d, const GcmIn &u, const void *alpha, const FluxOut &uo, void *stream)
+{
+    ENTRY_LOCK_FOR(u.play, d.irng && *d.irng != 0);
+    if (int rc = check_mcica_build()) return rc;
+    if (!d.icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
+    if (int rc = check_subcol_args(d.ncol, d.nlay, *d.icld, d.irng)) return rc;
+    if (d.idrv == 1 && (!uo.duflx_dt || !uo.duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
+    const int icld_gen = *d.icld;
+    if (*d.icld > 3) *d.icld = 2;                                 // what rrtmg_lw does to the generator's icld (src/rrtmg_lw_rad.f90:469)
+    const int mode = icld_gen == 0 ? 0 : 3;
+    const bool two = icld_gen == 4 || icld_gen == 5;
+    const hipStream_t s = (hipStream_t)stream;
+    const int nbmax = balanced_batch(d.ncol, eff_batch(d.nlay));
+    if (int rc = ensure_workspace(d.nlay, nbmax, mode != 0, false, d.idrv, mode)) return rc;
+    if (mode == 3) {
+        if (!u.play || !u.cldfr || (two && !alpha)) return fail(RRTMG_LW_HIP_EARG, two && !alpha ? "icld = 4/5 needs alpha" : "null generator input");
+        const size_t L = (size_t)d.nlay, n = (size_t)d.ncol;
+        std::vector<FormItem> gen = {form_item(u.play, A_PLAY, L), form_item(u.cldfr, A_CLDFR, L)};
+        if (two) gen.push_back(form_item(alpha, A_ALPHA, L));
+        std::vector<double *> sg;
+        const size_t need = form_place(gen, n, nullptr, sg);
+        if (int rc = ensure_form(&G.form_gen, &G.form_gen_bytes, need * 8)) return rc;
+        form_place(gen, n, (double *)G.form_gen, sg);
+        if (int rc = ensure_pipeline()) return rc;
+        if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last, 0));
+        if (int rc = form_launch(s, true, f, gen, sg, n, 0, n)) return rc;
+        if (int rc = generate_mask(s, d.ncol, d.nlay, icld_gen, d.permuteseed, *d.irng, sg[0], sg[1], two ? sg[2] : nullptr)) return rc;
+    }
+    return form_solve(f, d, mode, u, uo, s);
+}
+
+int gas_optics_device_as(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, int idrv, const GcmIn &u, const OptOut &uo, void *stream)
+{
+    ENTRY_LOCK_FOR(u.play);
+    if (int rc = check_common(ncol, nlay)) return rc;
+    if (int rc = check_optics(idrv, uo)) return rc;
+    const size_t L = (size_t)nlay;
+    const double *up[NA_IN];
+    gcm_pointers(u, nullptr, up);
+    std::vector<FormItem> ins, outs;
+    for (int a = 0; a <= A_EMIS; a++) {
+        if (!up[a]) return fail(RRTMG_LW_HIP_EARG, "gas optics: null input array");
+        ins.push_back(form_item(up[a], a, L));
+    }
+    // (pos: 0 .. 5 = the members of OptOut)
+    const auto out = [&](void *p, int pos, int V, int inner, bool vertical) { if (p) outs.push_back(FormItem{p, pos, V, inner, FA_PLANE, vertical}); };
+    out(uo.taug, 0, nlay, NGPT, true); out(uo.fracs, 1, nlay, NGPT, true); out(uo.planklay, 2, nlay, NBND, true);
+    out(uo.planklev, 3, nlay + 1, NBND, true); out(uo.plankbnd, 4, NBND, 1, false); out(idrv == 1 ? uo.dplankbnd : nullptr, 5, NBND, 1, false);
+    // (the outputs are ~40 times a column's inputs: batches of at most ~256 MB of staging each, like the host-pointer entry)
+    std::vector<double *> si, so;
+    const size_t per_col = (form_place(ins, 1, nullptr, si) + form_place(outs, 1, nullptr, so)) * 8;
+    const size_t cap = std::max<size_t>(64, std::min<size_t>((size_t)eff_batch(nlay), ((size_t)256 << 20) / per_col / 64 * 64));
+    const size_t nbmax = (size_t)balanced_batch(ncol, (int)std::min<size_t>(cap, (size_t)eff_batch(nlay)));
+    if (int rc = ensure_form(&G.form_base, &G.form_bytes, per_col * nbmax)) return rc;
+    if (int rc = ensure_pipeline()) return rc;
+    if (int rc = ensure_optics_ws(nlay, (int)nbmax)) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last, 0));
+    int rc = 0;
+    for (size_t col0 = 0; col0 < (size_t)ncol && rc == 0; col0 += nbmax) {
+        const size_t nb = std::min(nbmax, (size_t)ncol - col0);
+        const size_t used = form_place(ins, nb, (double *)G.form_base, si);
+        form_place(outs, nb, (double *)G.form_base + used, so);
+        const double *sp[NA_IN] = {};
+        for (size_t k = 0; k < ins.size(); k++) sp[ins[k].pos] = si[k];
+        double *op[6] = {};
+        for (size_t k = 0; k < outs.size(); k++) op[outs[k].pos] = so[k];
+        rc = form_launch(s, true, f, ins, si, (size_t)ncol, col0, nb);
+        if (rc == 0) rc = run_optics<true>(s, (int)nb, 0, (int)nb, nlay, idrv, gcm_from(sp), ColIn{}, OptOut{op[0], op[1], op[2], op[3], op[4], op[5]});
+        if (rc == 0) rc = form_launch(s, false, f, outs, so, (size_t)ncol, col0, nb);
+    }
+    HIP_TRY(hipEventRecord(G.ev_last, s));
+    G.ev_last_valid = true;
+    return rc;
+}
+
+}   // namespace
+
+extern "C" {
+
+#define AS_(name) (const double *)name
+#define GCM_PARAMS_AS                                                                                           \
+    const void *play, const void *plev, const void *tlay, const void *tlev, const void *tsfc,                   \
+    const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *n2ovmr,          \
+    const void *o2vmr, const void *cfc11vmr, const void *cfc12vmr, const void *cfc22vmr,                        \
+    const void *ccl4vmr, const void *emis
+#define CLOUD_PARAMS_AS const void *cldfr, const void *taucld, const void *cicewp, const void *cliqwp, const void *reice, const void *reliq
+#define OUT_PARAMS_AS void *uflx, void *dflx, void *hr, void *uflxc, void *dflxc, void *hrc, void *duflx_dt, void *duflxc_dt
+#define GCM_NAMES_AS                                                                                            \
+    AS_(play), AS_(plev), AS_(tlay), AS_(tlev), AS_(tsfc), AS_(h2ovmr), AS_(o3vmr), AS_(co2vmr), AS_(ch4vmr), AS_(n2ovmr), AS_(o2vmr), \
+    AS_(cfc11vmr), AS_(cfc12vmr), AS_(cfc22vmr), AS_(ccl4vmr), AS_(emis)
+#define CLOUD_NAMES_AS AS_(cldfr), AS_(taucld), AS_(cicewp), AS_(cliqwp), AS_(reice), AS_(reliq)
+#define OUT_NAMES_AS (double *)uflx, (double *)dflx, (double *)hr, (double *)uflxc, (double *)dflxc, (double *)hrc, (double *)duflx_dt, (double *)duflxc_dt
+
+int rrtmg_lw_hip_run_nomcica_device_as(const rrtmg_lw_hip_array_form *form, int ncol, int nlay, int *icld, int idrv, GCM_PARAMS_AS,
+    int inflglw, int iceflglw, int liqflglw, CLOUD_PARAMS_AS, const void *tauaer, OUT_PARAMS_AS, void *stream)
+{
+    bool plain = false;
+    if (int rc = form_check(form, &plain)) return rc;
+    if (plain) return rrtmg_lw_hip_run_nomcica_device(ncol, nlay, icld, idrv, GCM_NAMES_AS, inflglw, iceflglw, liqflglw, CLOUD_NAMES_AS, AS_(tauaer), OUT_NAMES_AS, stream);
+    return nomcica_device_as(*form, {ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw}, {GCM_NAMES_AS, CLOUD_NAMES_AS, AS_(tauaer)}, {OUT_NAMES_AS}, stream);
+}
+
+int rrtmg_lw_hip_run_mcica_subcol_device_as(const rrtmg_lw_hip_array_form *form, int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng,
+    GCM_PARAMS_AS, int inflglw, int iceflglw, int liqflglw, CLOUD_PARAMS_AS, const void *alpha, const void *tauaer, OUT_PARAMS_AS, void *stream)
+{
+    bool plain = false;
+    if (int rc = form_check(form, &plain)) return rc;
+    if (plain) return rrtmg_lw_hip_run_mcica_subcol_device(ncol, nlay, icld, idrv, permuteseed, irng, GCM_NAMES_AS, inflglw, iceflglw, liqflglw,
+                                                           CLOUD_NAMES_AS, AS_(alpha), AS_(tauaer), OUT_NAMES_AS, stream);
+    return mcica_subcol_device_as(*form, {ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng}, {GCM_NAMES_AS, CLOUD_NAMES_AS, AS_(tauaer)},
+                                  alpha, {OUT_NAMES_AS}, stream);
+}
+
+int rrtmg_lw_hip_gas_optics_device_as(const rrtmg_lw_hip_array_form *form, int ncol, int nlay, int idrv, GCM_PARAMS_AS,
+    void *taug, void *fracs, void *planklay, void *planklev, void *plankbnd, void *dplankbnd_dt, void *stream)
+{
+    bool plain = false;
+    if (int rc = form_check(form, &plain)) return rc;
+    if (plain) return rrtmg_lw_hip_gas_optics_device(ncol, nlay, idrv, GCM_NAMES_AS, (double *)taug, (double *)fracs, (double *)planklay,
+                                                     (double *)planklev, (double *)plankbnd, (double *)dplankbnd_dt, stream);
+    return gas_optics_device_as(*form, ncol, nlay, idrv, {GCM_NAMES_AS},
+                                OptOut{(double *)taug, (double *)fracs, (double *)planklay, (double *)planklev, (double *)plankbnd, (double *)dplankbnd_dt}, stream);
 }
 
 }  // extern "C"

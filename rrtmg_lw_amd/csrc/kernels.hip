@@ -4403,4 +4403,157 @@ __global__ __launch_bounds__(256) void k_fill_rows(const RowFill *__restrict__ t
     for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < e.n; i += (unsigned long long)FILL_BLOCKS * 256) e.dst[i] = e.bits;
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_form_in / k_form_out : the *_as entries (include/rrtmg_lw_hip.h, rrtmg_lw_hip_array_form).  One launch brings every input array of
+//               a column batch from the caller's form (float32 or float64; reference order or column-slowest C order; surface or top
+//               first) into the float64 reference form, nb columns wide, that the solver's kernels read; one launch takes the staged
+//               outputs back.  The table - one entry per array, passed by value - names the arrays; a workgroup finds its array from its
+//               block index and moves one tile of it.
+//   FA_PLANE    reference form (column, row) at column + nb * row, row = k + V * b (k: vertical index of V, b: trailing index of
+//               `inner`: 16 bands, NG g-points).  Reference-order caller: the same rows, ncol wide.  Column-slowest caller: the column's
+//               V * inner values lie together, at kk * inner + b - a transposition of 64 columns x 64 values through LDS, so that the
+//               loads run along the caller's fastest index and the stores along the columns.  The tile's rows are padded by one value
+//               (65 doubles = 130 dwords: the 32 lanes of a ds_read_b64 group that walk down a tile column fall on 32 different bank pairs).
+//   FA_TAUCLD   taucld, whose 16 bands are fastest in both forms ((16, ncol, nlay) | (ncol, nlay, 16)): they move as units, no LDS.
+//   FA_TAUCTOT  taucld again, where the solver reads only its band sum (inflglw >= 1, GcmIn::tauctot): the sum is formed here in the
+//               reference's order (src/rrtmg_lw_cldprop.f90:173-186) and one value per cell is staged.
+//   With `flip` the caller's vertical index runs from the top: reference k lies at V - 1 - k.  Offsets into the caller's arrays are
+//   64-bit (1e6 x 137 x 16 elements); threads past the batch's last column or the array's last row neither load nor store.
+// ------------------------------------------------------------------------------------------------
+enum { FA_PLANE = 0, FA_TAUCLD = 1, FA_TAUCTOT = 2 };
+struct FormArray {
+    void *user;                 // the caller's array (all ncol columns)
+    double *staged;             // the batch's columns in reference form
+    int V, inner, kind, flip;
+    unsigned tile0;             // first workgroup of this array
+};
+constexpr int FORM_MAX = 26;
+constexpr int FORM_TILE = 64;
+struct FormTable {
+    FormArray a[FORM_MAX];
+    int n;                      // arrays
+    int nb;                     // columns of the batch (width of the staged arrays)
+    int layer_fastest;
+    unsigned long long ncol, col0;      // the caller's columns, the batch's first
+};
+template <class T> __device__ __forceinline__ double form_load(const void *p, unsigned long long i) { return (double)((const T *)p)[i]; }
+template <class T> __device__ __forceinline__ void form_store(void *p, unsigned long long i, double v) { ((T *)p)[i] = (T)v; }
+// the caller's row (reference order) or offset inside the column (column-slowest order) of reference row r = k + V * b, and back
+__device__ __forceinline__ unsigned form_user_of(const FormArray &e, unsigned r, bool lf)
+{
+    const unsigned b = r / (unsigned)e.V, k = r - b * (unsigned)e.V, kk = e.flip ? (unsigned)e.V - 1u - k : k;
+    return lf ? kk * (unsigned)e.inner + b : kk + (unsigned)e.V * b;
+}
+__device__ __forceinline__ unsigned form_row_of(const FormArray &e, unsigned j)      // column-slowest offset j = kk * inner + b -> r
+{
+    const unsigned kk = j / (unsigned)e.inner, b = j - kk * (unsigned)e.inner, k = e.flip ? (unsigned)e.V - 1u - kk : kk;
+    return k + (unsigned)e.V * b;
+}
+__device__ __forceinline__ int form_find(const FormTable &t)
+{
+    int a = 0;
+    while (a + 1 < t.n && blockIdx.x >= t.a[a + 1].tile0) a++;
+    return a;
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_form_in(const FormTable t)
+{
+    __shared__ double tile[FORM_TILE][FORM_TILE + 1];
+    const FormArray e = t.a[form_find(t)];
+    const bool lf = t.layer_fastest != 0;
+    const unsigned nb = (unsigned)t.nb, nct = (nb + FORM_TILE - 1) / FORM_TILE;
+    const unsigned tl = blockIdx.x - e.tile0, ct = tl % nct, jt = tl / nct;
+    const unsigned lane = threadIdx.x & 63u, ty = threadIdx.x >> 6;
+    const unsigned long long ncol = t.ncol, col0 = t.col0;
+    if (e.kind == FA_TAUCLD) {           // jt: the reference layer; 64 columns x 16 bands
+        const unsigned k = jt, kk = e.flip ? (unsigned)e.V - 1u - k : k;
+#pragma unroll
+        for (unsigned it = 0; it < 4; it++) {
+            const unsigned el = threadIdx.x + 256u * it, col = ct * FORM_TILE + (el >> 4), b = el & 15u;
+            if (col >= nb) continue;
+            const unsigned long long cell = lf ? (col0 + col) * (unsigned long long)e.V + kk : (col0 + col) + ncol * kk;
+            e.staged[(size_t)NBND * ((size_t)col + (size_t)nb * k) + b] = form_load<T>(e.user, cell * NBND + b);
+        }
+        return;
+    }
+    const unsigned R = e.kind == FA_TAUCTOT ? (unsigned)e.V : (unsigned)e.V * (unsigned)e.inner;      // staged rows
+    if (!lf) {                           // the caller's rows are the reference's: lanes along the columns on both sides
+        const unsigned col = ct * FORM_TILE + lane;
+#pragma unroll 4
+        for (unsigned it = 0; it < FORM_TILE / 4; it++) {
+            const unsigned r = jt * FORM_TILE + ty + 4u * it;
+            if (col >= nb || r >= R) continue;
+            double v;
+            if (e.kind == FA_TAUCTOT) {
+                const unsigned kk = e.flip ? (unsigned)e.V - 1u - r : r;
+                const unsigned long long p = ((col0 + col) + ncol * kk) * NBND;
+                double sum = 0.0;
+                for (int ib = 0; ib < NBND; ib++) sum = sum + form_load<T>(e.user, p + ib);
+                v = sum;
+            } else v = form_load<T>(e.user, (col0 + col) + ncol * form_user_of(e, r, false));
+            e.staged[(size_t)col + (size_t)nb * r] = v;
+        }
+        return;
+    }
+    // column-slowest caller: loads along the column's own values, stores along the columns
+#pragma unroll 4
+    for (unsigned it = 0; it < FORM_TILE / 4; it++) {
+        const unsigned c = ty + 4u * it, col = ct * FORM_TILE + c, j = jt * FORM_TILE + lane;
+        if (col >= nb || j >= R) continue;
+        double v;
+        if (e.kind == FA_TAUCTOT) {
+            const unsigned long long p = ((col0 + col) * (unsigned long long)e.V + j) * NBND;
+            double sum = 0.0;
+            for (int ib = 0; ib < NBND; ib++) sum = sum + form_load<T>(e.user, p + ib);
+            v = sum;
+        } else v = form_load<T>(e.user, (col0 + col) * (unsigned long long)R + j);
+        tile[c][lane] = v;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (unsigned it = 0; it < FORM_TILE / 4; it++) {
+        const unsigned jj = ty + 4u * it, col = ct * FORM_TILE + lane, j = jt * FORM_TILE + jj;
+        if (col >= nb || j >= R) continue;
+        const unsigned r = e.kind == FA_TAUCTOT ? (e.flip ? (unsigned)e.V - 1u - j : j) : form_row_of(e, j);
+        e.staged[(size_t)col + (size_t)nb * r] = tile[lane][jj];
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_form_out(const FormTable t)          // FA_PLANE arrays only
+{
+    __shared__ double tile[FORM_TILE][FORM_TILE + 1];
+    const FormArray e = t.a[form_find(t)];
+    const bool lf = t.layer_fastest != 0;
+    const unsigned nb = (unsigned)t.nb, nct = (nb + FORM_TILE - 1) / FORM_TILE;
+    const unsigned tl = blockIdx.x - e.tile0, ct = tl % nct, jt = tl / nct;
+    const unsigned lane = threadIdx.x & 63u, ty = threadIdx.x >> 6;
+    const unsigned long long ncol = t.ncol, col0 = t.col0;
+    const unsigned R = (unsigned)e.V * (unsigned)e.inner;
+    if (!lf) {
+        const unsigned col = ct * FORM_TILE + lane;
+#pragma unroll 4
+        for (unsigned it = 0; it < FORM_TILE / 4; it++) {
+            const unsigned r = jt * FORM_TILE + ty + 4u * it;
+            if (col >= nb || r >= R) continue;
+            form_store<T>(e.user, (col0 + col) + ncol * form_user_of(e, r, false), e.staged[(size_t)col + (size_t)nb * r]);
+        }
+        return;
+    }
+#pragma unroll 4
+    for (unsigned it = 0; it < FORM_TILE / 4; it++) {          // loads along the columns (a tile row per value of the column) ...
+        const unsigned jj = ty + 4u * it, col = ct * FORM_TILE + lane, j = jt * FORM_TILE + jj;
+        if (col >= nb || j >= R) continue;
+        tile[jj][lane] = e.staged[(size_t)col + (size_t)nb * form_row_of(e, j)];
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (unsigned it = 0; it < FORM_TILE / 4; it++) {          // ... stores along the column's own values
+        const unsigned c = ty + 4u * it, col = ct * FORM_TILE + c, j = jt * FORM_TILE + lane;
+        if (col >= nb || j >= R) continue;
+        form_store<T>(e.user, (col0 + col) * (unsigned long long)R + j, tile[lane][c]);
+    }
+}
+
 }  // namespace rrlw

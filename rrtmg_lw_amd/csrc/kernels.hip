@@ -66,6 +66,7 @@
     defined(RRLW_SWEEPC_WAVES_CAP) || defined(RRLW_SWEEPC_QUAD_BARRIER) || defined(RRLW_SWEEPC_CODES) || defined(RRLW_SWEEPC_SPLIT) || defined(RRLW_SWEEPC_SPLIT3) || \
     defined(RRLW_SWEEPC_SPLIT_P1) || defined(RRLW_SWEEPZ_CT_SLOTS) || defined(RRLW_SWEEPZ_G2) || defined(RRLW_SWEEPZ_WAVES_G2) || defined(RRLW_SWEEPZ_WAVES_G1) || \
     defined(RRLW_SWEEPZ_WAVES_IDRV) || defined(RRLW_GEN_BESIDE_SWEEP) || defined(RRLW_FANOUT_MAX) || defined(RRLW_KI_SALU) || \
+    defined(RRLW_SWEEPC_THIN) || defined(RRLW_SWEEPC_THIN_P1) || \
     defined(RRLW_DBG_DUMP)      /* (driver.hip: one more entry, rrtmg_lw_hip_debug_scratch - reads k_layer's cell codes back; tuning builds only) */
 #define RRLW_BF_GEOMETRY 16u
 #else
@@ -3057,7 +3058,15 @@ __device__ __forceinline__ unsigned code_index(scr_t c) { return (unsigned)max((
 // the optical depth of a series cell, 0 for a table cell: max(c, 0) on the bit pattern (a negative float is a negative integer)
 __device__ __forceinline__ float code_od(scr_t c) { return __int_as_float(max(__float_as_int(c), 0)); }
 // (1 - transmittance, tfn factor) of a cell from its code and the table entry at code_index: rtrn :439-451.  Branch-free: a table
-// cell adds the series terms of od = 0, a series cell adds the table terms of entry 0 - both exact zeros.
+// cell adds the series terms of od = 0, a series cell adds the table terms of entry 0 - both exact zeros.  Float arithmetic up to the
+// two conversions (decode_f32: the part in float): the table values are floats already, and of the two summands one is an exact
+// zero; the series terms carry ~1e-7 relative error (od <= 0.06), the same class as the float table entries.
+__device__ __forceinline__ void decode_f32(scr_t c, const float2 &e, float &atr, float &tfn)
+{
+    const float od = code_od(c);
+    atr = e.x + __builtin_fmaf(-0.5f * od, od, od);
+    tfn = __builtin_fmaf(0.166667f, od, e.y);
+}
 __device__ __forceinline__ void decode(scr_t c, const float2 &e, double &atr, double &tfn)
 {
 #ifdef RRLW_DECODE_F64
@@ -3065,13 +3074,42 @@ __device__ __forceinline__ void decode(scr_t c, const float2 &e, double &atr, do
     atr = (double)e.x + fma(-0.5 * od, od, od);
     tfn = fma(0.166667, od, (double)e.y);
 #else
-    // float arithmetic up to the two conversions: the table values are floats already, and of the two summands one is an exact
-    // zero; the series terms carry ~1e-7 relative error (od <= 0.06), the same class as the float table entries
-    const float od = code_od(c);
-    atr = (double)(e.x + __builtin_fmaf(-0.5f * od, od, od));
-    tfn = (double)__builtin_fmaf(0.166667f, od, e.y);
+    float fa, ft;
+    decode_f32(c, e, fa, ft);
+    atr = (double)fa;
+    tfn = (double)ft;
 #endif
 }
+// Records that are all thin.  Above the clouds 96 % of the cells are series cells, and 89 % of the quad records a wave loads with one
+// 16-byte access hold series cells in all 64 lanes (profiles/sweepc_thin_records.md).  For those the table side of decode() - the index,
+// the LDS address, the gathered read of entry 0 = {0, 0}, the clamp and the two additions of zero - produces nothing.  k_sweepc tests
+// per record whether every code of the wave has its sign bit clear and then takes decode_thin (RRLW_SWEEPC_THIN = 1; 0 = decode()
+// everywhere; RRLW_SWEEPC_THIN_P1: the same choice for the downward phase above the clouds alone).  One test per thread and level
+// over all of its records, with two straight-line bodies, spilled registers in the downward phase of the 12- and 16-g-point bands and
+// was not kept.  The reduced code widths and the two numerics variants of decode() keep the general body.
+#ifndef RRLW_SWEEPC_THIN
+#define RRLW_SWEEPC_THIN 1
+#endif
+#ifndef RRLW_SWEEPC_THIN_P1
+#define RRLW_SWEEPC_THIN_P1 RRLW_SWEEPC_THIN
+#endif
+#if defined(RRLW_DECODE_F64) || defined(RRLW_SWEEP_EXPF)
+constexpr bool SWEEPC_THIN_OK = false;
+#else
+constexpr bool SWEEPC_THIN_OK = CODE_BITS == 32;
+#endif
+__host__ __device__ constexpr int sweepc_thin(int PHASE) { return !SWEEPC_THIN_OK ? 0 : (PHASE == 1 ? RRLW_SWEEPC_THIN_P1 : RRLW_SWEEPC_THIN) ? 1 : 0; }
+// decode_f32() of a series cell (sign bit of the code clear: the code is the optical depth, code_index is 0).  Rounds like decode_f32():
+// there e.x = +0.0f is added to a float that is never negative (od <= 0.06) and comes out +0 at od = 0 - the sum is that float, bit for
+// bit - and fmaf(0.166667f, od, +0.0f) rounds the one product 0.166667f * od; the float denormal mode is the same for all of these.
+__device__ __forceinline__ void decode_thin(scr_t od, float &atr, float &tfn)
+{
+    atr = __builtin_fmaf(-0.5f * od, od, od);
+    tfn = 0.166667f * od;
+}
+// no code of the wave's lanes in these records is a table code: a wave-uniform (scalar) condition, the exec mask stays whole.  A negative
+// float - a table code, -0.0f included - is a negative integer.
+__device__ __forceinline__ bool wave_all_thin(unsigned orw) { return __builtin_amdgcn_ballot_w64((int)orw < 0) == 0ull; }
 // RRLW_SWEEP_EXPF (measurement variant, north_star "__builtin_amdgcn_expf for transmittance"): the table entry of index i evaluated
 // instead of looked up - the same closed forms rrtmg_lw_ini tabulates (src/rrtmg_lw_init.f90:125-142: t = i / 1e4,
 // tau = bpade t / (1 - t), 1 - exp(-tau), tfn = tau / 6 below 0.06 else 1 - 2 (1 / tau - exp / (1 - exp))) in float32 with the hardware
@@ -3446,6 +3484,9 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
         // (sums as a tree - pairs inside a quad, then the quads: a running sum over 16 g-points is a chain of 16 dependent additions, and a
         // wave issues in order, so each of them would hold the wave for the latency of the one before)
         double qs[G], qsc[G], qd[G], qdc[G];
+        // MODE 0: every cell through decode().  1: a record whose codes are series codes in all 64 lanes takes decode_thin - only the
+        // transmittance terms sit in the (scalar) branch, the level's loads and the recurrences are common to both sides.
+        constexpr int MODE = sweepc_thin(PHASE);
 #pragma unroll
         for (int k = 0; k < G; k++) {
             float2 e[4];
@@ -3453,9 +3494,38 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
 #pragma unroll
             for (int c = 0; c < NC; c++) if (c == slot) pk = cc[k][c];
             const scr4 ck = unpack4(pk);
+            bool thin = false;
+            if constexpr (MODE == 1) {
+                unsigned orw = pk.w[0];
 #pragma unroll
-            for (int jj = 0; jj < 4; jj++) e[jj] = RRLW_LUT_ENTRY(s_lut, code_index(ck.v[jj]));
-            {
+                for (int i = 1; i < CODE_WORDS; i++) orw |= pk.w[i];
+                thin = wave_all_thin(orw);
+            }
+            if constexpr (MODE == 0) {
+#pragma unroll
+                for (int jj = 0; jj < 4; jj++) e[jj] = RRLW_LUT_ENTRY(s_lut, code_index(ck.v[jj]));
+            }
+            if constexpr (MODE == 0) {
+                const pk4 nx = ld_c(lev + NC * dir, k);
+#pragma unroll
+                for (int c = 0; c < NC; c++) if (c == slot) cc[k][c] = nx;
+            }
+            // (floats across the join, widened behind it: four registers per quad more than the codes they replace)
+            float fa[4], ft[4];
+            if constexpr (MODE == 1) {
+                if (thin) {
+#pragma unroll
+                    for (int jj = 0; jj < 4; jj++) decode_thin(ck.v[jj], fa[jj], ft[jj]);
+                } else {
+#pragma unroll
+                    for (int jj = 0; jj < 4; jj++) e[jj] = RRLW_LUT_ENTRY(s_lut, code_index(ck.v[jj]));
+#pragma unroll
+                    for (int jj = 0; jj < 4; jj++) decode_f32(ck.v[jj], e[jj], fa[jj], ft[jj]);
+                }
+            }
+            if constexpr (MODE == 1) {
+                // (behind the branch, where the record's codes have been consumed: issued in front of it, while they are live, the load
+                // cannot go to their registers, the slots rotate through copies at the end of a round and those wait for every load)
                 const pk4 nx = ld_c(lev + NC * dir, k);
 #pragma unroll
                 for (int c = 0; c < NC; c++) if (c == slot) cc[k][c] = nx;
@@ -3464,7 +3534,11 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
             for (int jj = 0; jj < 4; jj++) {
                 const int j = 4 * k + jj;
                 double atr, tfn;
-                decode(ck.v[jj], e[jj], atr, tfn);
+                if constexpr (MODE == 0) decode(ck.v[jj], e[jj], atr, tfn);
+                else {
+                    atr = (double)fa[jj];
+                    tfn = (double)ft[jj];
+                }
                 double fr = row[j];
                 if constexpr (BIN) fr = fma(fpl, row[16 + j] - fr, fr);
                 const double bb = fr * fma(tfn, dpl, blay);
@@ -3483,6 +3557,18 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
                 if constexpr (TWO) qdc[k] = (dradc[4 * k] + dradc[4 * k + 1]) + (dradc[4 * k + 2] + dradc[4 * k + 3]);
             }
             if (RRLW_SWEEPC_QUAD_BARRIER) __builtin_amdgcn_sched_barrier(0);
+            if constexpr (MODE == 1) {
+                // (the quad's recurrences stay in front of the next record's branch: sunk behind it - their results are not used before
+                // the end of the level - the transmittance terms of every quad of the level are live across the branches, 16 registers
+                // per quad)
+#pragma unroll
+                for (int jj = 0; jj < 4; jj++) {
+                    asm volatile("" : "+v"(rad[4 * k + jj]));
+                    if constexpr (TWO && !DN) asm volatile("" : "+v"(radc[4 * k + jj]));
+                    if constexpr (IDRV && !DN) asm volatile("" : "+v"(drad[4 * k + jj]));
+                    if constexpr (IDRV && TWO && !DN) asm volatile("" : "+v"(dradc[4 * k + jj]));
+                }
+            }
         }
         auto tree = [&](const double (&q)[G]) -> double {
             if constexpr (G == 1) return q[0];

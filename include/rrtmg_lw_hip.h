@@ -379,6 +379,17 @@ int rrtmg_lw_hip_set_layer_split(int on);
 int rrtmg_lw_hip_set_column_sort(int on, int min_gain);
 /* the threshold in force (min_gain above; values beyond 2^24 are taken as 2^24 = never) */
 int rrtmg_lw_hip_column_sort_min(void);
+/* A block of 64 columns that holds no cloud at all once its window is sorted, and did as the columns lie, is worth more than the levels of
+ * its top: where its group of twelve sorted blocks is cloud-free it is swept like a cloud-free call (below).  `percent` of nlay block-levels
+ * are added to the window's gain for each such block (0 .. 1000; default 18, i.e. 12 block-levels at 72 layers; 0: the criterion above; RRTMG_LW_COLSORT_CLEAR).  Results do not
+ * depend on it (bit for bit).  Returns the previous value; rrtmg_lw_hip_column_sort_clear() the value in force. */
+int rrtmg_lw_hip_set_column_sort_clear(int percent);
+int rrtmg_lw_hip_column_sort_clear(void);
+/* The sweeps of a cloudy batch hand over per group of twelve sorted 64-column blocks at the group's highest cloud.  A group that holds no
+ * cloud in any column is swept like a cloud-free call - one clear-sky launch over the whole column, one stream, 8-byte partials - and
+ * leaves the three cloudy launches (default on, RRTMG_LW_CLEAR_GROUPS=0 to switch off: such a group then goes through all three with two
+ * identical streams).  Results do not depend on it (bit for bit).  Returns the previous value. */
+int rrtmg_lw_hip_set_clear_groups(int on);
 /* Bytes of device memory the library holds right now, over all its devices: per-batch workspace (it holds what the call shapes seen so far need and only
  * grows: per column of the batch at 72 layers 62 KB for cloud-free calls, 148 KB for rtrnmr, 152 KB for rtrn, 166 KB with idrv = 1; 310 KB at
  * 137 layers with idrv = 1: rrtmg_lw_hip_set_batch trades it against launch count), host-entry staging, McICA masks, the slab buffer

@@ -227,6 +227,23 @@ def column_sort_min():
     return int(lib().rrtmg_lw_hip_column_sort_min())
 
 
+def set_column_sort_clear(percent):
+    """what a block that the column order leaves without any cloud adds to its window's gain, in per cent of nlay block-levels
+    (rrtmg_lw_hip_set_column_sort_clear); returns the previous value"""
+    return int(lib().rrtmg_lw_hip_set_column_sort_clear(C.c_int(int(percent))))
+
+
+def column_sort_clear():
+    """the bonus of set_column_sort_clear in force"""
+    return int(lib().rrtmg_lw_hip_column_sort_clear())
+
+
+def set_clear_groups(on):
+    """cloud-free block groups of a cloudy batch take the one clear-sky sweep launch of a cloud-free call (rrtmg_lw_hip_set_clear_groups);
+    returns the previous on / off"""
+    return int(lib().rrtmg_lw_hip_set_clear_groups(C.c_int(1 if on else 0)))
+
+
 def cu_partition():
     return int(lib().rrtmg_lw_hip_cu_partition())
 

@@ -375,8 +375,8 @@ hipEvent_t get_event()
 template <int Q, bool SPEC = false>
 int sweepc_attr_one()
 {
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 0, false, sweepc_nt(Q, 0, false), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));      // (cloud-free groups of a cloudy call: in the tuning build too)
 #ifndef RRLW_TUNE
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 0, false, sweepc_nt(Q, 0, false), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
     HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 0, true, sweepc_nt(Q, 0, true), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
     HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 2, true, sweepc_nt(Q, 2, true), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
 #endif
@@ -615,6 +615,15 @@ bool use_colsort(bool gcm, int mode, int nb);
 // block-levels a window's reordering must take out of the cloud zone (k_colsort; measured break-even on an MI355X, profiles/round4_column_order.md)
 constexpr int COLSORT_NEVER = 1 << 24;     // no window gains this many block-levels (4 blocks x 603 layers at most): "never reorder"
 int g_colsort_min = []() { const char *e = getenv("RRTMG_LW_COLSORT_MIN"); return e ? std::max(0, std::min(atoi(e), COLSORT_NEVER)) : 24; }();
+// what a block that the reordering leaves without any cloud adds to its window's gain, in per cent of nlay block-levels (k_colsort's
+// clear_bonus; rrtmg_lw_hip_set_column_sort_clear / RRTMG_LW_COLSORT_CLEAR; measurement: profiles/clear_groups.md)
+constexpr int COLSORT_CLEAR_MAX = 1000;
+constexpr int COLSORT_CLEAR_DEFAULT = 18;      // 12 block-levels at 72 layers: with the 13.8 the benchmark's windows gain on average, past the threshold of 24 (profiles/clear_groups.md)
+int g_colsort_clear = []() { const char *e = getenv("RRTMG_LW_COLSORT_CLEAR"); return e ? std::max(0, std::min(atoi(e), COLSORT_CLEAR_MAX)) : COLSORT_CLEAR_DEFAULT; }();
+// Block groups of a cloudy batch that hold no cloud (hand-off level 0) are swept as a cloud-free call sweeps its columns - one launch, one
+// stream, 8-byte partials (SweepArgs::cfree, run_sweep).  rrtmg_lw_hip_set_clear_groups / RRTMG_LW_CLEAR_GROUPS=0 keep them in the three
+// cloudy launches; results do not depend on it.
+bool g_clear_groups = []() { const char *e = getenv("RRTMG_LW_CLEAR_GROUPS"); return !e || atoi(e) != 0; }();
 
 // the workspace view of prep set k (see State::prep); sorted: the batch's columns go through k_colsort's order
 Workspace ws_for(int k, bool sorted)
@@ -696,7 +705,7 @@ int run_prep(hipStream_t s, const Workspace &Wk, int nb, int col0, int nct, int 
     const dim3 cgrid1((nb + 63) / 64), cblock1(64);
     if (Wk.perm) {
         const dim3 wgrid((nb + COLSORT_WIN - 1) / COLSORT_WIN);
-        LAUNCH("k_colsort", (k_colsort<GCM>), wgrid, dim3(COLSORT_WIN, COLSORT_TY), s, Wk, g, c, nb, col0, nct, g_colsort_min);
+        LAUNCH("k_colsort", (k_colsort<GCM>), wgrid, dim3(COLSORT_WIN, COLSORT_TY), s, Wk, g, c, nb, col0, nct, g_colsort_min, (int)((long long)Wk.nlay * g_colsort_clear / 100));
     }
     // (k_cloudscan needs nothing of k_colprep - k_cloudlay does: the secants - and both are one dependent walk over a column's layers: with a
     // side stream, a call that is a single batch, they run side by side: -30 us of its 0.5 ms)
@@ -837,6 +846,9 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, int nb, int col0, int nct, in
     SweepArgs sa;
     sa.ncol = nb; sa.col0 = col0; sa.nct = nct; sa.idrv = idrv; sa.istart = istart; sa.iend = iend;
     sa.split = split ? 1 : 0;
+    // (cloud-free block groups of a batch that takes the three sweep launches: their own launch, below)
+    const bool cfree = g_clear_groups && mode != 0 && !one_sweep(nb, mode);
+    sa.cfree = cfree ? 1 : 0;
     sa.emis = GCM ? g.emis : c.semiss;
     sa.cldfrac = GCM ? g.cldfr : c.cldfrac;
     sa.tlay = GCM ? g.tlay : c.tavel;
@@ -850,7 +862,9 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, int nb, int col0, int nct, in
     // k_sweepc<., 1> (layers above the batch's highest cloud, downward), k_sweepz<., mode> (layers 1 .. ltop down, surface, up) and
     // k_sweepc<., 2> (layers above, upward).  The classes are independent of each other: with `fan` each class has its own stream;
     // on one stream the launches go phase by phase (all downward ones, then the cloud zone, then the upward ones) so that consecutive
-    // launches never wait for each other's last workgroups.
+    // launches never wait for each other's last workgroups.  With `cfree` a fourth launch per class, k_sweepc<., 0> over the sorted block
+    // order, takes the groups that hold no cloud - whole columns, one stream - and the workgroups of the other three leave at once there
+    // (each decides by its group's hand-off level; the grids stay those of the batch).
     SweepGroups fg;
     if (!make_groups(mode, idrv, istart, iend, fg)) return fail(RRTMG_LW_HIP_EARG, "internal: more than %d sweep groups", NGROUP_MAX);
     if ((!split && fg.n > G.ws_groups) || (idrv == 1 && !G.ws_gdp)) return fail(RRTMG_LW_HIP_EARG, "internal: workspace holds %d band groups, the call needs %d", G.ws_groups, fg.n);
@@ -921,7 +935,7 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, int nb, int col0, int nct, in
 #else
             if (mode == 0) SWEEPC_Q(0);
 #endif
-            else if (phase == 0) SWEEPC_Q(1);
+            else if (phase == 0) { SWEEPC_Q(1); if (cfree) SWEEPC_Q(0); }
             else SWEEPC_Q(2);
         }
     }
@@ -937,8 +951,8 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, int nb, int col0, int nct, in
     {
         const dim3 wgrid((nb + COLSORT_WIN - 1) / COLSORT_WIN, (nlay + 1 + FLUX_LV - 1) / FLUX_LV), wblock(COLSORT_WIN, FLUX_TY);
         const double *pz = GCM ? g.plev : c.pz;
-        if (idrv == 1) LAUNCH_LDS("k_flux", (k_flux<true>), wgrid, wblock, FLUX_LDS_BYTES, s, G.D, Wk, out, pz, nb, col0, nct, mode == 0 ? 1 : 0, fg.n, gsz);
-        else LAUNCH_LDS("k_flux", (k_flux<false>), wgrid, wblock, FLUX_LDS_BYTES, s, G.D, Wk, out, pz, nb, col0, nct, mode == 0 ? 1 : 0, fg.n, gsz);
+        if (idrv == 1) LAUNCH_LDS("k_flux", (k_flux<true>), wgrid, wblock, FLUX_LDS_BYTES, s, G.D, Wk, out, pz, nb, col0, nct, mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0);
+        else LAUNCH_LDS("k_flux", (k_flux<false>), wgrid, wblock, FLUX_LDS_BYTES, s, G.D, Wk, out, pz, nb, col0, nct, mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
@@ -1088,7 +1102,7 @@ int run_pipelined(hipStream_t s, int ncol, int nlay, int mode, int idrv, const G
         // (what else decides which kernels run with which arguments: the workspace, the tuning switches)
         // (what the kernel nodes carry BY VALUE: the tables of this initialisation - DevTables with heatfac and the table pointers - on its device)
         key_put(key, G.init_gen); key_put(key, G.device);
-        key_put(key, G.ws_base); key_put(key, G.ws_bytes); key_put(key, g_colsort); key_put(key, g_colsort_min); key_put(key, g_one_sweep_max);
+        key_put(key, G.ws_base); key_put(key, G.ws_bytes); key_put(key, g_colsort); key_put(key, g_colsort_min); key_put(key, g_colsort_clear); key_put(key, g_clear_groups); key_put(key, g_one_sweep_max);
         key_put(key, g_wide_window); key_put(key, g_layer_split); key_put(key, g_prep_fork); key_put(key, G.sweep_fanout); key_put(key, eff_batch(nlay)); key_put(key, g_split_max);
         for (auto &e : G.graphs) if (e.key == key) { gent = &e; break; }
         if (!gent) {
@@ -2444,6 +2458,32 @@ int rrtmg_lw_hip_column_sort_min(void)
 {
     ENTRY_LOCK;
     return g_colsort_min;
+}
+
+// What a block that k_colsort's order leaves without any cloud adds to its window's gain, in per cent of nlay block-levels (0 .. 1000;
+// such a block leaves the cloudy launches where its group of sorted blocks is cloud-free).  Results do not depend on it.  Returns the
+// previous value.
+int rrtmg_lw_hip_set_column_sort_clear(int percent)
+{
+    ENTRY_LOCK;
+    const int prev = g_colsort_clear;
+    g_colsort_clear = std::max(0, std::min(percent, COLSORT_CLEAR_MAX));
+    return prev;
+}
+int rrtmg_lw_hip_column_sort_clear(void)
+{
+    ENTRY_LOCK;
+    return g_colsort_clear;
+}
+
+// Cloud-free block groups of a cloudy batch in one k_sweepc<., 0> launch (on = 1, default) or in the three cloudy launches like every
+// other group (0).  Results do not depend on it.  Returns the previous value.
+int rrtmg_lw_hip_set_clear_groups(int on)
+{
+    ENTRY_LOCK;
+    const int prev = g_clear_groups ? 1 : 0;
+    g_clear_groups = on != 0;
+    return prev;
 }
 
 // CU partition of the overlapped pipeline (device-pointer entries): k_layer of batch i + 1 on `layer_cus` CUs (rounded to a multiple of 8:

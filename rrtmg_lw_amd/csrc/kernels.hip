@@ -267,10 +267,13 @@ __device__ __forceinline__ double fdiv(double a, double b)
 // A window is reordered only where that pays: reading the caller's arrays out of order costs every kernel something (eight-byte accesses
 // spread over the window's cache lines instead of consecutive ones), so the order is taken when it removes at least `min_gain` block-levels
 // from the cloud zone - the sum over the window's four 64-column blocks of the block's highest cloudy layer, as the columns lie against
-// sorted - and the window keeps its order otherwise (a homogeneous deck, a tower system that fills whole blocks).
+// sorted - and the window keeps its order otherwise (a homogeneous deck, a tower system that fills whole blocks).  A block that holds no
+// cloud at all once sorted and did as the columns lie is worth more than its top: where its group of sorted blocks is cloud-free too it
+// leaves the cloudy launches altogether for the one-stream sweep of a cloud-free call (SweepArgs::cfree).  `clear_bonus` block-levels are
+// added to the gain for each such block (driver.hip: g_colsort_clear, a share of nlay).
 constexpr int COLSORT_TY = 4;       // threads per column: the walk over the layers and the copy of the rows in four parts
 template <bool GCM>
-__global__ __launch_bounds__(COLSORT_WIN * COLSORT_TY) void k_colsort(Workspace W, GcmIn g, ColIn c, int ncol, int col0, int nct, int min_gain)
+__global__ __launch_bounds__(COLSORT_WIN * COLSORT_TY) void k_colsort(Workspace W, GcmIn g, ColIn c, int ncol, int col0, int nct, int min_gain, int clear_bonus)
 {
     constexpr int NB = COLSORT_WIN / 64;
     __shared__ int s_key[COLSORT_WIN], s_perm[COLSORT_WIN], s_top[COLSORT_TY][COLSORT_WIN];
@@ -307,7 +310,7 @@ __global__ __launch_bounds__(COLSORT_WIN * COLSORT_TY) void k_colsort(Workspace 
     __syncthreads();
     int gain = 0;
 #pragma unroll
-    for (int b = 0; b < NB; b++) gain += s_nat[b] - s_srt[b];
+    for (int b = 0; b < NB; b++) gain += s_nat[b] - s_srt[b] + ((s_srt[b] == 0 && s_nat[b] != 0) ? clear_bonus : 0);
     const bool keep = gain * 4 < min_gain * NB;     // (uniform over the workgroup; min_gain is quoted for four blocks)
     if (ty == 0) {
         if (keep) rank = t;
@@ -2942,6 +2945,9 @@ struct SweepArgs {
                                // otherwise - so the fluxes do not depend on it
     int ncol, col0, nct, idrv;
     int istart, iend;          // only bands in [istart, iend] are swept
+    int cfree;                 // 1 (a cloudy batch of three sweep launches, driver.hip: g_clear_groups): the block groups whose hand-off level is 0 -
+                               // no cloudy cell in any of their columns - are swept by a k_sweepc<., 0> launch over the sorted block order and by
+                               // no other: a workgroup of that launch leaves unless its group's level is 0, one of the other three if it is
     const double *emis;        // semiss (nct,16)
     const double *cldfrac;     // (nct,nlay)
     const double *tlay;        // (nct,nlay)     layer temperatures    (tlay | tavel)
@@ -3313,6 +3319,10 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
     constexpr bool DOWN = PHASE != 2, UP = PHASE != 1, TWO = PHASE == 2;       // TWO: total and clear-sky streams differ
     constexpr int NVAL = sweepc_nval(PHASE, IDRV);
     extern __shared__ __align__(16) unsigned char smem[];
+    // The hand-off level of the workgroup's block group (it never straddles two groups): ONE scalar load, taken before anything is staged.
+    // Cloud-free groups of a cloudy batch (SweepArgs::cfree) belong to phase 0 and to no other phase.  (A cloud-free call has no groups.)
+    const int hgrp = (PHASE == 0 && !a.cfree) ? 0 : __builtin_amdgcn_readfirstlane(W.hgrp[(blockIdx.x * blockDim.z) / SORT_GROUP]);
+    if (a.cfree && (PHASE == 0) != (hgrp == 0)) return;
     // (a wave = 64 consecutive threadIdx.x of one (y, z): band and sub-block are wave-uniform - made scalar, so that everything derived
     // from the band, buffer descriptors included, lives in scalar registers)
     const int tx = threadIdx.x, ty = __builtin_amdgcn_readfirstlane(threadIdx.y), sub = __builtin_amdgcn_readfirstlane(threadIdx.z);
@@ -3323,9 +3333,9 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
     double (*s_fr)[16] = reinterpret_cast<double (*)[16]>(smem + SWEEP_LUT_BYTES + bi * SWEEPC_BAND_BYTES + SWEEP_PL_BYTES);
     double *red = reinterpret_cast<double *>(smem + SWEEP_LUT_BYTES + nb * SWEEPC_BAND_BYTES);      // [2][NVAL][nb][NC][ncw]
     // the wave's 64-column block: position (workgroup, sub-block) of the order k_blocksort left (deepest clouds first); a cloud-free call
-    // (PHASE 0) has no order and takes the blocks as they come
+    // (PHASE 0 without cfree) has no order and takes the blocks as they come
     const int slot = blockIdx.x * nsb + sub;
-    const int cblock = PHASE == 0 ? slot : __builtin_amdgcn_readfirstlane(W.order[slot]);
+    const int cblock = (PHASE == 0 && !a.cfree) ? slot : __builtin_amdgcn_readfirstlane(W.order[slot]);
     const int col = cblock * 64 + tx;
     const int bsel = a.split ? (int)blockIdx.y : 0;                             // split: this workgroup's band of the group
     const unsigned long long bands = a.bands >> (4 * bsel);
@@ -3345,7 +3355,7 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
     sweep_stage_lut(T, smem, (sub * ny + ty) * 64 + tx, 64 * ny * nsb);
     sweep_stage_band(T, s_pl, s_fr, B, alt16, lo_bin, up_bin, (sub * NT + part) * 64 + tx, NT * ncw);
     __syncthreads();
-    const int lo = PHASE == 0 ? 1 : __builtin_amdgcn_readfirstlane(W.hgrp[(blockIdx.x * nsb) / SORT_GROUP]) + 1;       // layers lo .. nlay (uniform over the workgroup)
+    const int lo = PHASE == 0 ? 1 : hgrp + 1;       // layers lo .. nlay (uniform over the workgroup)
     const size_t qstride = (size_t)nlay * ncb;
     const unsigned *__restrict__ sC = W.scr[S_CODE] + (size_t)quad * qstride * CODE_WORDS;
     const unsigned *__restrict__ sFw = W.fw + (size_t)fw_slot(B) * nlay * ncb;
@@ -3649,6 +3659,25 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
             usum = usum + rad[j];
             if constexpr (IDRV) { drad[j] = times(fr, dpb); dusum = dusum + drad[j]; }
         }
+        if (a.cfree) {
+            // In a cloudy batch the surface partial of every other group comes from k_sweepz: one thread per quad adds its four radiances
+            // in sequence, round_end the band's quads pairs first.  The same order here - a level's partial must not depend on the path,
+            // and batch size decides which blocks share a group.  (A cloud-free call keeps the running sum it has always had.)
+            double qs[G], qd[G];
+#pragma unroll
+            for (int k = 0; k < G; k++) {
+                qs[k] = 0.0; qd[k] = 0.0;
+#pragma unroll
+                for (int jj = 0; jj < 4; jj++) {
+                    qs[k] = qs[k] + rad[4 * k + jj];
+                    if constexpr (IDRV) qd[k] = qd[k] + drad[4 * k + jj];
+                }
+            }
+            if constexpr (G == 1) { usum = qs[0]; dusum = qd[0]; }
+            else if constexpr (G == 2) { usum = qs[0] + qs[1]; dusum = qd[0] + qd[1]; }
+            else if constexpr (G == 3) { usum = (qs[0] + qs[1]) + qs[2]; dusum = (qd[0] + qd[1]) + qd[2]; }
+            else { usum = (qs[0] + qs[1]) + (qs[2] + qs[3]); dusum = (qd[0] + qd[1]) + (qd[2] + qd[3]); }
+        }
         red_put(0, 0, usum);
         if constexpr (IDRV) red_put(0, 1, dusum);
         round_end(false_type{}, 0, 1);              // level 0
@@ -3738,6 +3767,9 @@ __global__ __launch_bounds__(256 * sweepz_waves(NQ, IDRV), sweepz_waves(NQ, IDRV
     constexpr int NS2 = MODE == 2 ? NG : 1;          // rtrnmr's extra state
     constexpr int NSD = IDRV ? NG : 1;               // d/dT state
     extern __shared__ __align__(16) unsigned char smem[];
+    // (a group without cloud is k_sweepc<., 0>'s - SweepArgs::cfree: the surface, all that is left for the zone there, is done by that launch)
+    const int ltop = __builtin_amdgcn_readfirstlane(W.hgrp[(blockIdx.x * blockDim.z) / SORT_GROUP]);       // layers 1 .. ltop (uniform over the workgroup): one scalar load, before anything is staged
+    if (a.cfree && ltop == 0) return;
     const int tx = threadIdx.x, ty = __builtin_amdgcn_readfirstlane(threadIdx.y), sub = __builtin_amdgcn_readfirstlane(threadIdx.z);
     const int bi = ty / NT, part = ty % NT;
     const int ny = blockDim.y, nb = ny / NT, nsb = blockDim.z, ncw = 64 * nsb;
@@ -3765,7 +3797,6 @@ __global__ __launch_bounds__(256 * sweepz_waves(NQ, IDRV), sweepz_waves(NQ, IDRV
     sweep_stage_lut(T, smem, (sub * ny + ty) * 64 + tx, 64 * ny * nsb);
     sweep_stage_band(T, s_pl, s_fr, B, alt16, lo_bin, up_bin, (sub * NT + part) * 64 + tx, NT * ncw);
     __syncthreads();
-    const int ltop = __builtin_amdgcn_readfirstlane(W.hgrp[(blockIdx.x * nsb) / SORT_GROUP]);       // layers 1 .. ltop (uniform over the workgroup)
     const size_t qstride = (size_t)nlay * ncb;
     const unsigned *__restrict__ sC = W.scr[S_CODE] + (size_t)quad * qstride * CODE_WORDS;
     const unsigned *__restrict__ sCt = W.scr[S_CODET] + (size_t)quad * qstride * CODE_WORDS;
@@ -4373,7 +4404,9 @@ __global__ __launch_bounds__(64 * N1_WAVES) void k_n1(DevTables T, Workspace W, 
 //           eight bytes per lane, the slabs cost a third more - sixteen cache lines per access instead of four -, scattered to the
 //           position's column the outputs 60 %; and the 256-column rows make this kernel 7 % faster than its 64-column predecessor
 //           where no column moves at all.)
-//           clear_from_total: a cloud-free call, the clear-sky stream equals the total-sky stream.  Only bands in [istart, iend] were
+//           clear_from_total: a cloud-free call, the clear-sky stream equals the total-sky stream.  clear_groups: so it does in the
+//           cloud-free block groups of a cloudy call, whose clear-sky sums are formed here from copies of the total ones - the values
+//           k_sweepc<., 2> wrote twice before.  Only bands in [istart, iend] were
 //           swept: the groups hold exactly those.
 // ------------------------------------------------------------------------------------------------
 constexpr int FLUX_LV = 8, FLUX_TY = 4;         // levels of a workgroup (+ 1: the level above, summed again), threads per column
@@ -4381,7 +4414,7 @@ static_assert(COLSORT_WIN * FLUX_TY <= 1024, "k_flux: a window x FLUX_TY threads
 constexpr int FLUX_LDS_BYTES = (FLUX_LV + 1) * 4 * COLSORT_WIN * 8;       // 72 KB: two workgroups per CU
 template <bool IDRV>
 __global__ __launch_bounds__(COLSORT_WIN * FLUX_TY) void k_flux(DevTables T, Workspace W, FluxOut out, const double *pz, int ncol, int col0, int nct,
-                                                                int clear_from_total, int ngroups, unsigned long long gsz)
+                                                                int clear_from_total, int ngroups, unsigned long long gsz, int clear_groups)
 {   // gsz: slabs per group, a nibble each (1, or - SweepArgs::split - the group's bands: added first, in their order, like the group's workgroup does)
     constexpr int NV = 4, NL = (FLUX_LV + FLUX_TY) / FLUX_TY;      // values that change places at a time; levels per thread
     extern __shared__ __align__(16) unsigned char smem_f[];
@@ -4396,7 +4429,8 @@ __global__ __launch_bounds__(COLSORT_WIN * FLUX_TY) void k_flux(DevTables T, Wor
     // Partials arrive summed per group of bands.  Downward at and above the hand-off level of the position's 64-column block, and everywhere
     // in a cloud-free call, the clear-sky stream equals the total one and one value was written (k_sweepc); below, and upward, two.
     const int ltop = (son && !clear_from_total) ? W.hblk[slot >> 6] : 0;       // (uniform over the wave)
-    const bool up1 = clear_from_total != 0;
+    // (clear_groups - SweepArgs::cfree: a block whose hand-off level is 0 was swept by k_sweepc<., 0>, one value upward as well)
+    const bool up1 = clear_from_total != 0 || (clear_groups != 0 && son && ltop == 0);
 #pragma unroll
     for (int k = 0; k < NL; k++) {          // (unrolled: kdu / kduc stay in registers)
         const int lc = ty + k * FLUX_TY, lev = lev0 + lc;

@@ -539,6 +539,47 @@ int rrtmg_lw_hip_gas_optics_device_as(const rrtmg_lw_hip_array_form *form, int n
     const void *ccl4vmr, const void *emis,
     void *taug, void *fracs, void *planklay, void *planklev, void *plankbnd, void *dplankbnd_dt, void *stream);
 
+/* ---- Surface-temperature adjustment of idrv = 1 results -----------------------------------------------------------------------------
+ * With idrv = 1 the rrtmg_lw entries return duflx_dt and duflxc_dt, "to approximate adjustments to the upward flux profile caused only by
+ * a change in surface temperature between full radiation calls" (src/rrtmg_lw_rad.nomcica.f90:161-171).  These entries apply them, as
+ * the reference's column driver does (src/rrtmg_lw.1col.f90:582-610): a host that calls radiation every N-th step keeps the fluxes of
+ * that call and, on each step between, hands them over with its current surface temperature.  In float64, per column i and level k:
+ *     uflx_adj(k) = uflx(k) + duflx_dt(k) * dtsfc(i)        (the product rounded, then the sum: no fused multiply-add)
+ *     net(k)      = uflx_adj(k) - dflx(k)
+ *     hr_adj(l)   = heatfac * (net(l) - net(l+1)) / (plev(l) - plev(l+1)),   l = 0 .. nlay-1
+ * and the same for the clear-sky set (uflxc, dflxc, duflxc_dt -> uflxc_adj, hrc_adj).  dtsfc (ncol) is the current surface temperature
+ * minus the tsfc of the radiation call that produced the fluxes; heatfac is that of the initialisation (cpdair).  The inputs are always
+ * the STORED, unadjusted fluxes of that call: an adjustment is not cumulative.  Downward fluxes do not change and are not output.  With
+ * dtsfc = 0 the outputs are the solver's own uflx and hr, bit for bit (its heating rate is formed by the same expression).
+ * Arrays: plev and the flux arrays (ncol,nlay+1), hr_adj and hrc_adj (ncol,nlay), dtsfc (ncol); columns fastest, level 0 at the surface.
+ * The five clear-sky arrays are all NULL - then none is read or written - or all set.  No output may overlap an input or another output
+ * (the address ranges are compared).  RRTMG_LW_HIP_EARG: a null required array, some but not all of the clear-sky arrays, an overlap,
+ * dimensions outside the limits of the other entries; nothing is written then.
+ *   rrtmg_lw_hip_adjust_tsfc            HOST pointers.  Takes the entry lock, splits the columns over the devices of
+ *                                       rrtmg_lw_hip_init_devices and moves them through the pipeline of the other host entries
+ *                                       (registered arrays are copied from where they lie).  The results do not depend on the batch
+ *                                       size or on the number of devices (bit for bit).
+ *   rrtmg_lw_hip_adjust_tsfc_device     DEVICE pointers.  One kernel launch on `stream`, on the state of the device `plev` lives on; no
+ *                                       workspace, no synchronisation; errors through rrtmg_lw_hip_check(stream) like the other device
+ *                                       entries.
+ *   rrtmg_lw_hip_adjust_tsfc_device_as  the same for arrays in the caller's form (rrtmg_lw_hip_array_form above, all three fields; with
+ *                                       real_bytes = 4 every array is float32, dtsfc included: inputs widened, the arithmetic above in
+ *                                       float64, outputs rounded, (float)x).  The kernel reads and writes the caller's arrays where
+ *                                       they lie - nothing is staged or converted.  {8, 0, 0} forwards to the plain device entry; form
+ *                                       errors as in the other *_as entries. */
+int rrtmg_lw_hip_adjust_tsfc(int ncol, int nlay, const double *plev, const double *dtsfc,
+    const double *uflx, const double *dflx, const double *duflx_dt,
+    const double *uflxc, const double *dflxc, const double *duflxc_dt,
+    double *uflx_adj, double *hr_adj, double *uflxc_adj, double *hrc_adj);
+int rrtmg_lw_hip_adjust_tsfc_device(int ncol, int nlay, const double *plev, const double *dtsfc,
+    const double *uflx, const double *dflx, const double *duflx_dt,
+    const double *uflxc, const double *dflxc, const double *duflxc_dt,
+    double *uflx_adj, double *hr_adj, double *uflxc_adj, double *hrc_adj, void *stream);
+int rrtmg_lw_hip_adjust_tsfc_device_as(const rrtmg_lw_hip_array_form *form, int ncol, int nlay, const void *plev, const void *dtsfc,
+    const void *uflx, const void *dflx, const void *duflx_dt,
+    const void *uflxc, const void *dflxc, const void *duflxc_dt,
+    void *uflx_adj, void *hr_adj, void *uflxc_adj, void *hrc_adj, void *stream);
+
 /* PMC calibration: one kernel that reads `bytes` and writes `bytes` with 16 B per lane (known HBM traffic), so that a
  * rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE pass can fix the counters' unit and scale in the same session. */
 int rrtmg_lw_hip_calibrate_stream(long long bytes);

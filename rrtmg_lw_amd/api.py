@@ -524,6 +524,66 @@ def gas_optics_columns(cols, idrv=0, out=None):
 
 
 # ---------------------------------------------------------------------------------------------------
+# Surface-temperature adjustment of idrv = 1 results (include/rrtmg_lw_hip.h, "Surface-temperature adjustment")
+# ---------------------------------------------------------------------------------------------------
+_ADJUST_IN = ("plev", "dtsfc", "uflx", "dflx", "duflx_dt", "uflxc", "dflxc", "duflxc_dt")
+_ADJUST_OUT = ("uflx_adj", "hr_adj", "uflxc_adj", "hrc_adj")
+_ADJUST_CLEAR = ("uflxc", "dflxc", "duflxc_dt", "uflxc_adj", "hrc_adj")
+# the argument lists of the three C entries as this module passes them (tests/test_adjust_tsfc.py holds them against the header)
+_ADJUST_ARGTYPES = {
+    "rrtmg_lw_hip_adjust_tsfc": [C.c_int, C.c_int] + [_dp] * 12,
+    "rrtmg_lw_hip_adjust_tsfc_device": [C.c_int, C.c_int] + [C.c_void_p] * 13,
+    "rrtmg_lw_hip_adjust_tsfc_device_as": [C.POINTER(_ArrayFormC), C.c_int, C.c_int] + [C.c_void_p] * 13,
+}
+
+
+def _adjust_fn(name):
+    fn = getattr(lib(), name)
+    fn.argtypes, fn.restype = _ADJUST_ARGTYPES[name], C.c_int
+    return fn
+
+
+def adjust_tsfc(ncol, nlay, plev, dtsfc, uflx, dflx, duflx_dt, uflxc=None, dflxc=None, duflxc_dt=None, out=None):
+    """The fluxes and heating rates of an idrv = 1 radiation call adjusted to a changed surface temperature (rrtmg_lw_hip_adjust_tsfc;
+    reference src/rrtmg_lw.1col.f90:582-610), host arrays: uflx_adj = uflx + duflx_dt * dtsfc, hr_adj from the new net flux.  dtsfc
+    (ncol,) is the current surface temperature minus the tsfc of that call; uflx, dflx, duflx_dt are its stored, unadjusted results.
+    The clear-sky arrays uflxc, dflxc, duflxc_dt are all given or all None.  Returns dict(uflx_adj (ncol, nlay+1), hr_adj (ncol, nlay)
+    [, uflxc_adj, hrc_adj]); `out` may hold preallocated (e.g. host_register'ed) Fortran-ordered arrays of those names."""
+    ncol, nlay = int(ncol), int(nlay)
+    clear = (uflxc, dflxc, duflxc_dt)
+    if any(x is None for x in clear) and not all(x is None for x in clear):
+        raise ValueError("adjust_tsfc: uflxc, dflxc and duflxc_dt must be all None or all arrays")
+    has_c = clear[0] is not None
+    lev, lay = (ncol, nlay + 1), (ncol, nlay)
+    null = C.cast(None, _dp)
+    ins = [_f(plev, lev), _f(dtsfc, (ncol,))] + [_f(x, lev) for x in (uflx, dflx, duflx_dt)] + ([_f(x, lev) for x in clear] if has_c else [])
+    out = {} if out is None else out
+    shapes = dict(uflx_adj=lev, hr_adj=lay, uflxc_adj=lev, hrc_adj=lay)
+    names = _ADJUST_OUT if has_c else _ADJUST_OUT[:2]
+    for k in names:
+        if k not in out:
+            out[k] = np.empty(shapes[k], order="F")
+        _out_ok(out[k], shapes[k], k)
+    o = [_p(out[k]) if k in names else null for k in _ADJUST_OUT]
+    _check(_adjust_fn("rrtmg_lw_hip_adjust_tsfc")(ncol, nlay, *[_p(x) for x in ins], *([null] * 3 if not has_c else []), *o))
+    return out
+
+
+def adjust_tsfc_device(arrays, out, stream=None, form=None):
+    """Device-resident adjustment (rrtmg_lw_hip_adjust_tsfc_device): `arrays` holds ncol, nlay and the torch CUDA tensors plev, dtsfc,
+    uflx, dflx, duflx_dt and - all or none - uflxc, dflxc, duflxc_dt, laid out column fastest as for rrtmg_lw_device; `out` the
+    preallocated tensors uflx_adj, hr_adj and, with the clear-sky inputs, uflxc_adj, hrc_adj.  One kernel launch on `stream`, no
+    synchronisation: check(stream) before the results are read.  form: an rrtmg_lw_amd.arrays.ArrayForm - every tensor then lies in
+    that form (dtsfc in its precision) and is read and written where it lies (rrtmg_lw_hip_adjust_tsfc_device_as)."""
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    args = [int(arrays["ncol"]), int(arrays["nlay"])] + [ptr(arrays.get(k)) for k in _ADJUST_IN] + [ptr(out.get(k)) for k in _ADJUST_OUT]
+    if form is not None:
+        _check(_adjust_fn("rrtmg_lw_hip_adjust_tsfc_device_as")(_form_arg(form, arrays, out, _ADJUST_IN, _ADJUST_OUT), *args, C.c_void_p(stream or 0)))
+        return
+    _check(_adjust_fn("rrtmg_lw_hip_adjust_tsfc_device")(*args, C.c_void_p(stream or 0)))
+
+
+# ---------------------------------------------------------------------------------------------------
 # McICA flavour: reference src/rrtmg_lw_rad.f90:99-108, src/mcica_subcol_gen_lw.f90:68,183
 # ---------------------------------------------------------------------------------------------------
 def _out_arrays(ncol, nlay, idrv):

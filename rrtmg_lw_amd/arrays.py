@@ -5,6 +5,7 @@ column index fastest, vertical index 0 at the surface, logical shapes as the For
 
     play, tlay, the gases, cldfr, cicewp, cliqwp, reice, reliq, alpha, hr, hrc      (ncol, nlay)
     plev, tlev, uflx, dflx, uflxc, dflxc, duflx_dt, duflxc_dt                       (ncol, nlay+1)
+    uflx_adj, uflxc_adj (ncol, nlay+1), hr_adj, hrc_adj (ncol, nlay), dtsfc (ncol,)   the surface-temperature adjustment (api.adjust_tsfc)
     emis, plankbnd, dplankbnd_dt                                                    (ncol, 16)
     taucld                                                                          (16, ncol, nlay)
     tauaer, planklay                                                                (ncol, nlay, 16)
@@ -32,12 +33,12 @@ import numpy as np
 NBND = 16
 
 LAYER_ARRAYS = ("play", "tlay", "h2ovmr", "o3vmr", "co2vmr", "ch4vmr", "n2ovmr", "o2vmr", "cfc11vmr", "cfc12vmr", "cfc22vmr",
-                "ccl4vmr", "cldfr", "cicewp", "cliqwp", "reice", "reliq", "alpha", "hr", "hrc")
-LEVEL_ARRAYS = ("plev", "tlev", "uflx", "dflx", "uflxc", "dflxc", "duflx_dt", "duflxc_dt")
+                "ccl4vmr", "cldfr", "cicewp", "cliqwp", "reice", "reliq", "alpha", "hr", "hrc", "hr_adj", "hrc_adj")
+LEVEL_ARRAYS = ("plev", "tlev", "uflx", "dflx", "uflxc", "dflxc", "duflx_dt", "duflxc_dt", "uflx_adj", "uflxc_adj")
 BAND_ARRAYS = ("emis", "plankbnd", "dplankbnd_dt")                      # (ncol, 16): no vertical axis
 LAYER_X_ARRAYS = ("tauaer", "planklay", "taug", "fracs")                # (ncol, nlay, 16 | NG)
 LEVEL_X_ARRAYS = ("planklev",)                                          # (ncol, nlay+1, 16)
-COLUMN_ARRAYS = ("tsfc",)
+COLUMN_ARRAYS = ("tsfc", "dtsfc")
 ALL_ARRAYS = LAYER_ARRAYS + LEVEL_ARRAYS + BAND_ARRAYS + LAYER_X_ARRAYS + LEVEL_X_ARRAYS + COLUMN_ARRAYS + ("taucld",)
 
 

@@ -3064,7 +3064,8 @@ int rrtmg_lw_hip_calibrate_stream(long long bytes)
     if (hipMalloc(&b, n * 16) != hipSuccess) { (void)hipFree(a); return fail(RRTMG_LW_HIP_EHIP, "hipMalloc failed"); }
     (void)hipMemset(a, 0, n * 16);
     (void)hipDeviceSynchronize();
-    hipLaunchKernelGGL(k_calibrate, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, G.stream, (const double2 *)a, (double2 *)b, n);
+    // (through the launch wrapper: under rrtmg_lw_hip_profile_begin / _end the copy's own time is the yardstick of tools/adjust_tsfc_timing.py)
+    LAUNCH("k_calibrate", k_calibrate, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), G.stream, (const double2 *)a, (double2 *)b, n);
     hipError_t e = hipStreamSynchronize(G.stream);
     (void)hipFree(a);
     (void)hipFree(b);
@@ -3884,9 +3885,155 @@ int gas_optics_device_as(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, i
     return rc;
 }
 
+// ---- surface-temperature adjustment of idrv = 1 results (rrtmg_lw_hip_adjust_tsfc*, k_adjust_cf / k_adjust_lf) -------------------------
+// The arrays of a call as the entries receive them; the clear-sky five all null or all set.
+struct AdjustIn { const void *plev, *dtsfc, *uflx, *dflx, *duflx_dt, *uflxc, *dflxc, *duflxc_dt; };
+struct AdjustOut { void *uflx_adj, *hr_adj, *uflxc_adj, *hrc_adj; };
+
+// what the three entries check before anything is enqueued; *clear: the clear-sky set is there
+int check_adjust(int ncol, int nlay, int real_bytes, const AdjustIn &in, const AdjustOut &o, bool *clear)
+{
+    if (int rc = check_common(ncol, nlay)) return rc;
+    if (!in.plev || !in.dtsfc || !in.uflx || !in.dflx || !in.duflx_dt) return fail(RRTMG_LW_HIP_EARG, "adjust_tsfc: null input array");
+    if (!o.uflx_adj || !o.hr_adj) return fail(RRTMG_LW_HIP_EARG, "adjust_tsfc: null output array");
+    const int nc = (in.uflxc != nullptr) + (in.dflxc != nullptr) + (in.duflxc_dt != nullptr) + (o.uflxc_adj != nullptr) + (o.hrc_adj != nullptr);
+    if (nc != 0 && nc != 5)
+        return fail(RRTMG_LW_HIP_EARG, "adjust_tsfc: uflxc, dflxc, duflxc_dt, uflxc_adj and hrc_adj must be all null or all set (%d of 5 are set)", nc);
+    *clear = nc == 5;
+    // no output may share a byte with an input or with another output
+    const size_t n = (size_t)ncol, lev = n * ((size_t)nlay + 1) * (size_t)real_bytes, lay = n * (size_t)nlay * (size_t)real_bytes;
+    struct Range { const char *name; const void *p; size_t bytes; };
+    const Range ins[] = {{"plev", in.plev, lev}, {"dtsfc", in.dtsfc, n * (size_t)real_bytes}, {"uflx", in.uflx, lev}, {"dflx", in.dflx, lev},
+                         {"duflx_dt", in.duflx_dt, lev}, {"uflxc", in.uflxc, lev}, {"dflxc", in.dflxc, lev}, {"duflxc_dt", in.duflxc_dt, lev}};
+    const Range outs[] = {{"uflx_adj", o.uflx_adj, lev}, {"hr_adj", o.hr_adj, lay}, {"uflxc_adj", o.uflxc_adj, lev}, {"hrc_adj", o.hrc_adj, lay}};
+    const auto meet = [](const Range &x, const Range &y) {
+        const uintptr_t a = (uintptr_t)x.p, b = (uintptr_t)y.p;
+        return x.p && y.p && a < b + y.bytes && b < a + x.bytes;
+    };
+    for (size_t k = 0; k < 4; k++) {
+        for (const Range &i : ins)
+            if (meet(outs[k], i)) return fail(RRTMG_LW_HIP_EARG, "adjust_tsfc: output %s overlaps input %s", outs[k].name, i.name);
+        for (size_t j = 0; j < k; j++)
+            if (meet(outs[k], outs[j])) return fail(RRTMG_LW_HIP_EARG, "adjust_tsfc: output %s overlaps output %s", outs[k].name, outs[j].name);
+    }
+    return 0;
+}
+
+template <class R, bool TOP, int NS>
+void adjust_launch_form(hipStream_t s, bool layer_fastest, const AdjustArgs &a, bool aligned)
+{
+    const size_t n = (size_t)a.ncol;
+    if (layer_fastest) {
+        constexpr size_t V = 16 / sizeof(R);
+        const size_t threads = (n * ((size_t)a.nlay + 1) + V - 1) / V;
+        LAUNCH("k_adjust_lf", (k_adjust_lf<R, TOP, NS>), dim3((unsigned)((threads + 255) / 256)), dim3(256), s, a);
+        return;
+    }
+    // 16-byte accesses where every row of every array starts on a 16-byte boundary
+    constexpr size_t V = 16 / sizeof(R);
+    const bool wide = aligned && n % V == 0;
+    const size_t threads = wide ? n / V : n;
+    // a small call is spread over the chip along the vertical: chunks of at least 8 layers until ~2^18 threads run
+    AdjustArgs b = a;
+    while (b.chunk > 8 && threads * (size_t)((a.nlay + b.chunk - 1) / b.chunk) < ((size_t)1 << 18)) b.chunk = (b.chunk + 1) / 2;
+    const dim3 grid((unsigned)((threads + 255) / 256), (unsigned)((a.nlay + b.chunk - 1) / b.chunk));
+    if (wide) LAUNCH("k_adjust_cf", (k_adjust_cf<R, (int)V, TOP, NS>), grid, dim3(256), s, b);
+    else LAUNCH("k_adjust_cf", (k_adjust_cf<R, 1, TOP, NS>), grid, dim3(256), s, b);
+}
+
+// one launch over ncol columns of arrays that are ncol columns wide, in the form f, on stream s
+int adjust_launch(hipStream_t s, const rrtmg_lw_hip_array_form &f, int ncol, int nlay, const AdjustIn &in, const AdjustOut &o, bool clear)
+{
+    AdjustArgs a{};
+    a.plev = in.plev; a.dtsfc = in.dtsfc;
+    a.s[0] = AdjustSet{in.uflx, in.dflx, in.duflx_dt, o.uflx_adj, o.hr_adj};
+    if (clear) a.s[1] = AdjustSet{in.uflxc, in.dflxc, in.duflxc_dt, o.uflxc_adj, o.hrc_adj};
+    a.ncol = (unsigned long long)ncol; a.nlay = nlay; a.chunk = nlay;
+    a.heatfac = G.H.heatfac;
+    // column-fastest: rows of ncol values (hr too), the wide path also asks ncol to be a multiple of the vector; layer-fastest: the
+    // level arrays as one run from their first byte (dtsfc and hr are accessed value by value)
+    const void *all[] = {in.plev, in.dtsfc, in.uflx, in.dflx, in.duflx_dt, o.uflx_adj, o.hr_adj, in.uflxc, in.dflxc, in.duflxc_dt, o.uflxc_adj, o.hrc_adj};
+    bool aligned = true;
+    for (const void *p : all) aligned = aligned && ((uintptr_t)p & 15u) == 0;
+    a.vec = aligned ? 1 : 0;
+    const bool lf = f.layer_fastest != 0, top = f.top_first != 0;
+#define ADJUST_GO(R)                                                                                     \
+    do {                                                                                                 \
+        if (top) { if (clear) adjust_launch_form<R, true, 2>(s, lf, a, aligned); else adjust_launch_form<R, true, 1>(s, lf, a, aligned); } \
+        else { if (clear) adjust_launch_form<R, false, 2>(s, lf, a, aligned); else adjust_launch_form<R, false, 1>(s, lf, a, aligned); } \
+    } while (0)
+    if (f.real_bytes == 4) ADJUST_GO(float); else ADJUST_GO(double);
+#undef ADJUST_GO
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "k_adjust launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int adjust_device(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, const AdjustIn &in, const AdjustOut &o, void *stream)
+{
+    ENTRY_LOCK_FOR(in.plev);
+    bool clear = false;
+    if (int rc = check_adjust(ncol, nlay, f.real_bytes, in, o, &clear)) return rc;
+    return adjust_launch((hipStream_t)stream, f, ncol, nlay, in, o, clear);
+}
+
+// columns [c0, c1) of a host-pointer call on the calling thread's current device state (the fan-out's worker); no lock taken
+int adjust_host_range(int ncol, int c0, int c1, int nlay, const AdjustIn &in, const AdjustOut &o, bool clear)
+{
+    const size_t L = (size_t)nlay;
+    const auto d = [](const void *p) { return static_cast<const double *>(p); };
+    std::vector<HostIn> ins = {HostIn{d(in.plev), 1, L + 1, nullptr}, HostIn{d(in.dtsfc), 1, 1, nullptr}, HostIn{d(in.uflx), 1, L + 1, nullptr},
+                               HostIn{d(in.dflx), 1, L + 1, nullptr}, HostIn{d(in.duflx_dt), 1, L + 1, nullptr}};
+    std::vector<HostOut> outs = {HostOut{static_cast<double *>(o.uflx_adj), L + 1, nullptr, true}, HostOut{static_cast<double *>(o.hr_adj), L, nullptr, true}};
+    if (clear) {
+        for (const void *p : {in.uflxc, in.dflxc, in.duflxc_dt}) ins.push_back(HostIn{d(p), 1, L + 1, nullptr});
+        outs.push_back(HostOut{static_cast<double *>(o.uflxc_adj), L + 1, nullptr, true});
+        outs.push_back(HostOut{static_cast<double *>(o.hrc_adj), L, nullptr, true});
+    }
+    const int nbmax = balanced_batch(c1 - c0, std::min(eff_batch(nlay), HOST_BATCH));
+    const rrtmg_lw_hip_array_form ref{8, 0, 0};
+    auto body = [&](hipStream_t s, int nb, int, std::vector<HostIn> &i_, std::vector<HostOut> &o_) -> int {
+        const AdjustIn si{i_[0].d, i_[1].d, i_[2].d, i_[3].d, i_[4].d, clear ? i_[5].d : nullptr, clear ? i_[6].d : nullptr, clear ? i_[7].d : nullptr};
+        const AdjustOut so{o_[0].d, o_[1].d, clear ? o_[2].d : nullptr, clear ? o_[3].d : nullptr};
+        return adjust_launch(s, ref, nb, nlay, si, so, clear);
+    };
+    return host_pipeline(ncol, c0, c1, nbmax, ins, outs, body);
+}
+
 }   // namespace
 
 extern "C" {
+
+int rrtmg_lw_hip_adjust_tsfc(int ncol, int nlay, const double *plev, const double *dtsfc,
+    const double *uflx, const double *dflx, const double *duflx_dt, const double *uflxc, const double *dflxc, const double *duflxc_dt,
+    double *uflx_adj, double *hr_adj, double *uflxc_adj, double *hrc_adj)
+{
+    ENTRY_LOCK;
+    const AdjustIn in{plev, dtsfc, uflx, dflx, duflx_dt, uflxc, dflxc, duflxc_dt};
+    const AdjustOut o{uflx_adj, hr_adj, uflxc_adj, hrc_adj};
+    bool clear = false;
+    if (int rc = check_adjust(ncol, nlay, 8, in, o, &clear)) return rc;
+    return fan_out(ncol, [&](int c0, int c1) { return adjust_host_range(ncol, c0, c1, nlay, in, o, clear); });
+}
+
+int rrtmg_lw_hip_adjust_tsfc_device(int ncol, int nlay, const double *plev, const double *dtsfc,
+    const double *uflx, const double *dflx, const double *duflx_dt, const double *uflxc, const double *dflxc, const double *duflxc_dt,
+    double *uflx_adj, double *hr_adj, double *uflxc_adj, double *hrc_adj, void *stream)
+{
+    return adjust_device({8, 0, 0}, ncol, nlay, {plev, dtsfc, uflx, dflx, duflx_dt, uflxc, dflxc, duflxc_dt}, {uflx_adj, hr_adj, uflxc_adj, hrc_adj}, stream);
+}
+
+int rrtmg_lw_hip_adjust_tsfc_device_as(const rrtmg_lw_hip_array_form *form, int ncol, int nlay, const void *plev, const void *dtsfc,
+    const void *uflx, const void *dflx, const void *duflx_dt, const void *uflxc, const void *dflxc, const void *duflxc_dt,
+    void *uflx_adj, void *hr_adj, void *uflxc_adj, void *hrc_adj, void *stream)
+{
+    bool plain = false;
+    if (int rc = form_check(form, &plain)) return rc;
+    if (plain) return rrtmg_lw_hip_adjust_tsfc_device(ncol, nlay, (const double *)plev, (const double *)dtsfc, (const double *)uflx, (const double *)dflx,
+                                                      (const double *)duflx_dt, (const double *)uflxc, (const double *)dflxc, (const double *)duflxc_dt,
+                                                      (double *)uflx_adj, (double *)hr_adj, (double *)uflxc_adj, (double *)hrc_adj, stream);
+    return adjust_device(*form, ncol, nlay, {plev, dtsfc, uflx, dflx, duflx_dt, uflxc, dflxc, duflxc_dt}, {uflx_adj, hr_adj, uflxc_adj, hrc_adj}, stream);
+}
 
 #define AS_(name) (const double *)name
 #define GCM_PARAMS_AS                                                                                           \

@@ -4510,6 +4510,184 @@ __global__ __launch_bounds__(256) void k_calibrate(const double2 *__restrict__ i
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_adjust_cf / k_adjust_lf : rrtmg_lw_hip_adjust_tsfc* - the column driver's idrv = 1 adjustment (src/rrtmg_lw.1col.f90:587-605) of
+//               the upward fluxes and heating rates of a stored radiation call to a changed surface temperature:
+//                   u'(k) = uflx(k) + duflx_dt(k) * dtsfc        (multiply rounded, add rounded: never fused - adjust_up)
+//                   hr(l) = heatfac * ((u'(l) - dflx(l)) - (u'(l+1) - dflx(l+1))) / (plev(l) - plev(l+1))       - k_flux's expression
+//               in float64 on float64 or widened float32 arrays, total sky and (NS = 2) clear sky.  Nothing but traffic - 6.4 KB per
+//               72-layer column -, so the kernels read and write the caller's arrays where they lie, in the caller's form (R: element
+//               type, TOP: vertical index 0 at the top of the atmosphere), every element once, lanes along the form's fastest index.
+//   k_adjust_cf   columns fastest.  A thread owns V consecutive columns (V x sizeof(R) = 16 bytes per access where every row of every
+//               array is 16-byte aligned, V = 1 otherwise) and walks the levels of its chunk (blockIdx.y) upward with the net flux and
+//               pressure of the level below in registers.  A chunk reads the level it ends at once more; the level belongs to the next
+//               chunk, which stores its u'.  The chunks only spread a small call over the chip: a large one walks whole columns.
+//   k_adjust_lf   levels fastest: the (ncol, nlay+1) arrays are walked as ONE run of ncol x (nlay+1) values, V per thread, whatever
+//               nlay + 1 is, so that every wave moves whole kilobytes.  The level above a thread's last value (below its first one
+//               with TOP) is the next thread's: a second, scalar load that hits L1.  hr is (ncol, nlay): its values lie at other
+//               offsets than the levels' - the run index minus the column (minus one with TOP) - and are stored one by one.
+// ------------------------------------------------------------------------------------------------
+struct AdjustSet { const void *u, *d, *du; void *ua, *hr; };
+struct AdjustArgs {
+    const void *plev, *dtsfc;
+    AdjustSet s[2];             // total sky, clear sky
+    unsigned long long ncol;    // columns, and the row length of column-fastest arrays
+    int nlay, chunk;            // chunk: layers per blockIdx.y (k_adjust_cf)
+    int vec;                    // k_adjust_lf: every level array starts on a 16-byte boundary
+    double heatfac;
+};
+template <class R, int V> struct AdjustVec { typedef R type __attribute__((ext_vector_type(V))); };
+// V values from p[at]: one access of V x sizeof(R) bytes (the caller has checked the alignment), or one value
+template <class R, int V>
+__device__ __forceinline__ void adjust_load(const void *p, size_t at, double (&x)[V])
+{
+    if constexpr (V == 1) x[0] = (double)static_cast<const R *>(p)[at];
+    else {
+        const typename AdjustVec<R, V>::type v = *reinterpret_cast<const typename AdjustVec<R, V>::type *>(static_cast<const R *>(p) + at);
+#pragma unroll
+        for (int j = 0; j < V; j++) x[j] = (double)v[j];
+    }
+}
+template <class R, int V>
+__device__ __forceinline__ void adjust_store(void *p, size_t at, const double (&x)[V])
+{
+    if constexpr (V == 1) static_cast<R *>(p)[at] = (R)x[0];
+    else {
+        typename AdjustVec<R, V>::type v;
+#pragma unroll
+        for (int j = 0; j < V; j++) v[j] = (R)x[j];
+        *reinterpret_cast<typename AdjustVec<R, V>::type *>(static_cast<R *>(p) + at) = v;
+    }
+}
+// u + du * dt with the product rounded before the sum.  Plain * and + under a contract-off pragma: __dmul_rn / __dadd_rn are inline
+// functions in this compiler's headers whose operations carry the build's contract flag, and the two were fused into one v_fma_f64.
+__device__ __forceinline__ double adjust_up(double u, double du, double dt)
+{
+#pragma clang fp contract(off)
+    const double prod = du * dt;
+    return u + prod;
+}
+
+template <class R, int V, bool TOP, int NS>
+__global__ __launch_bounds__(256) void k_adjust_cf(AdjustArgs a)
+{
+#pragma clang fp contract(off)
+    const size_t n = (size_t)a.ncol, c = ((size_t)blockIdx.x * 256 + threadIdx.x) * V;
+    if (c >= n) return;
+    const int nlay = a.nlay, k0 = (int)blockIdx.y * a.chunk, k1 = min(nlay, k0 + a.chunk);
+    double dt[V], pb[V], nb[NS][V];         // dtsfc; pressure and net fluxes of the level below
+    adjust_load<R, V>(a.dtsfc, c, dt);
+#pragma unroll 2
+    for (int k = k0; k <= k1; k++) {
+        const size_t at = (size_t)(TOP ? nlay - k : k) * n + c;
+        const bool mine = k < k1 || k1 == nlay;          // (the chunk's last level is the next chunk's first)
+        double p[V], net[NS][V];
+        adjust_load<R, V>(a.plev, at, p);
+#pragma unroll
+        for (int s = 0; s < NS; s++) {
+            double u[V], d[V], du[V];
+            adjust_load<R, V>(a.s[s].u, at, u);
+            adjust_load<R, V>(a.s[s].d, at, d);
+            adjust_load<R, V>(a.s[s].du, at, du);
+#pragma unroll
+            for (int j = 0; j < V; j++) { u[j] = adjust_up(u[j], du[j], dt[j]); net[s][j] = u[j] - d[j]; }
+            if (mine) adjust_store<R, V>(a.s[s].ua, at, u);
+        }
+        if (k > k0) {
+            const size_t ah = (size_t)(TOP ? nlay - k : k - 1) * n + c;          // layer k - 1
+#pragma unroll
+            for (int s = 0; s < NS; s++) {
+                double h[V];
+#pragma unroll
+                for (int j = 0; j < V; j++) h[j] = a.heatfac * (nb[s][j] - net[s][j]) / (pb[j] - p[j]);
+                adjust_store<R, V>(a.s[s].hr, ah, h);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < V; j++) {
+            pb[j] = p[j];
+#pragma unroll
+            for (int s = 0; s < NS; s++) nb[s][j] = net[s][j];
+        }
+    }
+}
+
+template <class R, bool TOP, int NS>
+__global__ __launch_bounds__(256) void k_adjust_lf(AdjustArgs a)
+{
+#pragma clang fp contract(off)
+    constexpr int V = 16 / (int)sizeof(R);
+    const size_t nlev = (size_t)a.nlay + 1, N = (size_t)a.ncol * nlev;
+    const size_t e0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * V;
+    if (e0 >= N) return;
+    const int nv = (int)min((size_t)V, N - e0);          // values of this thread (the run's last thread: fewer)
+    // column and vertical index of the first value
+    size_t i0;
+    if (N <= 0xffffffffull) i0 = (unsigned)e0 / (unsigned)nlev; else i0 = e0 / nlev;
+    const int kk0 = (int)(e0 - i0 * nlev);
+    // slots 1 .. V: the thread's values; slot 0 (TOP) or V + 1: the neighbour that holds the level above the last of them
+    double p[V + 2], net[NS][V + 2], dt[V + 2];
+    size_t col[V + 2];
+    int kk[V + 2];
+    bool on[V + 2];
+    {
+        size_t i = i0; int q = kk0;
+#pragma unroll
+        for (int j = 1; j <= V; j++) { col[j] = i; kk[j] = q; on[j] = j <= nv; if (++q == (int)nlev) { q = 0; i++; } }
+        // the neighbour counts only inside the same column; otherwise its slot is never used
+        if constexpr (TOP) { on[0] = kk0 > 0; col[0] = i0; kk[0] = kk0 - 1; on[V + 1] = false; col[V + 1] = 0; kk[V + 1] = 0; }
+        else { on[V + 1] = nv == V && kk[V] < (int)nlev - 1; col[V + 1] = col[V]; kk[V + 1] = kk[V] + 1; on[0] = false; col[0] = 0; kk[0] = 0; }
+    }
+    const bool wide = a.vec != 0 && nv == V;
+    constexpr int X = TOP ? 0 : V + 1;                   // the neighbour's slot
+#pragma unroll
+    for (int j = 0; j < V + 2; j++) dt[j] = on[j] ? (double)static_cast<const R *>(a.dtsfc)[col[j]] : 0.0;
+    auto load = [&](const void *src, double (&x)[V + 2]) {
+        if (wide) {
+            double v[V];
+            adjust_load<R, V>(src, e0, v);
+#pragma unroll
+            for (int j = 0; j < V; j++) x[j + 1] = v[j];
+        } else {
+#pragma unroll
+            for (int j = 1; j <= V; j++) x[j] = on[j] ? (double)static_cast<const R *>(src)[e0 + (size_t)(j - 1)] : 0.0;
+        }
+        x[TOP ? V + 1 : 0] = 0.0;
+        x[X] = on[X] ? (double)static_cast<const R *>(src)[TOP ? e0 - 1 : e0 + (size_t)V] : 0.0;
+    };
+    load(a.plev, p);
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+        double u[V + 2], d[V + 2], du[V + 2];
+        load(a.s[s].u, u);
+        load(a.s[s].d, d);
+        load(a.s[s].du, du);
+#pragma unroll
+        for (int j = 0; j < V + 2; j++) { u[j] = adjust_up(u[j], du[j], dt[j]); net[s][j] = u[j] - d[j]; }
+        if (wide) {
+            double v[V];
+#pragma unroll
+            for (int j = 0; j < V; j++) v[j] = u[j + 1];
+            adjust_store<R, V>(a.s[s].ua, e0, v);
+        } else {
+#pragma unroll
+            for (int j = 1; j <= V; j++) if (on[j]) static_cast<R *>(a.s[s].ua)[e0 + (size_t)(j - 1)] = (R)u[j];
+        }
+    }
+    // the layer above each of the thread's levels: between slot j (below) and slot j + 1, or j - 1 with TOP (above)
+#pragma unroll
+    for (int j = 1; j <= V; j++) {
+        constexpr int UP = TOP ? -1 : 1;
+        const bool has = on[j] && (TOP ? kk[j] > 0 : kk[j] < (int)nlev - 1);      // (the top level carries no layer; then slot j + UP is on)
+        if (has) {
+            const size_t ah = col[j] * (size_t)a.nlay + (size_t)(TOP ? kk[j] - 1 : kk[j]);
+#pragma unroll
+            for (int s = 0; s < NS; s++)
+                static_cast<R *>(a.s[s].hr)[ah] = (R)(a.heatfac * (net[s][j] - net[s][j + UP]) / (p[j] - p[j + UP]));
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_fill_rows : the host-pointer entries do not copy a row of an input array whose values are all the same for the columns of a batch
 //               (well-mixed gases, cloud and aerosol arrays outside the cloudy / dusty layers): entry blockIdx.y of the table (pinned host
 //               memory, written by the entry's host threads) names a run of such rows and the 8-byte pattern they hold.

@@ -16,6 +16,7 @@
 #include <functional>
 #include <map>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rrtmg_lw_hip.h"
@@ -151,6 +152,34 @@ struct CallDesc {
     bool spectral = false;                        // a *_spectral entry: uflxs and dflxs are required (check_spec)
 };
 CallDesc spectral(CallDesc d) { d.spectral = true; return d; }
+
+// The scalars of a batch below the entry points, as CallDesc and the array structs are for a call: what is fixed for the call, and the
+// columns [col0, col0 + nb) of arrays nct columns wide that one batch takes.  Whoever knows the values names them once; run_prep,
+// run_layer, run_sweep, run_batch and run_optics read them.
+struct Batch {
+    int nlay = 0, nct = 0;
+    int mode = 0;                                 // 0 clear, 1 rtrn, 2 rtrnmr, 3 rtrnmc (McICA)
+    int idrv = 0;
+    int istart = 1, iend = 16;                    // only bands in [istart, iend] (the column entries)
+    int inflag = 0, iceflag = 0, liqflag = 0;
+    const McIn *mc = nullptr;                     // mode 3: the sub-column arrays, or null when the sub-columns come from the generator's mask (Workspace::mask)
+    int nb = 0, col0 = 0;                         // this batch
+};
+// a GCM call's batches: all bands, arrays as wide as the call
+Batch batch_of(const CallDesc &d, int mode, const McIn *mc = nullptr)
+{
+    Batch b;
+    b.nlay = d.nlay; b.nct = d.ncol; b.mode = mode; b.idrv = d.idrv;
+    b.inflag = d.inflg; b.iceflag = d.iceflg; b.liqflag = d.liqflg; b.mc = mc;
+    return b;
+}
+// ... and one of nb columns of its own, staged at column 0 (the host-pointer entries, the array-form entries)
+Batch staged_batch(const CallDesc &d, int mode, int nb, const McIn *mc = nullptr)
+{
+    Batch b = batch_of(d, mode, mc);
+    b.nct = b.nb = nb;
+    return b;
+}
 
 // The arrays of a call by position: the inputs in rrtmg_lw's order (what "argument %d" of a refusal counts), the generator's alpha, the
 // outputs.  A list of a call's pointers (gcm_pointers, flux_pointers) is indexed by these and by nothing else.
@@ -371,91 +400,110 @@ hipEvent_t get_event()
         }                                                                                        \
     } while (0)
 
-// the sweeps stage the transmittance table in LDS: more than the 64 KB a kernel may use without asking
-template <int Q, bool SPEC = false>
-int sweepc_attr_one()
+// after the launches of a batch's stage
+int launches_ok()
 {
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 0, false, sweepc_nt(Q, 0, false), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));      // (cloud-free groups of a cloudy call: in the tuning build too)
-#ifndef RRLW_TUNE
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 0, true, sweepc_nt(Q, 0, true), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 2, true, sweepc_nt(Q, 2, true), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-#endif
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 1, false, sweepc_nt(Q, 1, false), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepc<Q, 2, false, sweepc_nt(Q, 2, false), SPEC>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
     return 0;
 }
-// the SPEC instantiations of the cloud-zone sweep (spectral outputs): every quad class, mode and d/dT flag
-template <int Q>
-int sweepz_attr_spec()
-{
-#ifndef RRLW_TUNE
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 1, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 3, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 4, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
+
+// ---- which kernel instantiations there are ------------------------------------------------------------------------------------------
+// The sweeps (k_sweepc, k_sweepz) and k_layer are templates over what a call's shape decides.  Per family ONE predicate says which
+// combinations are instantiated and ONE dispatcher turns the run-time choice into compile-time constants; raising the sweeps' LDS limit
+// (ensure_sweep_attrs) and launching them (run_sweep) both go through the dispatcher, so an instantiation is added in these two places.
+// Tuning builds (tools/build_variant.sh name -DRRLW_TUNE ...): only the kernels of the benchmark's default workload - GCM entry,
+// rtrn / rtrnmr, idrv = 0 - are instantiated (a quarter of the compile time); every other call shape is refused.
+#ifdef RRLW_TUNE
+constexpr bool TUNING = true;
+#else
+constexpr bool TUNING = false;
 #endif
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<Q, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    return 0;
+constexpr bool sweepc_exists(int, bool ddt) { return !ddt || !TUNING; }
+// Phase 1 (down, above the clouds) forms no d/dT terms: a call with idrv = 1 launches its plain instantiation.  (Its d/dT instantiation is
+// compiled all the same, as it always was - the launch macro named it in a branch that is never taken - and is left in the list so that the
+// code object keeps its kernels; `phase != 1` in sweepc_exists is all it takes to drop it.)
+constexpr bool sweepc_ddt(int phase, int idrv) { return idrv == 1 && phase != 1; }
+constexpr bool sweepz_exists(int mode, bool ddt) { return !TUNING || (mode == 2 && !ddt); }
+constexpr bool layer_exists(bool gcm, int cloud) { return TUNING ? gcm && cloud == 1 : gcm || cloud != 3; }     // the generator's mask: GCM entries only
+
+// f(std::integral_constant<int, V>) for the V among Vs that v equals; v = EVERY: for each of them in turn, until one fails
+constexpr int EVERY = -1;
+template <int... Vs, class F>
+int with_const(int v, F &&f)
+{
+    int rc = 0;
+    bool hit = false;
+    ((((v == Vs || v == EVERY) && rc == 0) ? (void)(hit = true, rc = f(std::integral_constant<int, Vs>{})) : (void)0), ...);
+    return hit ? rc : fail(RRTMG_LW_HIP_EARG, "internal: no kernel instantiation for %d", v);
 }
+
+// the names the profile records carry (State::ProfRec::name): "k_sweepc<4,1>", "k_sweepz<3,2,spec>"
+struct KernelName { char s[24]; };
+constexpr KernelName sweep_name(char family, int nq, int x, bool spec)
+{
+    KernelName n{};
+    int k = 0;
+    for (const char *p = "k_sweep"; *p; p++) n.s[k++] = *p;
+    n.s[k++] = family; n.s[k++] = '<'; n.s[k++] = (char)('0' + nq); n.s[k++] = ','; n.s[k++] = (char)('0' + x);
+    if (spec) for (const char *p = ",spec"; *p; p++) n.s[k++] = *p;
+    n.s[k++] = '>';
+    return n;
+}
+// what a launch needs of an instantiation: its name, threads (waves) per band, column sub-blocks per workgroup for a group of nbands, LDS
+template <int Q, int PH, bool I, bool SPEC>
+struct SweepC {
+    static constexpr KernelName name = sweep_name('c', Q, PH, SPEC);
+    static constexpr int nt = sweepc_nt(Q, PH, I);
+    static constexpr auto kernel() { return &k_sweepc<Q, PH, I, nt, SPEC>; }
+    static int nsb(int nbands) { return sweepc_nsb(Q, PH, I, nbands); }
+    static int lds_bytes(int wnb, int nsb) { return sweepc_lds_bytes(PH, I, wnb, nsb, nt); }
+};
+template <int Q, int M, bool I, bool SPEC>
+struct SweepZ {
+    static constexpr KernelName name = sweep_name('z', Q, M, SPEC);
+    static constexpr int nt = sweepz_nt(Q);
+    static constexpr auto kernel() { return &k_sweepz<Q, M, I, SPEC>; }
+    static int nsb(int nbands) { return sweepz_nsb(Q, nbands, I); }
+    static int lds_bytes(int wnb, int nsb) { return sweepz_lds_bytes(wnb, nsb, nt, I); }
+};
+// k_sweepc of bands of nq quads, phase 0 (a whole cloud-free column) / 1 (down, above the clouds) / 2 (up, above the clouds), with d/dT
+// terms or not, with spectral outputs or not: f(SweepC<..>{}).  EVERY for all four: f for every instantiation there is.
+template <class F>
+int sweepc_dispatch(int nq, int phase, int ddt, int spec, F &&f)
+{
+    return with_const<1, 2, 3, 4>(nq, [&](auto Q) { return with_const<0, 1, 2>(phase, [&](auto PH) {
+           return with_const<0, 1>(ddt, [&](auto I) { return with_const<0, 1>(spec, [&](auto S) {
+               if constexpr (sweepc_exists(decltype(PH)::value, decltype(I)::value != 0))
+                   return f(SweepC<decltype(Q)::value, decltype(PH)::value, decltype(I)::value != 0, decltype(S)::value != 0>{});
+               else return ddt == EVERY ? 0 : fail(RRTMG_LW_HIP_EARG, "internal: no such k_sweepc");
+           }); }); }); });
+}
+// k_sweepz (the cloud zone) of bands of nq quads, mode 1 rtrn / 2 rtrnmr / 3 rtrnmc with sub-column arrays / 4 rtrnmc with the generator's mask
+template <class F>
+int sweepz_dispatch(int nq, int mode, int ddt, int spec, F &&f)
+{
+    return with_const<1, 2, 3, 4>(nq, [&](auto Q) { return with_const<1, 2, 3, 4>(mode, [&](auto M) {
+           return with_const<0, 1>(ddt, [&](auto I) { return with_const<0, 1>(spec, [&](auto S) {
+               if constexpr (sweepz_exists(decltype(M)::value, decltype(I)::value != 0))
+                   return f(SweepZ<decltype(Q)::value, decltype(M)::value, decltype(I)::value != 0, decltype(S)::value != 0>{});
+               else return ddt == EVERY ? 0 : fail(RRTMG_LW_HIP_EARG, "internal: no such k_sweepz");
+           }); }); }); });
+}
+
+constexpr int N1_LDS_MAX = 160 * 1024;      // the prototype k_n1 (run_sweep, G.n1)
+// the sweeps stage the transmittance table in LDS: more than the 64 KB a kernel may use without asking.  Per device, once.
 int ensure_sweep_attrs()
 {
     if (G.sweep_attrs) return 0;
-#ifdef RRLW_TUNE
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-#else
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<1, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<1, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<1, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<1, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<2, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<2, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<2, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<3, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<3, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<3, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<3, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<3, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<3, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<4, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<4, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<4, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<4, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_sweepz<4, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX));
-#endif
-    if (int rc = sweepc_attr_one<1>()) return rc;
-    if (int rc = sweepc_attr_one<2>()) return rc;
-    if (int rc = sweepc_attr_one<3>()) return rc;
-    if (int rc = sweepc_attr_one<4>()) return rc;
-    if (int rc = sweepc_attr_one<1, true>()) return rc;
-    if (int rc = sweepc_attr_one<2, true>()) return rc;
-    if (int rc = sweepc_attr_one<3, true>()) return rc;
-    if (int rc = sweepc_attr_one<4, true>()) return rc;
-    if (int rc = sweepz_attr_spec<1>()) return rc;
-    if (int rc = sweepz_attr_spec<2>()) return rc;
-    if (int rc = sweepz_attr_spec<3>()) return rc;
-    if (int rc = sweepz_attr_spec<4>()) return rc;
+    const auto raise = [](auto K) { HIP_TRY(hipFuncSetAttribute((const void *)K.kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX)); return 0; };
+    if (int rc = sweepc_dispatch(EVERY, EVERY, EVERY, EVERY, raise)) return rc;
+    if (int rc = sweepz_dispatch(EVERY, EVERY, EVERY, EVERY, raise)) return rc;
     HIP_TRY(hipFuncSetAttribute((const void *)k_flux<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FLUX_LDS_BYTES));
     HIP_TRY(hipFuncSetAttribute((const void *)k_flux<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FLUX_LDS_BYTES));
+#ifndef RRLW_TUNE
+    HIP_TRY(hipFuncSetAttribute((const void *)k_n1<false>, hipFuncAttributeMaxDynamicSharedMemorySize, N1_LDS_MAX));      // (the prototype run_sweep launches when G.n1 is set)
+#endif
     G.sweep_attrs = true;
     return 0;
 }
@@ -698,120 +746,116 @@ bool use_colsort(bool gcm, int mode, int nb) { return g_colsort && gcm && (mode 
 // per-column part of one batch: k_colprep (+ k_cloudscan / k_cloudlay for rtrn / rtrnmr): it runs on the
 // auxiliary stream one batch ahead of the heavy kernels (run_pipelined).
 template <bool GCM>
-int run_prep(hipStream_t s, const Workspace &Wk, int nb, int col0, int nct, int mode, int idrv, int istart,
-             const GcmIn &g, const ColIn &c, int inflag, int iceflag, int liqflag, hipStream_t side = nullptr)
+int run_prep(hipStream_t s, const Workspace &Wk, const Batch &b, const GcmIn &g, const ColIn &c, hipStream_t side = nullptr)
 {
     // thread-per-column kernels: one wave per workgroup so that a batch (one wave per 64 columns) spreads over all 256 CUs
-    const dim3 cgrid1((nb + 63) / 64), cblock1(64);
+    const dim3 cgrid1((b.nb + 63) / 64), cblock1(64);
     if (Wk.perm) {
-        const dim3 wgrid((nb + COLSORT_WIN - 1) / COLSORT_WIN);
-        LAUNCH("k_colsort", (k_colsort<GCM>), wgrid, dim3(COLSORT_WIN, COLSORT_TY), s, Wk, g, c, nb, col0, nct, g_colsort_min, (int)((long long)Wk.nlay * g_colsort_clear / 100));
+        const dim3 wgrid((b.nb + COLSORT_WIN - 1) / COLSORT_WIN);
+        LAUNCH("k_colsort", (k_colsort<GCM>), wgrid, dim3(COLSORT_WIN, COLSORT_TY), s, Wk, g, c, b.nb, b.col0, b.nct, g_colsort_min, (int)((long long)Wk.nlay * g_colsort_clear / 100));
     }
     // (k_cloudscan needs nothing of k_colprep - k_cloudlay does: the secants - and both are one dependent walk over a column's layers: with a
     // side stream, a call that is a single batch, they run side by side: -30 us of its 0.5 ms)
-    const bool scan = mode == 1 || mode == 2, fork = scan && side && side != s;
+    const bool scan = b.mode == 1 || b.mode == 2, fork = scan && side && side != s;
     if (fork) {
         HIP_TRY(hipEventRecord(G.ev_fork, s));
         HIP_TRY(hipStreamWaitEvent(side, G.ev_fork, 0));
     }
-    LAUNCH("k_colprep", (k_colprep<GCM>), cgrid1, cblock1, fork ? side : s, G.D, Wk, g, c, nb, col0, nct, idrv, istart, scan ? 0 : 1);
+    LAUNCH("k_colprep", (k_colprep<GCM>), cgrid1, cblock1, fork ? side : s, G.D, Wk, g, c, b.nb, b.col0, b.nct, b.idrv, b.istart, scan ? 0 : 1);
     if (fork) HIP_TRY(hipEventRecord(G.ev_join, side));
     if (scan) {
-        LAUNCH("k_cloudscan", (k_cloudscan<GCM>), cgrid1, cblock1, s, Wk, g, c, nb, col0, nct, inflag, iceflag, liqflag, mode);
+        LAUNCH("k_cloudscan", (k_cloudscan<GCM>), cgrid1, cblock1, s, Wk, g, c, b.nb, b.col0, b.nct, b.inflag, b.iceflag, b.liqflag, b.mode);
         if (fork) HIP_TRY(hipStreamWaitEvent(s, G.ev_join, 0));
-        const dim3 lgrid((nb + BLOCK - 1) / BLOCK, Wk.nlay), lblock(BLOCK);
-        LAUNCH("k_cloudlay", (k_cloudlay<GCM>), lgrid, lblock, s, G.D, Wk, g, c, nb, col0, nct, mode, inflag, iceflag, liqflag);
-        LAUNCH("k_blocksort", k_blocksort, dim3(1), dim3(256), s, Wk, (nb + 63) / 64, one_sweep(nb, mode) ? 1 : 0);      // the blocks by cloud top, hand-off levels
+        const dim3 lgrid((b.nb + BLOCK - 1) / BLOCK, Wk.nlay), lblock(BLOCK);
+        LAUNCH("k_cloudlay", (k_cloudlay<GCM>), lgrid, lblock, s, G.D, Wk, g, c, b.nb, b.col0, b.nct, b.mode, b.inflag, b.iceflag, b.liqflag);
+        LAUNCH("k_blocksort", k_blocksort, dim3(1), dim3(256), s, Wk, (b.nb + 63) / 64, one_sweep(b.nb, b.mode) ? 1 : 0);      // the blocks by cloud top, hand-off levels
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launches_ok();
 }
 
-// the arguments of a k_layer / k_optics launch over nb columns
-LayerArgs layer_args(int nb, int col0, int nct, int nlay, int idrv, int istart, int iend, const double *tauaer)
+// the arguments of a k_layer / k_optics launch over a batch's columns
+LayerArgs layer_args(const Batch &b, const double *tauaer)
 {
     LayerArgs la;
-    la.ncol = nb; la.col0 = col0; la.nct = nct; la.idrv = idrv; la.istart = istart; la.iend = iend;
+    la.ncol = b.nb; la.col0 = b.col0; la.nct = b.nct; la.idrv = b.idrv; la.istart = b.istart; la.iend = b.iend;
     la.ktab_bytes = (int)(G.H.ktab.size() * 8);
     la.tauaer = tauaer;
-    const unsigned gx = (nb + LAYER_BLOCK - 1) / LAYER_BLOCK;
+    const unsigned gx = (b.nb + LAYER_BLOCK - 1) / LAYER_BLOCK;
     // A batch whose (window, layer) pairs do not fill the chip - 768 workgroups at three per CU - spreads the bands of a pair over two or
     // four workgroups (k_layer: LayerArgs::partmask): a workgroup's sixteen bands are a 100 us chain, and a small call waits for ONE round
     // of them.  The parts follow the staging passes (a workgroup stages only the passes it has a band of).
     const auto bits = [](std::initializer_list<int> bands) { unsigned m = 0; for (int b : bands) m |= 1u << (b - 1); return m; };
     const unsigned quarter[4] = {bits({1, 2, 11, 15, 6}), bits({8, 10, 14, 16, 12, 13}), bits({4, 9, 7}), bits({3, 5})};
-    const unsigned pairs_ = gx * (unsigned)nlay;
+    const unsigned pairs_ = gx * (unsigned)b.nlay;
     la.nparts = !g_layer_split ? 1 : (pairs_ * 4 <= 1152 ? 4 : (pairs_ * 2 <= 1152 ? 2 : 1));
     for (int p = 0; p < 4; p++) la.partmask[p] = la.nparts == 4 ? quarter[p] : (la.nparts == 2 && p < 2 ? (quarter[2 * p] | quarter[2 * p + 1]) : 0xffffu);
     return la;
 }
 
-// layer-local part of one batch (k_cloudmc, k_layer groups), everything device-resident.  mode: 0 clear, 1 rtrn, 2 rtrnmr,
-// 3 rtrnmc (McICA; `mc` = the sub-column arrays, or null when the sub-columns come from the generator's mask in Wk.mask)
+// layer-local part of one batch (k_cloudmc, k_layer), everything device-resident
 template <bool GCM>
-int run_layer(hipStream_t s, const Workspace &Wk, int nb, int col0, int nct, int nlay, int mode, int idrv, int istart, int iend,
-              const GcmIn &g, const ColIn &c, int inflag, int iceflag, int liqflag, const McIn *mc = nullptr)
+int run_layer(hipStream_t s, const Workspace &Wk, const Batch &b, const GcmIn &g, const ColIn &c)
 {
     const dim3 block(BLOCK);
-    if (mode == 3) {
-        const dim3 cgrid((nb + BLOCK - 1) / BLOCK, nlay);
-        if (mc) LAUNCH("k_cloudmc<arrays>", (k_cloudmc<false>), cgrid, block, s, G.D, Wk, *mc, g, nb, col0, nct, inflag, iceflag, liqflag);
-        else LAUNCH("k_cloudmc<mask>", (k_cloudmc<true>), cgrid, block, s, G.D, Wk, McIn{}, g, nb, col0, nct, inflag, iceflag, liqflag);
-        LAUNCH("k_blocksort", k_blocksort, dim3(1), dim3(256), s, Wk, (nb + 63) / 64, one_sweep(nb, mode) ? 1 : 0);
+    if (b.mode == 3) {
+        const dim3 cgrid((b.nb + BLOCK - 1) / BLOCK, b.nlay);
+        if (b.mc) LAUNCH("k_cloudmc<arrays>", (k_cloudmc<false>), cgrid, block, s, G.D, Wk, *b.mc, g, b.nb, b.col0, b.nct, b.inflag, b.iceflag, b.liqflag);
+        else LAUNCH("k_cloudmc<mask>", (k_cloudmc<true>), cgrid, block, s, G.D, Wk, McIn{}, g, b.nb, b.col0, b.nct, b.inflag, b.iceflag, b.liqflag);
+        LAUNCH("k_blocksort", k_blocksort, dim3(1), dim3(256), s, Wk, (b.nb + 63) / 64, one_sweep(b.nb, b.mode) ? 1 : 0);
     }
-    const LayerArgs la = layer_args(nb, col0, nct, nlay, idrv, istart, iend, GCM ? g.tauaer : c.taua);
-    const unsigned gx = (nb + LAYER_BLOCK - 1) / LAYER_BLOCK;
-    const dim3 lgrid(gx, nlay, la.nparts), lblock(LAYER_BLOCK);
+    const LayerArgs la = layer_args(b, GCM ? g.tauaer : c.taua);
+    const unsigned gx = (b.nb + LAYER_BLOCK - 1) / LAYER_BLOCK;
+    const dim3 lgrid(gx, b.nlay, la.nparts), lblock(LAYER_BLOCK);
     // the wide-window pass over the (window, layer) pairs the narrow launch could not take (GCM entry; kernels.hip: StageWin): as many
     // workgroups as fit the chip at once, which leave at once when the list is empty
     Workspace Wn = Wk;
     if (!GCM || !HAVE_WIDE || !g_wide_window) Wn.wide = nullptr;
-    const dim3 wgrid(gx * nlay, la.nparts);
+    const dim3 wgrid(gx * b.nlay, la.nparts);
     // (the list's count: cleared on the stream in front of the narrow launch - a memset node when the call is captured as a graph)
     if (Wn.wide) HIP_TRY(hipMemsetAsync(Wn.wide, 0, sizeof(int), s));
-#ifdef RRLW_TUNE
-    // tuning builds (tools/build_variant.sh name -DRRLW_TUNE ...): only the kernels of the benchmark's default workload - GCM entry,
-    // rtrn / rtrnmr, idrv = 0 - are instantiated (a quarter of the compile time); every other call shape is refused
-#define LAYER_GROUP(GR)                                                                                              \
-    if constexpr (GCM) { if (mode == 1 || mode == 2) { LAUNCH("k_layer<cloud," #GR ">", (k_layer<true, 1, GR>), lgrid, lblock, s, G.D, Wn, g, c, la); \
-                                                       if (Wn.wide) LAUNCH("k_layer<cloud,1>", (k_layer<true, 1, 1>), wgrid, lblock, s, G.D, Wn, g, c, la); } \
-                         else return fail(RRTMG_LW_HIP_EARG, "tuning build: cloudy non-McICA calls only"); }          \
-    else return fail(RRTMG_LW_HIP_EARG, "tuning build: GCM entry only");
-#else
-#define LAYER_GROUP(GR)                                                                                              \
-    if (mode == 0) LAUNCH("k_layer<clear," #GR ">", (k_layer<GCM, 0, GR>), lgrid, lblock, s, G.D, Wn, g, c, la);         \
-    else if (mode == 3) { if (mc) LAUNCH("k_layer<mcica," #GR ">", (k_layer<GCM, 2, GR>), lgrid, lblock, s, G.D, Wn, g, c, la); \
-                          else if constexpr (GCM) LAUNCH("k_layer<mcmask," #GR ">", (k_layer<true, 3, GR>), lgrid, lblock, s, G.D, Wn, g, c, la); } \
-    else LAUNCH("k_layer<cloud," #GR ">", (k_layer<GCM, 1, GR>), lgrid, lblock, s, G.D, Wn, g, c, la);             \
-    if constexpr (GCM) {                                                                                             \
-        if (Wn.wide) {                                                                                               \
-            if (mode == 0) LAUNCH("k_layer<clear,1>", (k_layer<true, 0, 1>), wgrid, lblock, s, G.D, Wn, g, c, la);        \
-            else if (mode == 3) { if (mc) LAUNCH("k_layer<mcica,1>", (k_layer<true, 2, 1>), wgrid, lblock, s, G.D, Wn, g, c, la); \
-                                  else LAUNCH("k_layer<mcmask,1>", (k_layer<true, 3, 1>), wgrid, lblock, s, G.D, Wn, g, c, la); } \
-            else LAUNCH("k_layer<cloud,1>", (k_layer<true, 1, 1>), wgrid, lblock, s, G.D, Wn, g, c, la);                  \
-        }                                                                                                            \
-    }
-#endif
-    LAYER_GROUP(0)
-#undef LAYER_GROUP
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
+    // k_layer's CLOUD: 0 clear, 1 cloud (rtrn / rtrnmr), 2 mcica (the sub-column arrays), 3 mcmask (the generator's mask)
+    const int cloud = b.mode == 0 ? 0 : b.mode == 3 ? (b.mc ? 2 : 3) : 1;
+    if (TUNING && !GCM) return fail(RRTMG_LW_HIP_EARG, "tuning build: GCM entry only");
+    if (TUNING && cloud != 1) return fail(RRTMG_LW_HIP_EARG, "tuning build: cloudy non-McICA calls only");
+    static const char *const names[4][2] = {{"k_layer<clear,0>", "k_layer<clear,1>"}, {"k_layer<cloud,0>", "k_layer<cloud,1>"},
+                                            {"k_layer<mcica,0>", "k_layer<mcica,1>"}, {"k_layer<mcmask,0>", "k_layer<mcmask,1>"}};
+    if (int rc = with_const<0, 1, 2, 3>(cloud, [&](auto CL) {
+            constexpr int cl = decltype(CL)::value;
+            if constexpr (layer_exists(GCM, cl)) {
+                LAUNCH(names[cl][0], (k_layer<GCM, cl, 0>), lgrid, lblock, s, G.D, Wn, g, c, la);
+                if constexpr (GCM) { if (Wn.wide) LAUNCH(names[cl][1], (k_layer<true, cl, 1>), wgrid, lblock, s, G.D, Wn, g, c, la); }
+            }
+            return 0;
+        })) return rc;
+    return launches_ok();
+}
+
+// what every sweep launch of a batch has in common (the group's bands, grid and slab come per launch)
+template <bool GCM>
+SweepArgs sweep_args(const Batch &b, const GcmIn &g, const ColIn &c, const FluxOut &out)
+{
+    SweepArgs sa{};
+    sa.ncol = b.nb; sa.col0 = b.col0; sa.nct = b.nct; sa.idrv = b.idrv; sa.istart = b.istart; sa.iend = b.iend;
+    sa.emis = GCM ? g.emis : c.semiss;
+    sa.cldfrac = GCM ? g.cldfr : c.cldfrac;
+    sa.tlay = GCM ? g.tlay : c.tavel;
+    sa.tlev = GCM ? g.tlev : c.tz;
+    // spectral outputs (GCM entries): the SPEC instantiations of the sweeps store every band's flux as well
+    if (GCM && out.uflxs) { sa.uflxs = out.uflxs; sa.dflxs = out.dflxs; sa.uflxcs = out.uflxcs; sa.dflxcs = out.dflxcs; }
+    return sa;
 }
 
 // vertical part of one batch: the sweep launches and k_flux
 template <bool GCM>
-int run_sweep(hipStream_t s, const Workspace &Wk_, int nb, int col0, int nct, int nlay, int mode, int idrv, int istart, int iend,
-              const GcmIn &g, const ColIn &c, const FluxOut &out, const McIn *mc = nullptr, int sset = 0)
+int run_sweep(hipStream_t s, const Workspace &Wk_, const Batch &b, const GcmIn &g, const ColIn &c, const FluxOut &out, int sset = 0)
 {
     Workspace Wk = Wk_;
+    const int nb = b.nb;
     // a batch that does not fill the chip: one band per workgroup, a slab per band (g_split_max, SweepArgs::split) - where the slab arrays hold
     // sixteen slabs of the batch's width
     const size_t pcb_split = align_up((size_t)nb, 64);
     const bool split = nb <= g_split_max && (size_t)NBND * pcb_split <= G.ws_slabcols && pcb_split <= (size_t)Wk.ncolb;
     Wk.pcb = split ? (int)pcb_split : Wk.ncolb;
-    const dim3 block(BLOCK);
     if (int rc = ensure_sweep_attrs()) return rc;
     // The four sweep launches of a batch (bands of 4, 3, 2, 1 quads) are independent.  Each workgroup owns a CU, so a launch ends with
     // a partly filled last round (1-quad bands: 2.5 rounds); on separate streams the other launches' workgroups fill those CUs.
@@ -826,38 +870,21 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, int nb, int col0, int nct, in
         HIP_TRY(hipEventRecord(SS.go, s));
         for (int k = 0; k < 3; k++) HIP_TRY(hipStreamWaitEvent(SS.q[k], SS.go, 0));
     }
-    const hipStream_t s_main = s;
+    SweepArgs sa = sweep_args<GCM>(b, g, c, out);
+    const bool spec = sa.uflxs != nullptr;
 #ifndef RRLW_TUNE
-    if (G.n1 && mode == 0 && GCM && istart == 1 && iend == 16 && idrv == 0 && !out.uflxs && n1_lds_bytes(nlay) <= 160 * 1024) {
+    if (G.n1 && b.mode == 0 && GCM && b.istart == 1 && b.iend == 16 && b.idrv == 0 && !spec && n1_lds_bytes(b.nlay) <= N1_LDS_MAX) {
         // prototype of the north-star mapping (one column per wavefront): replaces the sweeps, k_flux and k_rates of a cloud-free call
-        SweepArgs sa{};
-        sa.ncol = nb; sa.col0 = col0; sa.nct = nct; sa.idrv = 0; sa.istart = 1; sa.iend = 16;
-        sa.emis = g.emis; sa.cldfrac = nullptr; sa.tlay = g.tlay; sa.tlev = g.tlev;
-        sa.uflxs = sa.dflxs = sa.uflxcs = sa.dflxcs = nullptr;
-        static bool attr = false;
-        if (!attr) { HIP_TRY(hipFuncSetAttribute((const void *)k_n1<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr = true; }
+        // (it takes no spectral call)
         const dim3 ngrid((nb + N1_WAVES - 1) / N1_WAVES), nblock(64 * N1_WAVES);
-        LAUNCH_LDS("k_n1", (k_n1<false>), ngrid, nblock, n1_lds_bytes(nlay), s, G.D, Wk, sa, out, g.plev);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-        return 0;
+        LAUNCH_LDS("k_n1", (k_n1<false>), ngrid, nblock, n1_lds_bytes(b.nlay), s, G.D, Wk, sa, out, g.plev);
+        return launches_ok();
     }
 #endif
-    SweepArgs sa;
-    sa.ncol = nb; sa.col0 = col0; sa.nct = nct; sa.idrv = idrv; sa.istart = istart; sa.iend = iend;
     sa.split = split ? 1 : 0;
     // (cloud-free block groups of a batch that takes the three sweep launches: their own launch, below)
-    const bool cfree = g_clear_groups && mode != 0 && !one_sweep(nb, mode);
+    const bool cfree = g_clear_groups && b.mode != 0 && !one_sweep(nb, b.mode);
     sa.cfree = cfree ? 1 : 0;
-    sa.emis = GCM ? g.emis : c.semiss;
-    sa.cldfrac = GCM ? g.cldfr : c.cldfrac;
-    sa.tlay = GCM ? g.tlay : c.tavel;
-    sa.tlev = GCM ? g.tlev : c.tz;
-    // spectral outputs (GCM entries): the SPEC instantiations of the sweeps store every band's flux as well; the prototype k_n1 above
-    // takes no spectral call
-    const bool spec = GCM && out.uflxs;
-    sa.uflxs = spec ? out.uflxs : nullptr; sa.dflxs = spec ? out.dflxs : nullptr;
-    sa.uflxcs = spec ? out.uflxcs : nullptr; sa.dflxcs = spec ? out.dflxcs : nullptr;
     // Per class of bands with the same number of quads: a cloud-free call (mode 0) is one k_sweepc<., 0> launch; the cloudy modes run
     // k_sweepc<., 1> (layers above the batch's highest cloud, downward), k_sweepz<., mode> (layers 1 .. ltop down, surface, up) and
     // k_sweepc<., 2> (layers above, upward).  The classes are independent of each other: with `fan` each class has its own stream;
@@ -866,109 +893,74 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, int nb, int col0, int nct, in
     // order, takes the groups that hold no cloud - whole columns, one stream - and the workgroups of the other three leave at once there
     // (each decides by its group's hand-off level; the grids stay those of the batch).
     SweepGroups fg;
-    if (!make_groups(mode, idrv, istart, iend, fg)) return fail(RRTMG_LW_HIP_EARG, "internal: more than %d sweep groups", NGROUP_MAX);
-    if ((!split && fg.n > G.ws_groups) || (idrv == 1 && !G.ws_gdp)) return fail(RRTMG_LW_HIP_EARG, "internal: workspace holds %d band groups, the call needs %d", G.ws_groups, fg.n);
-    const int *gq = fg.gq;
+    if (!make_groups(b.mode, b.idrv, b.istart, b.iend, fg)) return fail(RRTMG_LW_HIP_EARG, "internal: more than %d sweep groups", NGROUP_MAX);
+    if ((!split && fg.n > G.ws_groups) || (b.idrv == 1 && !G.ws_gdp)) return fail(RRTMG_LW_HIP_EARG, "internal: workspace holds %d band groups, the call needs %d", G.ws_groups, fg.n);
     // first slab of every group, slabs per group (k_flux)
     int slab0[NGROUP_MAX];
     unsigned long long gsz = 0ull;
-    { int sl = 0; for (int g = 0; g < fg.n; g++) { slab0[g] = sl; const int n = split ? fg.nb[g] : 1; gsz |= (unsigned long long)n << (4 * g); sl += n; } }
-#define SWEEPC_I(Q, PH, I)                                                                                           \
-    do {                                                                                                             \
-        constexpr int nt = sweepc_nt(Q, PH, I);                                                                      \
-        const int wnb = split ? 1 : sa.nbands;              /* bands of a workgroup */                               \
-        const int nsb = split ? 1 : sweepc_nsb(Q, PH, I, sa.nbands);                                                 \
-        sa.ncb = (nb + 64 * nsb - 1) / (64 * nsb);                                                                   \
-        const dim3 sgrid((unsigned)sa.ncb, split ? sa.nbands : 1), sblock(64, wnb * nt, nsb);                        \
-        if (spec) LAUNCH_LDS("k_sweepc<" #Q "," #PH ",spec>", (k_sweepc<Q, PH, I, nt, true>), sgrid, sblock, sweepc_lds_bytes(PH, I, wnb, nsb, nt), s, G.D, Wk, sa); \
-        else LAUNCH_LDS("k_sweepc<" #Q "," #PH ">", (k_sweepc<Q, PH, I, nt>), sgrid, sblock, sweepc_lds_bytes(PH, I, wnb, nsb, nt), s, G.D, Wk, sa); \
-    } while (0)
-#ifdef RRLW_TUNE
-#define SWEEPC(Q, PH) do { if (idrv == 1) return fail(RRTMG_LW_HIP_EARG, "tuning build: idrv = 0 only"); else SWEEPC_I(Q, PH, false); } while (0)
-#else
-#define SWEEPC(Q, PH) do { if (idrv == 1 && PH != 1) SWEEPC_I(Q, PH, true); else SWEEPC_I(Q, PH, false); } while (0)
-#endif
-#define SWEEPC_Q(PH) do { if (nq == 4) SWEEPC(4, PH); else if (nq == 3) SWEEPC(3, PH); else if (nq == 2) SWEEPC(2, PH); else SWEEPC(1, PH); } while (0)
+    { int sl = 0; for (int gi = 0; gi < fg.n; gi++) { slab0[gi] = sl; const int n = split ? fg.nb[gi] : 1; gsz |= (unsigned long long)n << (4 * gi); sl += n; } }
+    // one launch of the instantiation K (SweepC<..> / SweepZ<..>) over the group sa holds, on its class's stream
+    hipStream_t gs = s;
+    const auto launch = [&](auto K) {
+        using Kn = decltype(K);
+        const int wnb = split ? 1 : sa.nbands;              // bands of a workgroup
+        const int nsb = split ? 1 : Kn::nsb(sa.nbands);
+        sa.ncb = (nb + 64 * nsb - 1) / (64 * nsb);
+        const dim3 sgrid((unsigned)sa.ncb, split ? sa.nbands : 1), sblock(64, wnb * Kn::nt, nsb);
+        LAUNCH_LDS(Kn::name.s, Kn::kernel(), sgrid, sblock, Kn::lds_bytes(wnb, nsb), gs, G.D, Wk, sa);
+        return 0;
+    };
+    const auto sweepc = [&](int nq, int phase) {
+        if (!sweepc_exists(phase, b.idrv == 1)) return fail(RRTMG_LW_HIP_EARG, "tuning build: idrv = 0 only");
+        return sweepc_dispatch(nq, phase, sweepc_ddt(phase, b.idrv), spec, launch);
+    };
+    const auto sweepz = [&](int nq) {
+        const int zmode = b.mode == 1 ? 1 : b.mode == 3 ? (b.mc ? 3 : 4) : 2;
+        if (!sweepz_exists(zmode, false)) return fail(RRTMG_LW_HIP_EARG, "tuning build: rtrnmr only");
+        if (!sweepz_exists(zmode, b.idrv == 1)) return fail(RRTMG_LW_HIP_EARG, "tuning build: idrv = 0 only");
+        return sweepz_dispatch(nq, zmode, b.idrv == 1, spec, launch);
+    };
     for (int phase = 0; phase < 3; phase++) {
-        if (phase == 1) {                           // cloud zone: k_sweepz, one launch per group
-            if (mode == 0) continue;
-            for (int g = 0; g < fg.n; g++) {
-                const int nq = gq[g];
-                sa.bands = fg.bands[g];
-                sa.nbands = fg.nb[g];
-                sa.group = slab0[g];
-                const hipStream_t s = (fan && nq < 4) ? SS.q[3 - nq] : s_main;
-#define SWEEPZ_I(Q, M, I)                                                                                            \
-    do {                                                                                                             \
-        constexpr int nt = sweepz_nt(Q);                                                                             \
-        const int wnb = split ? 1 : sa.nbands;                                                                       \
-        const int nsb = split ? 1 : sweepz_nsb(Q, sa.nbands, I);                                                     \
-        sa.ncb = (nb + 64 * nsb - 1) / (64 * nsb);                                                                   \
-        const dim3 sgrid((unsigned)sa.ncb, split ? sa.nbands : 1), sblock(64, wnb * nt, nsb);                        \
-        if (spec) LAUNCH_LDS("k_sweepz<" #Q "," #M ",spec>", (k_sweepz<Q, M, I, true>), sgrid, sblock, sweepz_lds_bytes(wnb, nsb, nt, I), s, G.D, Wk, sa); \
-        else LAUNCH_LDS("k_sweepz<" #Q "," #M ">", (k_sweepz<Q, M, I>), sgrid, sblock, sweepz_lds_bytes(wnb, nsb, nt, I), s, G.D, Wk, sa); \
-    } while (0)
-#ifdef RRLW_TUNE
-#define SWEEPZ_M(Q, M) do { if (idrv == 1) return fail(RRTMG_LW_HIP_EARG, "tuning build: idrv = 0 only"); else SWEEPZ_I(Q, M, false); } while (0)
-#define SWEEPZ(Q) do { if (mode == 2) SWEEPZ_M(Q, 2); else return fail(RRTMG_LW_HIP_EARG, "tuning build: rtrnmr only"); } while (0)
-#else
-#define SWEEPZ_M(Q, M) do { if (idrv == 1) SWEEPZ_I(Q, M, true); else SWEEPZ_I(Q, M, false); } while (0)
-#define SWEEPZ(Q) do { if (mode == 1) SWEEPZ_M(Q, 1); else if (mode == 3 && mc) SWEEPZ_M(Q, 3); else if (mode == 3) SWEEPZ_M(Q, 4); else SWEEPZ_M(Q, 2); } while (0)
-#endif
-                if (nq == 4) SWEEPZ(4); else if (nq == 3) SWEEPZ(3); else if (nq == 2) SWEEPZ(2); else SWEEPZ(1);
-#undef SWEEPZ_I
-#undef SWEEPZ_M
-#undef SWEEPZ
-            }
-            continue;
-        }
-        if (mode == 0 && phase == 2) continue;
-        if (one_sweep(nb, mode)) continue;          // (the cloud-zone kernel walks all levels of a small batch)
-        for (int g = 0; g < fg.n; g++) {            // above the clouds (or a cloud-free call): one launch per group
-            const int nq = gq[g];
-            sa.bands = fg.bands[g];
-            sa.nbands = fg.nb[g];
-            sa.group = slab0[g];
-            const hipStream_t s = (fan && nq < 4) ? SS.q[3 - nq] : s_main;
-#ifdef RRLW_TUNE
-            if (mode == 0) return fail(RRTMG_LW_HIP_EARG, "tuning build: cloudy calls only");
-#else
-            if (mode == 0) SWEEPC_Q(0);
-#endif
-            else if (phase == 0) { SWEEPC_Q(1); if (cfree) SWEEPC_Q(0); }
-            else SWEEPC_Q(2);
+        if (b.mode == 0 && phase != 0) continue;                    // (a cloud-free call: phase 0 is all of it)
+        if (phase != 1 && one_sweep(nb, b.mode)) continue;          // (the cloud-zone kernel walks all levels of a small batch)
+        for (int gi = 0; gi < fg.n; gi++) {                         // one launch per group
+            const int nq = fg.gq[gi];
+            sa.bands = fg.bands[gi];
+            sa.nbands = fg.nb[gi];
+            sa.group = slab0[gi];
+            gs = (fan && nq < 4) ? SS.q[3 - nq] : s;
+            int rc = 0;
+            if (phase == 1) rc = sweepz(nq);                        // the cloud zone
+            else if (b.mode == 0) rc = TUNING ? fail(RRTMG_LW_HIP_EARG, "tuning build: cloudy calls only") : sweepc(nq, 0);
+            else if (phase == 0) { rc = sweepc(nq, 1); if (rc == 0 && cfree) rc = sweepc(nq, 0); }      // above the clouds ...
+            else rc = sweepc(nq, 2);
+            if (rc) return rc;
         }
     }
-#undef SWEEPC_Q
-#undef SWEEPC
-#undef SWEEPC_I
     if (fan) {
         for (int k = 0; k < 3; k++) {
             HIP_TRY(hipEventRecord(SS.done[k], SS.q[k]));
-            HIP_TRY(hipStreamWaitEvent(s_main, SS.done[k], 0));
+            HIP_TRY(hipStreamWaitEvent(s, SS.done[k], 0));
         }
     }
     {
-        const dim3 wgrid((nb + COLSORT_WIN - 1) / COLSORT_WIN, (nlay + 1 + FLUX_LV - 1) / FLUX_LV), wblock(COLSORT_WIN, FLUX_TY);
+        const dim3 wgrid((nb + COLSORT_WIN - 1) / COLSORT_WIN, (b.nlay + 1 + FLUX_LV - 1) / FLUX_LV), wblock(COLSORT_WIN, FLUX_TY);
         const double *pz = GCM ? g.plev : c.pz;
-        if (idrv == 1) LAUNCH_LDS("k_flux", (k_flux<true>), wgrid, wblock, FLUX_LDS_BYTES, s, G.D, Wk, out, pz, nb, col0, nct, mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0);
-        else LAUNCH_LDS("k_flux", (k_flux<false>), wgrid, wblock, FLUX_LDS_BYTES, s, G.D, Wk, out, pz, nb, col0, nct, mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0);
+        if (b.idrv == 1) LAUNCH_LDS("k_flux", (k_flux<true>), wgrid, wblock, FLUX_LDS_BYTES, s, G.D, Wk, out, pz, nb, b.col0, b.nct, b.mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0);
+        else LAUNCH_LDS("k_flux", (k_flux<false>), wgrid, wblock, FLUX_LDS_BYTES, s, G.D, Wk, out, pz, nb, b.col0, b.nct, b.mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launches_ok();
 }
 
 
 // one batch on one stream (host-pointer entries, whose staging buffer serialises the batches anyway)
 template <bool GCM>
-int run_batch(hipStream_t s, int nb, int col0, int nct, int nlay, int mode, int idrv, int istart, int iend,
-              const GcmIn &g, const ColIn &c, int inflag, int iceflag, int liqflag, const FluxOut &out, const McIn *mc = nullptr)
+int run_batch(hipStream_t s, const Batch &b, const GcmIn &g, const ColIn &c, const FluxOut &out)
 {
-    const Workspace Wk = ws_for(0, use_colsort(GCM, mode, nb) && !mc);
-    if (int rc = run_prep<GCM>(s, Wk, nb, col0, nct, mode, idrv, istart, g, c, inflag, iceflag, liqflag)) return rc;
-    if (int rc = run_layer<GCM>(s, Wk, nb, col0, nct, nlay, mode, idrv, istart, iend, g, c, inflag, iceflag, liqflag, mc)) return rc;
-    return run_sweep<GCM>(s, Wk, nb, col0, nct, nlay, mode, idrv, istart, iend, g, c, out, mc);
+    const Workspace Wk = ws_for(0, use_colsort(GCM, b.mode, b.nb) && !b.mc);
+    if (int rc = run_prep<GCM>(s, Wk, b, g, c)) return rc;
+    if (int rc = run_layer<GCM>(s, Wk, b, g, c)) return rc;
+    return run_sweep<GCM>(s, Wk, b, g, c, out);
 }
 
 // ---- gas optics (rrtmg_lw_hip_gas_optics*) ------------------------------------------------------------------------------------------
@@ -993,25 +985,24 @@ int ensure_optics_ws(int nlay, int ncolb)
     return 0;
 }
 
-// one batch of the gas-optics entries on stream s: columns col0 .. col0 + nb - 1 of arrays nct columns wide (inputs and outputs alike)
+// one batch of the gas-optics entries on stream s: columns col0 .. col0 + nb - 1 of arrays nct columns wide (inputs and outputs alike;
+// of the Batch it reads these, nlay and idrv: all bands)
 template <bool GCM>
-int run_optics(hipStream_t s, int nb, int col0, int nct, int nlay, int idrv, const GcmIn &g, const ColIn &c, const OptOut &o)
+int run_optics(hipStream_t s, const Batch &b, const GcmIn &g, const ColIn &c, const OptOut &o)
 {
     Workspace W{};
-    W.ncolb = G.opt_ncolb; W.pcb = G.opt_ncolb; W.nlay = nlay; W.err = G.d_err;
+    W.ncolb = G.opt_ncolb; W.pcb = G.opt_ncolb; W.nlay = b.nlay; W.err = G.d_err;
     W.percol = G.opt_percol; W.laytrop = G.opt_laytrop;
     W.wide = GCM && HAVE_WIDE && g_wide_window ? G.opt_wide : nullptr;
-    LAUNCH("k_colprep", (k_colprep<GCM>), dim3((nb + 63) / 64), dim3(64), s, G.D, W, g, c, nb, col0, nct, idrv, 1, 0);
-    const LayerArgs la = layer_args(nb, col0, nct, nlay, idrv, 1, 16, nullptr);
-    const unsigned gx = (nb + LAYER_BLOCK - 1) / LAYER_BLOCK;
+    LAUNCH("k_colprep", (k_colprep<GCM>), dim3((b.nb + 63) / 64), dim3(64), s, G.D, W, g, c, b.nb, b.col0, b.nct, b.idrv, 1, 0);
+    const LayerArgs la = layer_args(b, nullptr);
+    const unsigned gx = (b.nb + LAYER_BLOCK - 1) / LAYER_BLOCK;
     if (W.wide) HIP_TRY(hipMemsetAsync(W.wide, 0, sizeof(int), s));
-    LAUNCH("k_optics", (k_optics<GCM, 0>), dim3(gx, nlay, la.nparts), dim3(LAYER_BLOCK), s, G.D, W, g, c, la, o);
+    LAUNCH("k_optics", (k_optics<GCM, 0>), dim3(gx, b.nlay, la.nparts), dim3(LAYER_BLOCK), s, G.D, W, g, c, la, o);
     if constexpr (GCM && HAVE_WIDE) {
-        if (W.wide) LAUNCH("k_optics<wide>", (k_optics<true, 1>), dim3(gx * nlay, la.nparts), dim3(LAYER_BLOCK), s, G.D, W, g, c, la, o);
+        if (W.wide) LAUNCH("k_optics<wide>", (k_optics<true, 1>), dim3(gx * b.nlay, la.nparts), dim3(LAYER_BLOCK), s, G.D, W, g, c, la, o);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launches_ok();
 }
 
 int check_optics(int idrv, const OptOut &o)
@@ -1070,10 +1061,11 @@ template <class T> void key_put(std::vector<unsigned char> &k, const T &v)
 
 struct KissGen { bool on; int icld, permuteseed; const double *alpha; };      // kissvec generator folded into the per-batch prep
 
-int run_pipelined(hipStream_t s, int ncol, int nlay, int mode, int idrv, const GcmIn &g, int inflag, int iceflag, int liqflag,
-                  const FluxOut &out, const McIn *mc, KissGen gen = KissGen{false, 0, 0, nullptr})
+int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOut &out, KissGen gen = KissGen{false, 0, 0, nullptr})
 {
     if (int rc = ensure_pipeline()) return rc;
+    const int ncol = call.nct, nlay = call.nlay, mode = call.mode, idrv = call.idrv;
+    const McIn *const mc = call.mc;
     const int nbmax = balanced_batch(ncol, eff_batch(nlay));
     // a call that is ONE batch has nothing for its per-column kernels to run beside: they go on the caller's stream, one cross-stream
     // event hop (~20 us of a 0.6 ms call) less
@@ -1093,7 +1085,7 @@ int run_pipelined(hipStream_t s, int ncol, int nlay, int mode, int idrv, const G
     bool capture = false;
     if (single && !split && !gen.on && !mc && !G.profile && !G.n1 && ncol <= g_graph_max) {
         std::vector<unsigned char> key;
-        key_put(key, ncol); key_put(key, nlay); key_put(key, mode); key_put(key, idrv); key_put(key, inflag); key_put(key, iceflag); key_put(key, liqflag);
+        key_put(key, ncol); key_put(key, nlay); key_put(key, mode); key_put(key, idrv); key_put(key, call.inflag); key_put(key, call.iceflag); key_put(key, call.liqflag);
         const double *gp[] = {g.play, g.plev, g.tlay, g.tlev, g.tsfc, g.h2ovmr, g.o3vmr, g.co2vmr, g.ch4vmr, g.n2ovmr, g.o2vmr, g.cfc11vmr, g.cfc12vmr,
                               g.cfc22vmr, g.ccl4vmr, g.emis, g.cldfr, g.taucld, g.cicewp, g.cliqwp, g.reice, g.reliq, g.tauaer, g.tauctot,
                               out.uflx, out.dflx, out.hr, out.uflxc, out.dflxc, out.hrc, out.duflx_dt, out.duflxc_dt, out.fnet, out.fnetc,
@@ -1141,8 +1133,10 @@ int run_pipelined(hipStream_t s, int ncol, int nlay, int mode, int idrv, const G
         HIP_TRY(hipStreamWaitEvent(aux, G.ev_in, 0));
     }
     int i = 0, rc_cap = 0;
+    Batch b = call;
     for (int col0 = 0; col0 < ncol; col0 += nbmax, i++) {
         const int nb = std::min(nbmax, ncol - col0), k = i & 1;
+        b.nb = nb; b.col0 = col0;
         const Workspace Wk = ws_for(k, use_colsort(true, mode, nb) && !mc);
         if (i >= 2) HIP_TRY(hipStreamWaitEvent(aux, G.ev_done[k], 0));       // prep set k is free again (sweep of batch i-2 done)
         // (The per-column kernels of batch i thus run beside k_layer of batch i-1.  Their few long-lived waves cost whatever runs beside
@@ -1151,12 +1145,12 @@ int run_pipelined(hipStream_t s, int ncol, int nlay, int mode, int idrv, const G
         if (capture) {
             // (one batch, one stream: the batch's launches, the fork to the sweep streams and their join become the graph; an error ends
             // the capture before it is reported)
-            rc_cap = run_prep<true>(s, Wk, nb, col0, ncol, mode, idrv, 1, g, c, inflag, iceflag, liqflag, g_prep_fork ? G.aux : nullptr);
-            if (rc_cap == 0) rc_cap = run_layer<true>(s, Wk, nb, col0, ncol, nlay, mode, idrv, 1, 16, g, c, inflag, iceflag, liqflag, mc);
-            if (rc_cap == 0) rc_cap = run_sweep<true>(s, Wk, nb, col0, ncol, nlay, mode, idrv, 1, 16, g, c, out, mc);
+            rc_cap = run_prep<true>(s, Wk, b, g, c, g_prep_fork ? G.aux : nullptr);
+            if (rc_cap == 0) rc_cap = run_layer<true>(s, Wk, b, g, c);
+            if (rc_cap == 0) rc_cap = run_sweep<true>(s, Wk, b, g, c, out);
             continue;
         }
-        if (int rc = run_prep<true>(aux, Wk, nb, col0, ncol, mode, idrv, 1, g, c, inflag, iceflag, liqflag, single && g_prep_fork ? G.aux : nullptr)) return rc;
+        if (int rc = run_prep<true>(aux, Wk, b, g, c, single && g_prep_fork ? G.aux : nullptr)) return rc;
         if (gen.on) {
 #if RRLW_GEN_BESIDE_SWEEP
             if (i >= 1 && !split) HIP_TRY(hipStreamWaitEvent(aux, G.ev_layer[(i - 1) & 1], 0));
@@ -1185,18 +1179,18 @@ int run_pipelined(hipStream_t s, int ncol, int nlay, int mode, int idrv, const G
                 if (i >= 1) HIP_TRY(hipStreamWaitEvent(sl, G.ev_layer[(i - 1) & 1], 0));     // (k_layer launches stay in batch order across the two streams)
             }
             if (i >= 2) HIP_TRY(hipStreamWaitEvent(sl, G.ev_done[k], 0));
-            if (int rc = run_layer<true>(sl, Wk, nb, col0, ncol, nlay, mode, idrv, 1, 16, g, c, inflag, iceflag, liqflag, mc)) return rc;
+            if (int rc = run_layer<true>(sl, Wk, b, g, c)) return rc;
             HIP_TRY(hipEventRecord(G.ev_layer[k], sl));
             HIP_TRY(hipStreamWaitEvent(ssm, G.ev_layer[k], 0));
             if (part && i >= 1) HIP_TRY(hipStreamWaitEvent(ssm, G.ev_done[(i - 1) & 1], 0));   // (the partial slabs and the hand-off array exist once: sweeps stay in batch order across the two sets)
-            if (int rc = run_sweep<true>(ssm, Wk, nb, col0, ncol, nlay, mode, idrv, 1, 16, g, c, out, mc, sset)) return rc;
+            if (int rc = run_sweep<true>(ssm, Wk, b, g, c, out, sset)) return rc;
             HIP_TRY(hipEventRecord(G.ev_done[k], ssm));
         } else {
-            if (int rc = run_layer<true>(s, Wk, nb, col0, ncol, nlay, mode, idrv, 1, 16, g, c, inflag, iceflag, liqflag, mc)) return rc;
+            if (int rc = run_layer<true>(s, Wk, b, g, c)) return rc;
 #if RRLW_GEN_BESIDE_SWEEP
             if (gen.on) HIP_TRY(hipEventRecord(G.ev_layer[k], s));
 #endif
-            if (int rc = run_sweep<true>(s, Wk, nb, col0, ncol, nlay, mode, idrv, 1, 16, g, c, out, mc)) return rc;
+            if (int rc = run_sweep<true>(s, Wk, b, g, c, out)) return rc;
             HIP_TRY(hipEventRecord(G.ev_done[k], s));
         }
     }
@@ -1212,7 +1206,7 @@ int run_pipelined(hipStream_t s, int ncol, int nlay, int mode, int idrv, const G
             (void)hipGetLastError();
             if (graph) (void)hipGraphDestroy(graph);
             gent->failed = true;
-            return run_pipelined(s, ncol, nlay, mode, idrv, g, inflag, iceflag, liqflag, out, mc, gen);
+            return run_pipelined(s, call, g, out, gen);
         }
         (void)hipGraphDestroy(graph);
         gent->exec = exec;
@@ -2619,7 +2613,7 @@ static int nomcica_device(const CallDesc &d, const GcmIn &g, const FluxOut &out,
     const int mode = *d.icld == 0 ? 0 : (*d.icld == 1 ? 1 : 2);      // :546-560 (icld=0 -> rtrnmr clear branch)
     const int nbmax = balanced_batch(d.ncol, eff_batch(d.nlay));
     if (int rc = ensure_workspace(d.nlay, nbmax, mode != 0, false, d.idrv, mode)) return rc;
-    return run_pipelined((hipStream_t)stream, d.ncol, d.nlay, mode, d.idrv, g, d.inflg, d.iceflg, d.liqflg, out, nullptr);
+    return run_pipelined((hipStream_t)stream, batch_of(d, mode), g, out);
 }
 
 #define GCM_PARAMS                                                                                              \
@@ -2714,7 +2708,7 @@ int nomcica_host_range(const CallDesc &d, int icld, int c0, int c1, const GcmIn 
     auto body = [&](hipStream_t s, int nb, int, std::vector<HostIn> &in, std::vector<HostOut> &out_) -> int {
         GcmIn gd = staged_gcm(in);
         if (use_tot) { gd.tauctot = gd.taucld; gd.taucld = nullptr; }
-        return run_batch<true>(s, nb, 0, nb, nlay, mode, idrv, 1, 16, gd, ColIn{}, d.inflg, d.iceflg, d.liqflg, staged_flux(out_));
+        return run_batch<true>(s, staged_batch(d, mode, nb), gd, ColIn{}, staged_flux(out_));
     };
     if (int rc = host_pipeline(ncol, c0, c1, nbmax, ins, outs, body, prep)) return rc;
     hipStream_t s = G.stream;
@@ -2830,7 +2824,10 @@ int rrtmg_lw_hip_run_columns(
     HIP_TRY(hipMemsetAsync(o[8], 0, n * (L + 1) * 8, s));
     HIP_TRY(hipMemsetAsync(o[9], 0, n * (L + 1) * 8, s));
     FluxOut out{o[0], o[1], o[3], o[4], o[5], o[7], o[8], o[9], o[2], o[6]};
-    if (int rc = run_batch<false>(s, ncol, 0, ncol, nlayers, mode, idrv, istart, iend, g, c, inflag, iceflag, liqflag, out)) return rc;
+    Batch b;
+    b.nlay = nlayers; b.nct = b.nb = ncol; b.mode = mode; b.idrv = idrv; b.istart = istart; b.iend = iend;
+    b.inflag = inflag; b.iceflag = iceflag; b.liqflag = liqflag;
+    if (int rc = run_batch<false>(s, b, g, c, out)) return rc;
     double *ho[10] = {totuflux, totdflux, fnet, htr, totuclfl, totdclfl, fnetc, htrc, dtotuflux_dt, dtotuclfl_dt};
     HIP_TRY(hipStreamSynchronize(s));
     for (int k = 0; k < 10; k++) if (int rc = bounce_d2h(ho[k], o[k], n * (L + 1) * 8)) return rc;
@@ -2857,8 +2854,12 @@ int rrtmg_lw_hip_gas_optics_device(OPTICS_GCM_PARAMS, void *stream)
     if (int rc = ensure_optics_ws(nlay, nbmax)) return rc;
     const hipStream_t s = (hipStream_t)stream;
     if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last, 0));      // an earlier call, possibly on another stream, still owns the workspace
-    for (int col0 = 0; col0 < ncol; col0 += nbmax)
-        if (int rc = run_optics<true>(s, std::min(nbmax, ncol - col0), col0, ncol, nlay, idrv, g, ColIn{}, o)) return rc;
+    Batch b;
+    b.nlay = nlay; b.nct = ncol; b.idrv = idrv;
+    for (b.col0 = 0; b.col0 < ncol; b.col0 += nbmax) {
+        b.nb = std::min(nbmax, ncol - b.col0);
+        if (int rc = run_optics<true>(s, b, g, ColIn{}, o)) return rc;
+    }
     HIP_TRY(hipEventRecord(G.ev_last, s));
     G.ev_last_valid = true;
     return 0;
@@ -2884,7 +2885,9 @@ static int gas_optics_host_range(int ncol, int c0, int c1, int nlay, int idrv, c
     auto body = [&](hipStream_t s, int nb, int, std::vector<HostIn> &in, std::vector<HostOut> &o_) -> int {
         auto d = [&](int k) { return o_[k].active ? o_[k].d : nullptr; };
         const OptOut o{d(0), d(1), d(2), d(3), d(4), d(5)};
-        return run_optics<true>(s, nb, 0, nb, nlay, idrv, staged_gcm(in), ColIn{}, o);
+        Batch b;
+        b.nlay = nlay; b.nct = b.nb = nb; b.idrv = idrv;
+        return run_optics<true>(s, b, staged_gcm(in), ColIn{}, o);
     };
     return host_pipeline(ncol, c0, c1, nbmax, ins, outs, body);
 }
@@ -2935,7 +2938,9 @@ int rrtmg_lw_hip_gas_optics_columns(
     const ColIn c{ins[0].d, ins[1].d, ins[2].d, ins[3].d, ins[4].d, ins[5].d, ins[6].d, ins[7].d, ins[8].d, ins[9].d, ins[10].d};
     const OptOut o{outs[0].d, outs[1].d, outs[2].d, outs[3].d, outs[4].d, outs[5].d};
     const hipStream_t s = G.stream;
-    if (int rc = run_optics<false>(s, ncol, 0, ncol, nlayers, idrv, GcmIn{}, c, o)) return rc;
+    Batch b;
+    b.nlay = nlayers; b.nct = b.nb = ncol; b.idrv = idrv;
+    if (int rc = run_optics<false>(s, b, GcmIn{}, c, o)) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     for (auto &r : outs) if (r.h) { if (int rc = bounce_d2h(r.h, r.d, r.cnt * 8)) return rc; }
     return 0;
@@ -2987,7 +2992,10 @@ int rrtmg_lw_hip_run_columns_mcica(
     HIP_TRY(hipMemsetAsync(o[8], 0, n * (L + 1) * 8, s));
     HIP_TRY(hipMemsetAsync(o[9], 0, n * (L + 1) * 8, s));
     FluxOut out{o[0], o[1], o[3], o[4], o[5], o[7], o[8], o[9], o[2], o[6]};
-    if (int rc = run_batch<false>(s, ncol, 0, ncol, nlayers, mode, idrv, istart, iend, g, c, inflag, iceflag, liqflag, out, &m)) return rc;
+    Batch b;
+    b.nlay = nlayers; b.nct = b.nb = ncol; b.mode = mode; b.idrv = idrv; b.istart = istart; b.iend = iend;
+    b.inflag = inflag; b.iceflag = iceflag; b.liqflag = liqflag; b.mc = &m;
+    if (int rc = run_batch<false>(s, b, g, c, out)) return rc;
     double *ho[10] = {totuflux, totdflux, fnet, htr, totuclfl, totdclfl, fnetc, htrc, dtotuflux_dt, dtotuclfl_dt};
     HIP_TRY(hipStreamSynchronize(s));
     for (int k = 0; k < 10; k++) if (int rc = bounce_d2h(ho[k], o[k], n * (L + 1) * 8)) return rc;
@@ -3353,7 +3361,7 @@ static int mcica_device(const CallDesc &d, const GcmIn &g, const McIn &m, const 
     const int mode = *d.icld == 0 ? 0 : 3;                       // inatm leaves the cloud arrays zero when icld = 0 (:899-911)
     const int nbmax = balanced_batch(d.ncol, eff_batch(d.nlay));
     if (int rc = ensure_workspace(d.nlay, nbmax, mode != 0, mode == 3, d.idrv, mode)) return rc;
-    return run_pipelined((hipStream_t)stream, d.ncol, d.nlay, mode, d.idrv, g, d.inflg, d.iceflg, d.liqflg, out, &m);
+    return run_pipelined((hipStream_t)stream, batch_of(d, mode, &m), g, out);
 }
 int rrtmg_lw_hip_run_mcica_device(MCICA_PARAMS, void *stream)
 {
@@ -3387,7 +3395,7 @@ static int mcica_host(const CallDesc &d, const GcmIn &g, const McIn &m, const Fl
         GcmIn gd = staged_gcm(in);          // (the sub-column arrays stand in the cloud arrays' places)
         const McIn md{gd.cldfr, gd.taucld, gd.cicewp, gd.cliqwp, gd.reice, gd.reliq};
         gd.cldfr = gd.taucld = gd.cicewp = gd.cliqwp = gd.reice = gd.reliq = nullptr;
-        return run_batch<true>(s, nb, 0, nb, nlay, mode, idrv, 1, 16, gd, ColIn{}, d.inflg, d.iceflg, d.liqflg, staged_flux(out_), &md);
+        return run_batch<true>(s, staged_batch(d, mode, nb, &md), gd, ColIn{}, staged_flux(out_));
     };
     // layers whose sub-column cloud fractions are all below cldmin for the batch: cldprmc reads nothing else of them (src/rrtmg_lw_cldprmc.f90:182-183)
     std::vector<unsigned char> cloudfree(L, 0), cf_uni(L, 0);
@@ -3549,7 +3557,7 @@ static int mcica_subcol_device(const CallDesc &d, const GcmIn &g, const double *
             gen.on = true;
         } else if (int rc = generate_mask(s, d.ncol, d.nlay, icld_gen, d.permuteseed, *d.irng, g.play, g.cldfr, alpha)) return rc;
     }
-    return run_pipelined(s, d.ncol, d.nlay, mode, d.idrv, g, d.inflg, d.iceflg, d.liqflg, out, nullptr, gen);
+    return run_pipelined(s, batch_of(d, mode), g, out, gen);
 }
 int rrtmg_lw_hip_run_mcica_subcol_device(SUBCOL_PARAMS, void *stream)
 {
@@ -3596,7 +3604,7 @@ static int mcica_subcol_host_range(const CallDesc &d, int icld_gen, int irng, in
     std::vector<HostOut> outs = host_outs(out, L, idrv);
     auto body = [&](hipStream_t bs, int nb, int col0, std::vector<HostIn> &in, std::vector<HostOut> &out_) -> int {
         G.W.mask_col0 = (size_t)(col0 - c0);                      // staged arrays start at column 0, the mask holds the block's columns
-        return run_batch<true>(bs, nb, 0, nb, nlay, mode, idrv, 1, 16, staged_gcm(in), ColIn{}, d.inflg, d.iceflg, d.liqflg, staged_flux(out_), nullptr);
+        return run_batch<true>(bs, staged_batch(d, mode, nb), staged_gcm(in), ColIn{}, staged_flux(out_));
     };
     {
         const int rc = host_pipeline(ncol, c0, c1, nbmax, ins, outs, body);
@@ -3723,9 +3731,7 @@ int form_launch(hipStream_t s, bool in, const rrtmg_lw_hip_array_form &f, const 
         if (f.real_bytes == 4) LAUNCH("k_form_out<f32>", (k_form_out<float>), grid, block, s, t);
         else LAUNCH("k_form_out<f64>", (k_form_out<double>), grid, block, s, t);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launches_ok();
 }
 // the staging of a batch / of the generator's call-wide arrays: grows like the workspace, freed by finalize and by a re-initialisation
 int ensure_form(void **base, size_t *have, size_t bytes)
@@ -3788,7 +3794,7 @@ int form_solve(const rrtmg_lw_hip_array_form &f, const CallDesc &d, int mode, co
         for (size_t k = 0; k < outs.size(); k++) op[outs[k].pos] = so[k];
         rc = form_launch(s, true, f, ins, si, ncol, col0, nb);
         G.W.mask_col0 = mode == 3 ? col0 : 0;             // staged arrays start at column 0, the mask holds the call's columns
-        if (rc == 0) rc = run_batch<true>(s, (int)nb, 0, (int)nb, d.nlay, mode, d.idrv, 1, 16, g, ColIn{}, d.inflg, d.iceflg, d.liqflg, flux_from(op), nullptr);
+        if (rc == 0) rc = run_batch<true>(s, staged_batch(d, mode, (int)nb), g, ColIn{}, flux_from(op));
         if (rc == 0) rc = form_launch(s, false, f, outs, so, ncol, col0, nb);
     }
     G.W.mask_col0 = 0;
@@ -3877,7 +3883,9 @@ int gas_optics_device_as(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, i
         double *op[6] = {};
         for (size_t k = 0; k < outs.size(); k++) op[outs[k].pos] = so[k];
         rc = form_launch(s, true, f, ins, si, (size_t)ncol, col0, nb);
-        if (rc == 0) rc = run_optics<true>(s, (int)nb, 0, (int)nb, nlay, idrv, gcm_from(sp), ColIn{}, OptOut{op[0], op[1], op[2], op[3], op[4], op[5]});
+        Batch b;
+        b.nlay = nlay; b.nct = b.nb = (int)nb; b.idrv = idrv;
+        if (rc == 0) rc = run_optics<true>(s, b, gcm_from(sp), ColIn{}, OptOut{op[0], op[1], op[2], op[3], op[4], op[5]});
         if (rc == 0) rc = form_launch(s, false, f, outs, so, (size_t)ncol, col0, nb);
     }
     HIP_TRY(hipEventRecord(G.ev_last, s));

@@ -314,9 +314,9 @@ int rrtmg_lw_hip_queue_flush(void);
 int rrtmg_lw_hip_queue_columns(void);
 
 /* What the library was built with: 0 for the shipped library, 8 for the 256-g-point one.  Bit 0: tuning build (-DRRLW_TUNE: only the
- * benchmark's kernels), bit 1: knock-out switch (WRONG results, timing only), bit 2: numerics variant (other code width / decode /
- * division than the product's), bit 3: -DRRLW_G256, bit 4: kernel-geometry switches (same results, other speed).
- * rrtmg_lw_hip_init[_devices] refuses a library with bit 1 or 2 unless RRTMG_LW_ALLOW_TUNE_BUILD=1 is set. */
+ * benchmark's kernels), bit 3: -DRRLW_G256, bit 4: kernel-geometry switches (same results, other speed).  Bits 1 and 2 (knock-out
+ * switch, numerics variant) are reserved: these sources no longer set them - the switches behind them are retired, and no build of
+ * these sources computes anything but the product's results. */
 unsigned rrtmg_lw_hip_build_flags(void);
 /* Columns processed per internal batch (bounds the device workspace); 0 = back to the default, which follows the call's layers: 262144 at up
  * to 96 layers, 131072 at 137 (the next lower power of two of 262144 x 72 / nlay) - the benchmark's call (1e6 x 72 layers, rtrnmr) then holds

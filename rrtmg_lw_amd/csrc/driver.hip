@@ -419,10 +419,8 @@ constexpr bool TUNING = true;
 #else
 constexpr bool TUNING = false;
 #endif
-constexpr bool sweepc_exists(int, bool ddt) { return !ddt || !TUNING; }
-// Phase 1 (down, above the clouds) forms no d/dT terms: a call with idrv = 1 launches its plain instantiation.  (Its d/dT instantiation is
-// compiled all the same, as it always was - the launch macro named it in a branch that is never taken - and is left in the list so that the
-// code object keeps its kernels; `phase != 1` in sweepc_exists is all it takes to drop it.)
+// Phase 1 (down, above the clouds) forms no d/dT terms: it has no d/dT instantiation, and a call with idrv = 1 launches its plain one.
+constexpr bool sweepc_exists(int phase, bool ddt) { return !ddt || (!TUNING && phase != 1); }
 constexpr bool sweepc_ddt(int phase, int idrv) { return idrv == 1 && phase != 1; }
 constexpr bool sweepz_exists(int mode, bool ddt) { return !TUNING || (mode == 2 && !ddt); }
 constexpr bool layer_exists(bool gcm, int cloud) { return TUNING ? gcm && cloud == 1 : gcm || cloud != 3; }     // the generator's mask: GCM entries only
@@ -454,7 +452,7 @@ constexpr KernelName sweep_name(char family, int nq, int x, bool spec)
 template <int Q, int PH, bool I, bool SPEC>
 struct SweepC {
     static constexpr KernelName name = sweep_name('c', Q, PH, SPEC);
-    static constexpr int nt = sweepc_nt(Q, PH, I);
+    static constexpr int nt = sweepc_nt(Q, PH);
     static constexpr auto kernel() { return &k_sweepc<Q, PH, I, nt, SPEC>; }
     static int nsb(int nbands) { return sweepc_nsb(Q, PH, I, nbands); }
     static int lds_bytes(int wnb, int nsb) { return sweepc_lds_bytes(PH, I, wnb, nsb, nt); }
@@ -860,10 +858,9 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, const Batch &b, const GcmIn &
     // The four sweep launches of a batch (bands of 4, 3, 2, 1 quads) are independent.  Each workgroup owns a CU, so a launch ends with
     // a partly filled last round (1-quad bands: 2.5 rounds); on separate streams the other launches' workgroups fill those CUs.
     // Measured: 10 000 columns 1.22 -> 0.98 ms; 125 000-column batches no gain (cloudy 98.9 -> 98.4 ms per 1e6 columns, McICA 115.5 -> 122.6).
-#ifndef RRLW_FANOUT_MAX
-#define RRLW_FANOUT_MAX 0x7fffffff     // (round 3: for every batch size - 61.4 -> 60.2 ms per 1e6 cloudy columns, three runs each; deep clouds 87.7 -> 85.7.
-#endif                                 // The HIP-event times of the sweep kernels then overlap: their sum exceeds the wall time they take together)
-    const bool fan = G.sweep_fanout && nb < RRLW_FANOUT_MAX;
+    // (Round 3: for every batch size - 61.4 -> 60.2 ms per 1e6 cloudy columns, three runs each; deep clouds 87.7 -> 85.7.  The HIP-event
+    // times of the sweep kernels then overlap: their sum exceeds the wall time they take together.)
+    const bool fan = G.sweep_fanout;
     State::SweepSet &SS = G.swset[sset];
     if (fan) {
         if (int rc = ensure_sweep_set(sset)) return rc;
@@ -911,7 +908,7 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, const Batch &b, const GcmIn &
         return 0;
     };
     const auto sweepc = [&](int nq, int phase) {
-        if (!sweepc_exists(phase, b.idrv == 1)) return fail(RRTMG_LW_HIP_EARG, "tuning build: idrv = 0 only");
+        if (TUNING && b.idrv == 1) return fail(RRTMG_LW_HIP_EARG, "tuning build: idrv = 0 only");
         return sweepc_dispatch(nq, phase, sweepc_ddt(phase, b.idrv), spec, launch);
     };
     const auto sweepz = [&](int nq) {
@@ -1030,14 +1027,11 @@ int ensure_pipeline()
 
 // all batches of a device-resident call on the caller's stream `s`, the per-column kernels of batch i+1 overlapping the
 // heavy kernels of batch i on the auxiliary stream (two prep sets)
-// Build switch: hold the sub-column generator of batch i+1 back until k_layer of batch i is done, so that it runs beside the sweeps
-// instead of beside k_layer.  Measured per 1e6 McICA columns: beside k_layer the generator takes 19.3 ms and k_layer 35.7 (26.7 alone,
-// both VALU-bound), beside the sweeps the generator takes its 12.9 ms and k_sweepc 29.1 instead of 19.9 (a sweep work-group needs most
+// (The sub-column generator of batch i+1 runs beside k_layer of batch i.  Held back until that k_layer is done, so that it runs beside
+// the sweeps instead, it gains nothing - measured per 1e6 McICA columns, profiles/HISTORY.md: beside k_layer the generator takes 19.3 ms
+// and k_layer 35.7 (26.7 alone, both VALU-bound), beside the sweeps the generator takes its 12.9 ms and k_sweepc 29.1 instead of 19.9 (a sweep work-group needs most
 // of a CU's LDS and waits for the generator's work-groups to leave) - 77.5 vs 77.7 ms a step either way, also with the auxiliary stream
-// at the lowest priority.  The generator's 12.9 ms are added work, not hidden work.
-#ifndef RRLW_GEN_BESIDE_SWEEP
-#define RRLW_GEN_BESIDE_SWEEP 0
-#endif
+// at the lowest priority.  The generator's 12.9 ms are added work, not hidden work.)
 int launch_kiss(hipStream_t s, const Workspace &Wk, int ncol, int col0, int nb, int nlay, int icld, int permuteseed, const SubcolIn &in);
 
 // A device-resident call of ONE batch that does not fill the chip is a chain of a dozen dependent launches on up to four streams: the
@@ -1152,9 +1146,6 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
         }
         if (int rc = run_prep<true>(aux, Wk, b, g, c, single && g_prep_fork ? G.aux : nullptr)) return rc;
         if (gen.on) {
-#if RRLW_GEN_BESIDE_SWEEP
-            if (i >= 1 && !split) HIP_TRY(hipStreamWaitEvent(aux, G.ev_layer[(i - 1) & 1], 0));
-#endif
             if (int rc = launch_kiss(aux, Wk, ncol, col0, nb, nlay, gen.icld, gen.permuteseed, SubcolIn{g.play, g.cldfr, gen.alpha})) return rc;
         }
         if (!single) HIP_TRY(hipEventRecord(G.ev_ready[k], aux));
@@ -1187,9 +1178,6 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
             HIP_TRY(hipEventRecord(G.ev_done[k], ssm));
         } else {
             if (int rc = run_layer<true>(s, Wk, b, g, c)) return rc;
-#if RRLW_GEN_BESIDE_SWEEP
-            if (gen.on) HIP_TRY(hipEventRecord(G.ev_layer[k], s));
-#endif
             if (int rc = run_sweep<true>(s, Wk, b, g, c, out)) return rc;
             HIP_TRY(hipEventRecord(G.ev_done[k], s));
         }
@@ -2200,8 +2188,8 @@ static int init_state(const char *static_tables_path, const char *kdata_path, do
 
 static void finalize_state();
 
-// What this library was built with (kernels.hip, "Tuning switches"): bit 0 tuning build (the benchmark's kernels only), 1 knock-out (wrong
-// results), 2 numerics variant, 3 the 256-g-point configuration, 4 kernel-geometry switches.  The shipped libraries: 0 and 8.
+// What this library was built with (kernels.hip, "Build switches"): bit 0 tuning build (the benchmark's kernels only), 3 the 256-g-point
+// configuration, 4 kernel-geometry switches; 1 and 2 (knock-out, numerics variant) reserved, no longer set.  The shipped libraries: 0 and 8.
 unsigned rrtmg_lw_hip_build_flags(void) { return BUILD_FLAGS; }
 
 int rrtmg_lw_hip_init(const char *static_tables_path, const char *kdata_path, double cpdair, int device)
@@ -2216,12 +2204,6 @@ int rrtmg_lw_hip_init_devices(const char *static_tables_path, const char *kdata_
 {
     std::lock_guard<std::mutex> lk(g_mu);
     g_cur = &g_states[0];
-    if (BUILD_FLAGS & (RRLW_BF_KNOCKOUT | RRLW_BF_NUMERICS)) {      // a measurement build whose results are not the product's
-        const char *e = getenv("RRTMG_LW_ALLOW_TUNE_BUILD");
-        if (!e || atoi(e) == 0)
-            return fail(RRTMG_LW_HIP_EARG, "this library is a measurement build (build flags 0x%x: knock-out or numerics variant); set RRTMG_LW_ALLOW_TUNE_BUILD=1 to use it",
-                        BUILD_FLAGS);
-    }
     if (ndev < 1 || ndev > MAXDEV || !devices) return fail(RRTMG_LW_HIP_EARG, "ndev must be 1..%d", MAXDEV);
     int rc = 0, done = 0;
     std::string err;
@@ -2516,7 +2498,6 @@ int rrtmg_lw_hip_cu_partition(void) { return g_states[0].cu_layer; }
 int rrtmg_lw_hip_set_n1_prototype(int on)
 {
     ENTRY_LOCK;
-    if (on && CODE_BITS != 32) return fail(RRTMG_LW_HIP_EARG, "the k_n1 prototype reads 32-bit cell codes");
     G.n1 = on != 0;
     return 0;
 }

@@ -30,29 +30,17 @@
 #include "kissjump.hpp"
 
 // ------------------------------------------------------------------------------------------------
-// Tuning switches.  This translation unit carries one-source measurement switches (-DRRLW_...: geometry of the kernels, numerics variants,
-// two knock-outs that give WRONG results); the shipped libraries are built with none of them (only -DRRLW_G256 for the 256-g-point
-// library).  What a library was built with is recorded in its build-flags word (rrtmg_lw_hip_build_flags): rrtmg_lw_hip_init refuses a
-// library whose results differ from the product's (knock-out or numerics variant) unless RRTMG_LW_ALLOW_TUNE_BUILD=1, and a knock-out
-// does not compile outside a tuning build (-DRRLW_TUNE: the benchmark's kernels only).
+// Build switches.  -DRRLW_G256 is the product's 256-g-point configuration and -DRRLW_TUNE the tuning build (the benchmark's kernels only:
+// a one-minute compile).  What remains beside them are plain numbers with one use each (block sizes, waves-per-SIMD tables: same results,
+// other speed) and two instruments that have tools (RRLW_LAYER_STAMPS, RRLW_DBG_DUMP); the shipped libraries are built with none of
+// them.  What a library was built with is recorded in its build-flags word (rrtmg_lw_hip_build_flags): bit 0 tuning, bit 3 G256, bit 4
+// geometry.  Bits 1 and 2 (knock-out, numerics variant) are reserved: the switches that set them - alternate code paths of experiments
+// that were run and lost - are retired, with their results under profiles/ (profiles/switch_retirement.md lists them).
 // ------------------------------------------------------------------------------------------------
-#if (defined(RRLW_KO_LDS_UNIFORM) || defined(RRLW_KO_HALFG) || defined(RRLW_KO_STORES) || defined(RRLW_KO_HALFSTORE)) && !defined(RRLW_TUNE)
-#error "RRLW_KO_* knock-outs give wrong results: tuning builds (-DRRLW_TUNE) only"
-#endif
 #ifdef RRLW_TUNE
 #define RRLW_BF_TUNE 1u
 #else
 #define RRLW_BF_TUNE 0u
-#endif
-#if defined(RRLW_KO_LDS_UNIFORM) || defined(RRLW_KO_HALFG) || defined(RRLW_KO_STORES) || defined(RRLW_KO_HALFSTORE)
-#define RRLW_BF_KNOCKOUT 2u
-#else
-#define RRLW_BF_KNOCKOUT 0u
-#endif
-#if (defined(RRLW_CODE_BITS) && RRLW_CODE_BITS != 32) || defined(RRLW_DECODE_F64) || defined(RRLW_SWEEP_EXPF) || defined(RRLW_EXACT_DIV) || defined(RRLW_FDIV_TWO_NEWTON)
-#define RRLW_BF_NUMERICS 4u
-#else
-#define RRLW_BF_NUMERICS 0u
 #endif
 #ifdef RRLW_G256
 #define RRLW_BF_G256 8u
@@ -60,13 +48,9 @@
 #define RRLW_BF_G256 0u
 #endif
 // kernel-geometry switches given on the command line (same results, other speed)
-#if defined(RRLW_LAYER_BLOCK) || defined(RRLW_STAGE_DOUBLES) || defined(RRLW_LAYER_WAVES) || defined(RRLW_LOAD_CHUNK) || defined(RRLW_CLOUD_QUADS) || \
-    defined(RRLW_MINOR_WIN) || defined(RRLW_COLSORT_WIN) || defined(RRLW_LAYER_PASS_PER_BAND) || defined(RRLW_LAYER_PASSES_3) || defined(RRLW_LAYER_PASSES_1) || \
-    defined(RRLW_LAYER_SYNCTHREADS) || defined(RRLW_LAYER_STAMPS) || defined(RRLW_NO_NT) || defined(RRLW_SWEEPC_P0) || defined(RRLW_SWEEPC_P2D) || \
-    defined(RRLW_SWEEPC_WAVES_CAP) || defined(RRLW_SWEEPC_QUAD_BARRIER) || defined(RRLW_SWEEPC_CODES) || defined(RRLW_SWEEPC_SPLIT) || defined(RRLW_SWEEPC_SPLIT3) || \
-    defined(RRLW_SWEEPC_SPLIT_P1) || defined(RRLW_SWEEPZ_CT_SLOTS) || defined(RRLW_SWEEPZ_G2) || defined(RRLW_SWEEPZ_WAVES_G2) || defined(RRLW_SWEEPZ_WAVES_G1) || \
-    defined(RRLW_SWEEPZ_WAVES_IDRV) || defined(RRLW_GEN_BESIDE_SWEEP) || defined(RRLW_FANOUT_MAX) || defined(RRLW_KI_SALU) || \
-    defined(RRLW_SWEEPC_THIN) || defined(RRLW_SWEEPC_THIN_P1) || \
+#if defined(RRLW_LAYER_BLOCK) || defined(RRLW_STAGE_DOUBLES) || defined(RRLW_LAYER_WAVES) || defined(RRLW_LOAD_CHUNK) || defined(RRLW_MINOR_WIN) || \
+    defined(RRLW_COLSORT_WIN) || defined(RRLW_SWEEPC_P0) || defined(RRLW_SWEEPC_P2D) || defined(RRLW_SWEEPC_WAVES_CAP) || defined(RRLW_SWEEPC_CODES) || \
+    defined(RRLW_SWEEPZ_WAVES_G1) || defined(RRLW_SWEEPZ_WAVES_IDRV) || defined(RRLW_LAYER_STAMPS) || \
     defined(RRLW_DBG_DUMP)      /* (driver.hip: one more entry, rrtmg_lw_hip_debug_scratch - reads k_layer's cell codes back; tuning builds only) */
 #define RRLW_BF_GEOMETRY 16u
 #else
@@ -81,7 +65,7 @@
 
 namespace rrlw {
 
-constexpr unsigned BUILD_FLAGS = RRLW_BF_TUNE | RRLW_BF_KNOCKOUT | RRLW_BF_NUMERICS | RRLW_BF_G256 | RRLW_BF_GEOMETRY;
+constexpr unsigned BUILD_FLAGS = RRLW_BF_TUNE | RRLW_BF_G256 | RRLW_BF_GEOMETRY;
 
 // ------------------------------------------------------------------------------------------------
 // device-side views
@@ -113,16 +97,11 @@ enum Scr { S_CODE, S_CODET, NSCR };
 // per-band partial fluxes, each [band][level][column] of {total-sky, clear-sky}: downward, upward, d(upward)/dT
 struct alignas(16) Part2 { double a, b; };
 
-// the per-cell codes handed from k_layer to the sweeps (all arithmetic stays float64): in registers a float (scr_t, cell_code), in
-// memory RRLW_CODE_BITS bits per cell, four cells (a quad) per record.  32 = the float itself; 24 and 16 are measurement variants that
-// keep the table index whole and round the series-branch optical depth to 18 / 11 mantissa bits (pack4 / unpack4).
+// the per-cell codes handed from k_layer to the sweeps (all arithmetic stays float64): in registers and in memory a float (scr_t,
+// cell_code), four cells (a quad) per record.  (24- and 16-bit records, which kept the table index whole and rounded the series-branch
+// optical depth to 18 / 11 mantissa bits, were measured in round 3 and lost: profiles/round3_code_bits.md.)
 typedef float scr_t;
-#ifndef RRLW_CODE_BITS
-#define RRLW_CODE_BITS 32
-#endif
-constexpr int CODE_BITS = RRLW_CODE_BITS;
-static_assert(CODE_BITS == 32 || CODE_BITS == 24 || CODE_BITS == 16, "bits per cell code");
-constexpr int CODE_WORDS = CODE_BITS / 8;        // 32-bit words per quad record
+constexpr int CODE_WORDS = 4;                    // 32-bit words per quad record
 constexpr int CODE_BYTES = 4 * CODE_WORDS;
 
 struct Workspace {
@@ -239,20 +218,12 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 // the correctly rounded one; where it feeds an index (`int(...)`, the 1e-4-quantised transmittance table) a different index needs the
 // exact quotient to sit within ~1e-16 of a boundary: tools/divtest.hip finds 0 quotients and 0 table indices different from the IEEE
 // division in 2.1e9 operands, with one Newton step as with two (profiles/round2_divtest.txt; round 3 made one the default: -0.3 ms).
-// -DRRLW_EXACT_DIV restores the IEEE division, -DRRLW_FDIV_TWO_NEWTON the second step.
 __device__ __forceinline__ double fdiv(double a, double b)
 {
-#ifdef RRLW_EXACT_DIV
-    return a / b;
-#else
     double r = __builtin_amdgcn_rcp(b);
     r = fma(fma(-b, r, 1.0), r, r);
-#ifdef RRLW_FDIV_TWO_NEWTON
-    r = fma(fma(-b, r, 1.0), r, r);
-#endif
     const double q = a * r;
     return fma(fma(-b, q, a), r, q);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1141,13 +1112,9 @@ __device__ __forceinline__ double2 ldl(const double2 *lds, unsigned elem_off) { 
 // store of the band they have just finished (stores count in vmcnt) sixteen times per layer although no other wave reads those codes.
 __device__ __forceinline__ void lds_barrier()
 {
-#if defined(RRLW_LAYER_SYNCTHREADS)
-    __syncthreads();
-#else
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-#endif
 }
 
 // In-kernel stamps (diagnostic build -DRRLW_LAYER_STAMPS only: where a k_layer wave spends its cycles; the build's run time means
@@ -1348,9 +1315,6 @@ __device__ __forceinline__ void rows_to_lds(Rows<N> &rw, const unsigned (&delta)
         const int role = i < IS ? RL_MAJOR : i < IF ? RL_SELF : i < IM0 ? RL_FOR :
                          (i < IC ? (R.nm > 1 && i >= IM1 ? (R.nm > 2 && i >= IM2 ? RL_MINOR2 : RL_MINOR1) : RL_MINOR0) : (i == IC ? RL_CFC0 : RL_CFC1));
         rw.off[i] = rw.off[i] + delta[role];
-#ifdef RRLW_KO_LDS_UNIFORM      // knock-out (timing only, wrong results): every lane reads the first lane's rows - pure broadcasts, no bank conflict
-        rw.off[i] = (unsigned)__builtin_amdgcn_readfirstlane((int)rw.off[i]);
-#endif
     }
 }
 
@@ -1362,19 +1326,12 @@ __device__ __forceinline__ void rows_to_lds(Rows<N> &rw, const unsigned (&delta)
 #ifndef RRLW_LOAD_CHUNK
 #define RRLW_LOAD_CHUNK 2       // loads in flight per pipeline stage.  From LDS two suffice (8 were needed through the vector L1) and the
 #endif                          // registers saved allow three waves per SIMD: 36.4 vs 40.9 ms per 1e6 cloudy columns
-#ifndef RRLW_CLOUD_QUADS
-#define RRLW_CLOUD_QUADS 1      // quads of a band whose cloudy-layer look-ups are in flight together (2 until round 5: with the quad-wise table indices two spill ten registers)
-#endif
 
 template <int B, bool LOWER, int N>
 struct BandLoads {
     static constexpr Region R = LOWER ? BT<B>::lo : BT<B>::up;
     static constexpr int ng = BT<B>::ng;
-#ifdef RRLW_KO_HALFG       // knock-out (timing only, wrong results): only the first half of a band's g-points is evaluated - the occupancy experiment of round 3
-    static constexpr int HP = (ng / 2 + 1) / 2;
-#else
     static constexpr int HP = ng / 2;                                    // 16-byte loads per table row
-#endif
     static constexpr int NK = N * HP;                                    // absorption-coefficient loads
     static constexpr int NL = NK;
     static constexpr int CH = RRLW_LOAD_CHUNK;
@@ -1467,91 +1424,30 @@ struct alignas(16) scr4 { scr_t v[4]; };
 typedef float scr_vec __attribute__((ext_vector_type(4)));
 // a quad's four codes as they lie in memory
 struct pk4 { unsigned w[CODE_WORDS]; };
-// Reduced code widths (measurement variants): bit (CODE_BITS - 1) = table cell, then the table index (<= 10000); otherwise the series-branch
-// optical depth (0 <= od <= 0.06) as a small float - its float32 pattern scaled so that the exponent field fits E bits, cut to M mantissa
-// bits with rounding; tiny values go through the scaled float's denormals, i.e. they keep an ABSOLUTE resolution.
-//   24 bits: E = 5, M = 18 (relative 1.9e-6), scale 2^-91;   16 bits: E = 4, M = 11 (relative 2.4e-4), scale 2^-107
-template <int BITS> struct CodeFmt;
-template <> struct CodeFmt<24> { static constexpr int SH = 5;  static constexpr unsigned FLAG = 0x800000u, MASK = 0x7fffffu; static constexpr float DN = 0x1p-91f,  UP = 0x1p+91f; };
-template <> struct CodeFmt<16> { static constexpr int SH = 12; static constexpr unsigned FLAG = 0x8000u,   MASK = 0x7fffu;   static constexpr float DN = 0x1p-107f, UP = 0x1p+107f; };
-template <int BITS> __device__ __forceinline__ unsigned code_narrow(scr_t c)
-{
-    using F = CodeFmt<BITS>;
-    if (c < 0.f) return F::FLAG | (unsigned)(int)(-c);
-    const unsigned u = __float_as_uint(c * F::DN) & 0x7fffffffu;
-    return min((u + (1u << (F::SH - 1))) >> F::SH, F::MASK);
-}
-template <int BITS> __device__ __forceinline__ scr_t code_widen(unsigned h)
-{
-    using F = CodeFmt<BITS>;
-    const float tbl = -(float)(h & 0x3fffu), ser = __uint_as_float((h & F::MASK) << F::SH) * F::UP;
-    return (h & F::FLAG) ? tbl : ser;
-}
 __device__ __forceinline__ pk4 pack4(const scr4 &v)
 {
     pk4 p;
-    if constexpr (CODE_BITS == 32) {
 #pragma unroll
-        for (int k = 0; k < 4; k++) p.w[k] = __float_as_uint(v.v[k]);
-    } else if constexpr (CODE_BITS == 16) {
-        p.w[0] = code_narrow<16>(v.v[0]) | (code_narrow<16>(v.v[1]) << 16);
-        p.w[1] = code_narrow<16>(v.v[2]) | (code_narrow<16>(v.v[3]) << 16);
-    } else {
-        const unsigned a = code_narrow<24>(v.v[0]), b = code_narrow<24>(v.v[1]), c = code_narrow<24>(v.v[2]), d = code_narrow<24>(v.v[3]);
-        p.w[0] = a | (b << 24); p.w[1] = (b >> 8) | (c << 16); p.w[2] = (c >> 16) | (d << 8);
-    }
+    for (int k = 0; k < 4; k++) p.w[k] = __float_as_uint(v.v[k]);
     return p;
 }
 __device__ __forceinline__ scr4 unpack4(const pk4 &p)
 {
     scr4 v;
-    if constexpr (CODE_BITS == 32) {
 #pragma unroll
-        for (int k = 0; k < 4; k++) v.v[k] = __uint_as_float(p.w[k]);
-    } else if constexpr (CODE_BITS == 16) {
-        v.v[0] = code_widen<16>(p.w[0] & 0xffffu); v.v[1] = code_widen<16>(p.w[0] >> 16);
-        v.v[2] = code_widen<16>(p.w[1] & 0xffffu); v.v[3] = code_widen<16>(p.w[1] >> 16);
-    } else {
-        v.v[0] = code_widen<24>(p.w[0] & 0xffffffu);
-        v.v[1] = code_widen<24>(__builtin_amdgcn_alignbit(p.w[1], p.w[0], 24) & 0xffffffu);
-        v.v[2] = code_widen<24>(__builtin_amdgcn_alignbit(p.w[2], p.w[1], 16) & 0xffffffu);
-        v.v[3] = code_widen<24>(p.w[2] >> 8);
-    }
+    for (int k = 0; k < 4; k++) v.v[k] = __uint_as_float(p.w[k]);
     return v;
 }
 typedef unsigned pk_vec __attribute__((ext_vector_type(CODE_WORDS)));
+// (Round 5 measured this store against a cached one, +0.3 ... +1.7 ms, and against two knock-outs with wrong results - codes formed and
+// not stored 17.6 ms, half of every record stored 20.3: profiles/round5_instruction_diet.md.)
 __device__ __forceinline__ void scr_store(unsigned *base, size_t cell, const scr4 &v)
 {
     const pk4 p = pack4(v);
     pk_vec x;
 #pragma unroll
     for (int k = 0; k < CODE_WORDS; k++) x[k] = p.w[k];
-#ifdef RRLW_KO_STORES       // knock-out (timing only, wrong results): the codes are formed - the empty asm keeps every one alive - and not stored
-    (void)base; (void)cell;
-#pragma unroll
-    for (int k = 0; k < CODE_WORDS; k++) asm volatile("" :: "v"(x[k]));
-    return;
-#endif
-#ifdef RRLW_KO_HALFSTORE    // knock-out (timing only, wrong results): half of every record is stored - as many store instructions, half the bytes
-    {
-        typedef unsigned v2h __attribute__((ext_vector_type(2)));
-        v2h lo = {p.w[0] ^ p.w[2], p.w[1] ^ p.w[3 % CODE_WORDS]};
-        __builtin_nontemporal_store(lo, reinterpret_cast<v2h *>(base + cell * 2));       // (contiguous: whole lines are written)
-        return;
-    }
-#endif
-#ifdef RRLW_NO_NT
-    __builtin_memcpy(base + cell * CODE_WORDS, &x, CODE_BYTES);
-#else
-    if constexpr (CODE_WORDS == 3) {        // (no 12-byte vector store through a pointer: 8 + 4)
-        typedef unsigned v2 __attribute__((ext_vector_type(2)));
-        v2 lo = {p.w[0], p.w[1]};
-        __builtin_nontemporal_store(lo, reinterpret_cast<v2 *>(base + cell * 3));
-        __builtin_nontemporal_store(p.w[2], base + cell * 3 + 2);
-    } else {
-        __builtin_nontemporal_store(x, reinterpret_cast<pk_vec *>(base + cell * CODE_WORDS));
-    }
-#endif
+    __builtin_nontemporal_store(x, reinterpret_cast<pk_vec *>(base + cell * CODE_WORDS));
 }
 // transmittance-table index of an optical depth: rtrn :445 (tblint = 10000, Pade constant bpade)
 __device__ __forceinline__ int lut_index(double od, double bpade) { return (int)(10000.0 * fdiv(od, bpade + od) + 0.5); }
@@ -1660,8 +1556,11 @@ __device__ __forceinline__ void band_cells(const DevTables &T, const Workspace &
         if (wave_cloudy) {
 #pragma unroll
             for (int j = 0; j < ng; j++) { if (!(od[j] >= 0.0)) od[j] = 0.0; }       // rtrn :369 (see above)
-            constexpr int QCW = CLOUD >= 2 ? 1 : RRLW_CLOUD_QUADS;
-            constexpr int QC = QCW < NQ ? QCW : NQ;
+            // QC: quads of a band whose cloudy-layer look-ups are in flight together (2 until round 5: with the quad-wise table indices
+            // two spill ten registers - profiles/round5_instruction_diet.md).  The loops over the QC quads of a group stay although QC is
+            // 1: written out for one quad the kernel compiles to other code (162 registers instead of 168, 3.6 KB more of it), which
+            // a change that is to leave the code object alone cannot take (profiles/switch_retirement.md).
+            constexpr int QC = 1;
 #pragma unroll
             for (int q0 = 0; q0 < NQ; q0 += QC) {
                 constexpr int GC = 4 * QC;
@@ -1926,15 +1825,11 @@ __device__ __forceinline__ void layer_band(const DevTables &T, const Workspace &
 // The staging passes: every band once, in evaluation order (bands that are the only users of some setcoef quantity - pavel, broadening
 // gases, O2, halocarbons, CO - first, the bands with the longest row lists last: their register peak then meets fewer live quantities).
 // A pass must fit the staging buffer in both regions of the atmosphere (static_assert in stage_pass).
+// (Measured against these four passes, 24.3 - 24.6 ms, in round 3: one staging round per band as before that round 25.9, three passes with
+// 384-thread workgroups and a 9 000-double buffer 40.6 against 23.6, one pass with one 768-thread workgroup per CU 25.6 -
+// profiles/round3_k_layer_stamps.md.)
 #ifdef RRLW_G256
 using LayerPasses = std::tuple<BandList<1, 2, 11, 15, 6>, BandList<8, 10, 14, 16>, BandList<12>, BandList<13>, BandList<4, 9>, BandList<7>, BandList<3>, BandList<5>>;
-#elif defined(RRLW_LAYER_PASS_PER_BAND)       // measurement: one staging round per band, as before round 3
-using LayerPasses = std::tuple<BandList<1>, BandList<2>, BandList<11>, BandList<15>, BandList<6>, BandList<8>, BandList<10>, BandList<14>, BandList<16>,
-                               BandList<12>, BandList<13>, BandList<4>, BandList<9>, BandList<7>, BandList<3>, BandList<5>>;
-#elif defined(RRLW_LAYER_PASSES_3)              // measurement: 384-thread workgroups with a 9 000-double buffer (two per CU)
-using LayerPasses = std::tuple<BandList<1, 2, 11, 15, 6, 8, 10, 14, 16, 12, 13, 4>, BandList<9, 7, 3>, BandList<5>>;
-#elif defined(RRLW_LAYER_PASSES_1)              // measurement: one 768-thread workgroup per CU, every table of the region staged at once
-using LayerPasses = std::tuple<BandList<1, 2, 11, 15, 6, 8, 10, 14, 16, 12, 13, 4, 9, 7, 3, 5>>;
 #else
 using LayerPasses = std::tuple<BandList<1, 2, 11, 15, 6, 8, 10, 14, 16, 12, 13>, BandList<4, 9>, BandList<7, 3>, BandList<5>>;
 #endif
@@ -2964,18 +2859,15 @@ __device__ __forceinline__ size_t spec_at(size_t gc, int lvl, int B, int nlay, i
 }
 
 // LDS of a sweep workgroup: transmittance table (float pairs), per band the Planck rows and the fraction rows
-#ifdef RRLW_SWEEP_EXPF
-constexpr int SWEEP_LUT_BYTES = 16;                   // no table in LDS
-#else
 constexpr int SWEEP_LUT_BYTES = 8 * (NTBL + 1) + 8;
-#endif
 constexpr int SWEEP_PL_BYTES = 2 * 184 * 8, SWEEP_FR_BYTES = 16 * 16 * 8;
 // Loads of the sweeps: wave-uniform base pointer in a buffer descriptor (scalar registers), per-lane 32-bit byte offset that does not
 // change from level to level - no 64-bit vector address arithmetic per load.  nt = streaming (non-temporal) access.
 // soff (round 5): the ROW of the level as a wave-uniform 32-bit byte offset in the instruction's scalar-offset operand.  Until then every
 // load of a level formed its row's 64-bit address (clamp, a signed 64-bit multiply by the row stride, the add, the descriptor's second
 // word: ~14 scalar instructions, ~106 per level and thread in k_sweepz), and the scalar stream is NOT hidden behind the vector one at
-// three waves per SIMD: 100 scalar instructions more per level cost the sweeps 10 % (knock-in, profiles/round5_instruction_diet.md).
+// three waves per SIMD: 100 scalar instructions more per level cost the sweeps 10 % (measured with a knock-in, n more dependent scalar
+// additions per level and thread: profiles/round5_instruction_diet.md).
 // Now the descriptor is built from the array's start (the compiler keeps it across the level loop) and a level costs the workspace arrays
 // one multiply for the row and a shift per element size; the rows of the caller's arrays, whose column stride is the whole call's column
 // count, keep a 64-bit address, formed from an unsigned 32 x 32 -> 64 bit product (row_ptr).  The driver keeps the end of every row inside
@@ -2988,18 +2880,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t sweep_rsrc(const void *base)
 __device__ __forceinline__ pk4 bload_pk4_nt(const void *base, unsigned voff, unsigned soff = 0u)
 {
     pk4 r;
-    if constexpr (CODE_WORDS == 4) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(sweep_rsrc(base), (int)voff, (int)soff, 2);
-        __builtin_memcpy(&r, &v, 16);
-    } else if constexpr (CODE_WORDS == 3) {
-        typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
-        const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(sweep_rsrc(base), (int)voff, (int)soff, 2);
-        r.w[0] = v[0]; r.w[1] = v[1]; r.w[2] = v[2];
-    } else {
-        typedef unsigned int u32x2_ __attribute__((ext_vector_type(2)));
-        const u32x2_ v = __builtin_amdgcn_raw_buffer_load_b64(sweep_rsrc(base), (int)voff, (int)soff, 2);
-        r.w[0] = v[0]; r.w[1] = v[1];
-    }
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(sweep_rsrc(base), (int)voff, (int)soff, 2);
+    __builtin_memcpy(&r, &v, 16);
     return r;
 }
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -3041,18 +2923,6 @@ __device__ __forceinline__ void bstore_f64x2(void *base, unsigned voff, double v
     __builtin_amdgcn_raw_buffer_store_b128(x, sweep_rsrc(base), (int)voff, 0, 0);
 }
 
-// Knock-IN (measurement, -DRRLW_KI_SALU=n): n more scalar instructions per level and thread in the sweeps, a dependent chain like the
-// address arithmetic of the level's loads - what the scalar stream costs is what adding to it costs (profiles/round5_instruction_diet.md).
-__device__ __forceinline__ void ki_salu(int &x)
-{
-#ifdef RRLW_KI_SALU
-#pragma unroll
-    for (int i = 0; i < RRLW_KI_SALU; i++) asm volatile("s_add_u32 %0, %0, 1" : "+s"(x));
-#else
-    (void)x;
-#endif
-}
-
 // table index of a cell's code (0 for the series branch: entry 0 is {1 - exp = 0, tfn = 0})
 // From here to the end of k_sweepz nothing is contracted behind the source's back: every fused multiply-add of the sweeps is written as
 // one (fma).  The two sweep kernels, and the copies of a level's body inside each (one per prefetch slot), must round a level alike -
@@ -3066,7 +2936,8 @@ __device__ __forceinline__ float code_od(scr_t c) { return __int_as_float(max(__
 // (1 - transmittance, tfn factor) of a cell from its code and the table entry at code_index: rtrn :439-451.  Branch-free: a table
 // cell adds the series terms of od = 0, a series cell adds the table terms of entry 0 - both exact zeros.  Float arithmetic up to the
 // two conversions (decode_f32: the part in float): the table values are floats already, and of the two summands one is an exact
-// zero; the series terms carry ~1e-7 relative error (od <= 0.06), the same class as the float table entries.
+// zero; the series terms carry ~1e-7 relative error (od <= 0.06), the same class as the float table entries.  (A float64
+// form of the same three operations was carried beside this one as a build switch and never selected; no profile holds numbers for it.)
 __device__ __forceinline__ void decode_f32(scr_t c, const float2 &e, float &atr, float &tfn)
 {
     const float od = code_od(c);
@@ -3075,36 +2946,19 @@ __device__ __forceinline__ void decode_f32(scr_t c, const float2 &e, float &atr,
 }
 __device__ __forceinline__ void decode(scr_t c, const float2 &e, double &atr, double &tfn)
 {
-#ifdef RRLW_DECODE_F64
-    const double od = (double)code_od(c);
-    atr = (double)e.x + fma(-0.5 * od, od, od);
-    tfn = fma(0.166667, od, (double)e.y);
-#else
     float fa, ft;
     decode_f32(c, e, fa, ft);
     atr = (double)fa;
     tfn = (double)ft;
-#endif
 }
 // Records that are all thin.  Above the clouds 96 % of the cells are series cells, and 89 % of the quad records a wave loads with one
 // 16-byte access hold series cells in all 64 lanes (profiles/sweepc_thin_records.md).  For those the table side of decode() - the index,
 // the LDS address, the gathered read of entry 0 = {0, 0}, the clamp and the two additions of zero - produces nothing.  k_sweepc tests
-// per record whether every code of the wave has its sign bit clear and then takes decode_thin (RRLW_SWEEPC_THIN = 1; 0 = decode()
-// everywhere; RRLW_SWEEPC_THIN_P1: the same choice for the downward phase above the clouds alone).  One test per thread and level
+// per record whether every code of the wave has its sign bit clear and then takes decode_thin.  (decode() for every record, the body before
+// this one, was 57.85 against 56.75 ms a step; the downward phase above the clouds does not lose with the thin body and needed no choice
+// of its own: profiles/sweepc_thin_records.md.)  One test per thread and level
 // over all of its records, with two straight-line bodies, spilled registers in the downward phase of the 12- and 16-g-point bands and
-// was not kept.  The reduced code widths and the two numerics variants of decode() keep the general body.
-#ifndef RRLW_SWEEPC_THIN
-#define RRLW_SWEEPC_THIN 1
-#endif
-#ifndef RRLW_SWEEPC_THIN_P1
-#define RRLW_SWEEPC_THIN_P1 RRLW_SWEEPC_THIN
-#endif
-#if defined(RRLW_DECODE_F64) || defined(RRLW_SWEEP_EXPF)
-constexpr bool SWEEPC_THIN_OK = false;
-#else
-constexpr bool SWEEPC_THIN_OK = CODE_BITS == 32;
-#endif
-__host__ __device__ constexpr int sweepc_thin(int PHASE) { return !SWEEPC_THIN_OK ? 0 : (PHASE == 1 ? RRLW_SWEEPC_THIN_P1 : RRLW_SWEEPC_THIN) ? 1 : 0; }
+// was not kept.
 // decode_f32() of a series cell (sign bit of the code clear: the code is the optical depth, code_index is 0).  Rounds like decode_f32():
 // there e.x = +0.0f is added to a float that is never negative (od <= 0.06) and comes out +0 at od = 0 - the sum is that float, bit for
 // bit - and fmaf(0.166667f, od, +0.0f) rounds the one product 0.166667f * od; the float denormal mode is the same for all of these.
@@ -3116,27 +2970,9 @@ __device__ __forceinline__ void decode_thin(scr_t od, float &atr, float &tfn)
 // no code of the wave's lanes in these records is a table code: a wave-uniform (scalar) condition, the exec mask stays whole.  A negative
 // float - a table code, -0.0f included - is a negative integer.
 __device__ __forceinline__ bool wave_all_thin(unsigned orw) { return __builtin_amdgcn_ballot_w64((int)orw < 0) == 0ull; }
-// RRLW_SWEEP_EXPF (measurement variant, north_star "__builtin_amdgcn_expf for transmittance"): the table entry of index i evaluated
-// instead of looked up - the same closed forms rrtmg_lw_ini tabulates (src/rrtmg_lw_init.f90:125-142: t = i / 1e4,
-// tau = bpade t / (1 - t), 1 - exp(-tau), tfn = tau / 6 below 0.06 else 1 - 2 (1 / tau - exp / (1 - exp))) in float32 with the hardware
-// exp2 / rcp.  The INDEX is still the reference's (formed in float64 by k_layer).  Frees the table's 80 KB of LDS; costs ~12 more
-// instructions per cell (4 of them transcendental) and float32 cancellation in 1 - exp and in tfn.  Measured: profiles/round2_expf.md.
-__device__ __forceinline__ float2 lut_entry_expf(unsigned idx, float bpade)
-{
-    const float t = (float)idx * 1.0e-4f;
-    const float tau = bpade * t * __builtin_amdgcn_rcpf(1.0f - t);                    // idx = 10000 -> +inf -> exp = 0, entry {1, 1}
-    const float ex = __builtin_amdgcn_exp2f(-1.44269504088896f * tau);
-    const float atr = 1.0f - ex;
-    float tfn = tau < 0.06f ? tau * (1.0f / 6.0f) : 1.0f - 2.0f * (__builtin_amdgcn_rcpf(tau) - ex * __builtin_amdgcn_rcpf(atr));
-    if (idx == 0u) tfn = 0.0f;                                                         // entry 0 = {0, 0} (series cells)
-    if (idx >= 10000u) tfn = 1.0f;
-    return make_float2(idx == 0u ? 0.0f : atr, tfn);
-}
-#ifdef RRLW_SWEEP_EXPF
-#define RRLW_LUT_ENTRY(lut, idx) lut_entry_expf((idx), 3.5971223f)
-#else
-#define RRLW_LUT_ENTRY(lut, idx) (lut)[(idx)]
-#endif
+// (The table entry evaluated instead of looked up - the closed forms rrtmg_lw_ini tabulates, src/rrtmg_lw_init.f90:125-142, in float32
+// with the hardware exp2 / rcp - frees the table's 80 KB of LDS and costs ~12 more instructions per cell, 4 of them transcendental, and
+// float32 cancellation in 1 - exp and in tfn.  Measured and not kept: profiles/round2_n1_expf.md.)
 
 // integrated Planck function at temperature t from one band's row of totplnk: setcoef :173-269
 __device__ __forceinline__ double planck_at(const double *tp, const double *tq, double t)
@@ -3155,11 +2991,7 @@ __device__ __forceinline__ void sweep_stage_lut(const DevTables &T, unsigned cha
     const double2 *src = reinterpret_cast<const double2 *>(T.stat + T.sl.lutf);
     double2 *dst = reinterpret_cast<double2 *>(smem);
     // (loads first, then the LDS writes, eight at a time: a plain copy loop waits for every load before it issues the next)
-#ifdef RRLW_SWEEP_EXPF
-    constexpr int NLUT = 0;
-#else
     constexpr int NLUT = SWEEP_LUT_BYTES / 16;
-#endif
     for (int i0 = tid; i0 < NLUT; i0 += 8 * nth) {
         double2 v[8];
 #pragma unroll
@@ -3230,9 +3062,6 @@ constexpr int NGROUP_MAX = 8;
 constexpr int SWEEPC_BAND_BYTES = SWEEP_PL_BYTES + SWEEP_FR_BYTES;
 // values per band, level and column in the reduction buffer: total [, clear] [, their d/dT]
 __host__ __device__ constexpr int sweepc_nval(int PHASE, bool IDRV) { return (PHASE == 2 ? 2 : 1) * ((IDRV && PHASE != 1) ? 2 : 1); }
-#ifndef RRLW_SWEEPC_QUAD_BARRIER
-#define RRLW_SWEEPC_QUAD_BARRIER 0   // 1: keep the quads of a level apart in the instruction schedule (fewer registers, less overlap; measured slower)
-#endif
 #ifndef RRLW_SWEEPC_CODES
 #define RRLW_SWEEPC_CODES 2       // code slots: levels of cell codes in flight (the codes are the one HBM stream of the sweep; 4 registers per quad and slot)
 #endif
@@ -3242,22 +3071,13 @@ __host__ __device__ constexpr int sweepc_lds_bytes(int PHASE, bool IDRV, int nb,
     return SWEEP_LUT_BYTES + nb * SWEEPC_BAND_BYTES + 2 * sweepc_nval(PHASE, IDRV) * nb * NT * RRLW_SWEEPC_CODES * nsb * 64 * 8;
 }
 // threads per band: two where a band's 16 g-points with two streams would otherwise leave one wave per SIMD
-#ifndef RRLW_SWEEPC_SPLIT
-#define RRLW_SWEEPC_SPLIT 1
-#endif
-#ifndef RRLW_SWEEPC_SPLIT3
-#define RRLW_SWEEPC_SPLIT3 0
-#endif
-__host__ __device__ constexpr int sweepc_nt(int NQ, int PHASE, bool IDRV)
+__host__ __device__ constexpr int sweepc_nt(int NQ, int PHASE)
 {
     // 12 g-points x {total, clear} x {radiance, d/dT} in one thread need 256 registers + 70 accumulation registers as spill space: one wave
-    // per SIMD.  Three threads of one quad (RRLW_SWEEPC_SPLIT3 = 1: three waves per SIMD, nothing spilled) repeat the level's Planck terms,
-    // fraction rows and temperature loads three times: 8.26 ms against 5.59 per 5e5 137-layer columns - the one-wave form stays.
-    if (RRLW_SWEEPC_SPLIT3 && NQ == 3 && PHASE == 2 && IDRV) return 3;
-#ifdef RRLW_SWEEPC_SPLIT_P1       // measurement: the downward clear-sky sweep of the 16-g-point bands on two threads as well
-    if (RRLW_SWEEPC_SPLIT && NQ == 4) return 2;
-#endif
-    return (RRLW_SWEEPC_SPLIT && NQ == 4 && (PHASE == 2 || PHASE == 0)) ? 2 : 1;
+    // per SIMD.  Three threads of one quad (three waves per SIMD, nothing spilled) repeat the level's Planck terms, fraction rows and
+    // temperature loads three times: 8.26 ms against 5.59 per 5e5 137-layer columns - the one-wave form stays.  (The downward clear-sky
+    // sweep of the 16-g-point bands on two threads as well was measured too and stays on one.)
+    return (NQ == 4 && (PHASE == 2 || PHASE == 0)) ? 2 : 1;
 }
 // bands per group: what fits the wave slots of the most register-hungry instantiation (phase 2 with d/dT)
 __host__ __device__ constexpr int sweepc_group_cap(int NQ)
@@ -3267,7 +3087,7 @@ __host__ __device__ constexpr int sweepc_group_cap(int NQ)
         for (int i = 0; i < 2; i++) {
             if (ph == 1 && i == 1) continue;
             const bool idrv = i == 1;
-            const int nt = sweepc_nt(NQ, ph, idrv), w = 4 * sweepc_waves(NQ / nt, ph, idrv) / nt;      // wave slots
+            const int nt = sweepc_nt(NQ, ph), w = 4 * sweepc_waves(NQ / nt, ph, idrv) / nt;      // wave slots
             if (w < cap) cap = w;
             while (cap > 1 && sweepc_lds_bytes(ph, idrv, cap, 1, nt) > SWEEPC_LDS_MAX) cap--;           // reduction buffer
         }
@@ -3276,7 +3096,7 @@ __host__ __device__ constexpr int sweepc_group_cap(int NQ)
 // column sub-blocks per workgroup for a group of nb bands
 __host__ __device__ constexpr int sweepc_nsb(int NQ, int PHASE, bool IDRV, int nb)
 {
-    const int nt = sweepc_nt(NQ, PHASE, IDRV);
+    const int nt = sweepc_nt(NQ, PHASE);
     int nsb = nsb_fit(4 * sweepc_waves(NQ / nt, PHASE, IDRV) / (nb * nt));         // (a divisor of SORT_GROUP: workgroups never straddle hand-off groups)
     while (nsb > 1 && sweepc_lds_bytes(PHASE, IDRV, nb, nsb, nt) > SWEEPC_LDS_MAX) nsb = nsb_fit(nsb - 1);
     return nsb;
@@ -3314,7 +3134,7 @@ __device__ __forceinline__ double times(double x, double y)
 template <int NQ, int PHASE, bool IDRV, int NT = 1, bool SPEC = false>
 __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_waves(NQ / NT, PHASE, IDRV)) void k_sweepc(DevTables T, Workspace W, SweepArgs a)
 {
-    static_assert(NQ % NT == 0 && (NT == 1 || NT == 2 || NT == 3), "threads per band");
+    static_assert(NQ % NT == 0 && (NT == 1 || NT == 2), "threads per band");
     constexpr int G = NQ / NT, NG = 4 * G, NC = RRLW_SWEEPC_CODES;
     constexpr bool DOWN = PHASE != 2, UP = PHASE != 1, TWO = PHASE == 2;       // TWO: total and clear-sky streams differ
     constexpr int NVAL = sweepc_nval(PHASE, IDRV);
@@ -3440,8 +3260,7 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
                 double sum = 0.0;
                 for (int q = 0; q < nb; q++) {
                     double pq = r[(unsigned)(q * NT * NC * ncw)];            // (the band's parts in the order one thread adds its quads: pairs first)
-                    if constexpr (NT >= 2) pq = pq + r[(unsigned)((q * NT + 1) * NC * ncw)];
-                    if constexpr (NT == 3) pq = pq + r[(unsigned)((q * NT + 2) * NC * ncw)];
+                    if constexpr (NT == 2) pq = pq + r[(unsigned)((q * NT + 1) * NC * ncw)];
                     const int bq = (int)((bands >> (4 * q)) & 15ull);
                     double v = (pq * 0.5) * T.delwave[bq];
                     if (deriv) v = v * T.fluxfac;
@@ -3481,11 +3300,9 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
     SweepcLev<G> cur;
     cur.w = 0u;
     pk4 cc[G][NC];
-    int ki = 0;
     auto level = [&](auto bin_tag, auto dn_tag, int lev, int slot) {
         constexpr bool BIN = decltype(bin_tag)::value, DN = decltype(dn_tag)::value;
         constexpr int dir = DN ? -1 : 1;
-        ki_salu(ki);
         double fpl;
         const double *row = frac_row(lev, cur.w, fpl);
         const double blay = planck_at(tp0, tp0, cur.tl);
@@ -3494,61 +3311,39 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
         // (sums as a tree - pairs inside a quad, then the quads: a running sum over 16 g-points is a chain of 16 dependent additions, and a
         // wave issues in order, so each of them would hold the wave for the latency of the one before)
         double qs[G], qsc[G], qd[G], qdc[G];
-        // MODE 0: every cell through decode().  1: a record whose codes are series codes in all 64 lanes takes decode_thin - only the
-        // transmittance terms sit in the (scalar) branch, the level's loads and the recurrences are common to both sides.
-        constexpr int MODE = sweepc_thin(PHASE);
+        // A record whose codes are series codes in all 64 lanes takes decode_thin - only the transmittance terms sit in the (scalar)
+        // branch, the level's loads and the recurrences are common to both sides.
 #pragma unroll
         for (int k = 0; k < G; k++) {
-            float2 e[4];
             pk4 pk;
 #pragma unroll
             for (int c = 0; c < NC; c++) if (c == slot) pk = cc[k][c];
             const scr4 ck = unpack4(pk);
-            bool thin = false;
-            if constexpr (MODE == 1) {
-                unsigned orw = pk.w[0];
+            unsigned orw = pk.w[0];
 #pragma unroll
-                for (int i = 1; i < CODE_WORDS; i++) orw |= pk.w[i];
-                thin = wave_all_thin(orw);
-            }
-            if constexpr (MODE == 0) {
-#pragma unroll
-                for (int jj = 0; jj < 4; jj++) e[jj] = RRLW_LUT_ENTRY(s_lut, code_index(ck.v[jj]));
-            }
-            if constexpr (MODE == 0) {
-                const pk4 nx = ld_c(lev + NC * dir, k);
-#pragma unroll
-                for (int c = 0; c < NC; c++) if (c == slot) cc[k][c] = nx;
-            }
+            for (int i = 1; i < CODE_WORDS; i++) orw |= pk.w[i];
+            const bool thin = wave_all_thin(orw);
             // (floats across the join, widened behind it: four registers per quad more than the codes they replace)
             float fa[4], ft[4];
-            if constexpr (MODE == 1) {
-                if (thin) {
+            if (thin) {
 #pragma unroll
-                    for (int jj = 0; jj < 4; jj++) decode_thin(ck.v[jj], fa[jj], ft[jj]);
-                } else {
+                for (int jj = 0; jj < 4; jj++) decode_thin(ck.v[jj], fa[jj], ft[jj]);
+            } else {
+                float2 e[4];
 #pragma unroll
-                    for (int jj = 0; jj < 4; jj++) e[jj] = RRLW_LUT_ENTRY(s_lut, code_index(ck.v[jj]));
+                for (int jj = 0; jj < 4; jj++) e[jj] = s_lut[code_index(ck.v[jj])];
 #pragma unroll
-                    for (int jj = 0; jj < 4; jj++) decode_f32(ck.v[jj], e[jj], fa[jj], ft[jj]);
-                }
+                for (int jj = 0; jj < 4; jj++) decode_f32(ck.v[jj], e[jj], fa[jj], ft[jj]);
             }
-            if constexpr (MODE == 1) {
-                // (behind the branch, where the record's codes have been consumed: issued in front of it, while they are live, the load
-                // cannot go to their registers, the slots rotate through copies at the end of a round and those wait for every load)
-                const pk4 nx = ld_c(lev + NC * dir, k);
+            // (behind the branch, where the record's codes have been consumed: issued in front of it, while they are live, the load
+            // cannot go to their registers, the slots rotate through copies at the end of a round and those wait for every load)
+            const pk4 nx = ld_c(lev + NC * dir, k);
 #pragma unroll
-                for (int c = 0; c < NC; c++) if (c == slot) cc[k][c] = nx;
-            }
+            for (int c = 0; c < NC; c++) if (c == slot) cc[k][c] = nx;
 #pragma unroll
             for (int jj = 0; jj < 4; jj++) {
                 const int j = 4 * k + jj;
-                double atr, tfn;
-                if constexpr (MODE == 0) decode(ck.v[jj], e[jj], atr, tfn);
-                else {
-                    atr = (double)fa[jj];
-                    tfn = (double)ft[jj];
-                }
+                const double atr = (double)fa[jj], tfn = (double)ft[jj];
                 double fr = row[j];
                 if constexpr (BIN) fr = fma(fpl, row[16 + j] - fr, fr);
                 const double bb = fr * fma(tfn, dpl, blay);
@@ -3566,18 +3361,15 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
                 qd[k] = (drad[4 * k] + drad[4 * k + 1]) + (drad[4 * k + 2] + drad[4 * k + 3]);
                 if constexpr (TWO) qdc[k] = (dradc[4 * k] + dradc[4 * k + 1]) + (dradc[4 * k + 2] + dradc[4 * k + 3]);
             }
-            if (RRLW_SWEEPC_QUAD_BARRIER) __builtin_amdgcn_sched_barrier(0);
-            if constexpr (MODE == 1) {
-                // (the quad's recurrences stay in front of the next record's branch: sunk behind it - their results are not used before
-                // the end of the level - the transmittance terms of every quad of the level are live across the branches, 16 registers
-                // per quad)
+            // (the quad's recurrences stay in front of the next record's branch: sunk behind it - their results are not used before
+            // the end of the level - the transmittance terms of every quad of the level are live across the branches, 16 registers
+            // per quad.  A scheduling barrier per quad instead - fewer registers, less overlap - was measured slower.)
 #pragma unroll
-                for (int jj = 0; jj < 4; jj++) {
-                    asm volatile("" : "+v"(rad[4 * k + jj]));
-                    if constexpr (TWO && !DN) asm volatile("" : "+v"(radc[4 * k + jj]));
-                    if constexpr (IDRV && !DN) asm volatile("" : "+v"(drad[4 * k + jj]));
-                    if constexpr (IDRV && TWO && !DN) asm volatile("" : "+v"(dradc[4 * k + jj]));
-                }
+            for (int jj = 0; jj < 4; jj++) {
+                asm volatile("" : "+v"(rad[4 * k + jj]));
+                if constexpr (TWO && !DN) asm volatile("" : "+v"(radc[4 * k + jj]));
+                if constexpr (IDRV && !DN) asm volatile("" : "+v"(drad[4 * k + jj]));
+                if constexpr (IDRV && TWO && !DN) asm volatile("" : "+v"(dradc[4 * k + jj]));
             }
         }
         auto tree = [&](const double (&q)[G]) -> double {
@@ -3711,26 +3503,18 @@ __global__ __launch_bounds__(256 * sweepc_waves(NQ / NT, PHASE, IDRV), sweepc_wa
 //            1.9x the time per clear level (per-quad duplication of the level's Planck terms, conditional loads with full waits, two
 //            barriers per four levels).
 // ------------------------------------------------------------------------------------------------
-#ifndef RRLW_SWEEPZ_CT_SLOTS
-#define RRLW_SWEEPZ_CT_SLOTS 1
-#endif
-#ifndef RRLW_SWEEPZ_G2
-#define RRLW_SWEEPZ_G2 0          // 1: two quads per thread for bands of 4 and 2 quads (253 registers, two waves per SIMD: measured slower)
-#endif
-__host__ __device__ constexpr int sweepz_g(int NQ) { return (RRLW_SWEEPZ_G2 && (NQ == 4 || NQ == 2)) ? 2 : 1; }          // quads per thread
-__host__ __device__ constexpr int sweepz_nt(int NQ) { return NQ / sweepz_g(NQ); }                    // threads (waves) per band
-#ifndef RRLW_SWEEPZ_WAVES_G2
-#define RRLW_SWEEPZ_WAVES_G2 2
-#endif
+// One quad per thread, so a band of NQ quads takes NQ threads (waves).  (Two quads per thread for the bands of 4 and 2 quads: 253
+// registers, two waves per SIMD - measured slower.)
+__host__ __device__ constexpr int sweepz_nt(int NQ) { return NQ; }
 #ifndef RRLW_SWEEPZ_WAVES_G1
 #define RRLW_SWEEPZ_WAVES_G1 3
 #endif
 #ifndef RRLW_SWEEPZ_WAVES_IDRV
 #define RRLW_SWEEPZ_WAVES_IDRV 2          // with d(flux)/dT: 16 more state registers per thread
 #endif
-__host__ __device__ constexpr int sweepz_waves(int NQ, bool IDRV = false)
+__host__ __device__ constexpr int sweepz_waves(int /* NQ */, bool IDRV = false)
 {
-    return IDRV ? RRLW_SWEEPZ_WAVES_IDRV : (sweepz_g(NQ) == 2 ? RRLW_SWEEPZ_WAVES_G2 : RRLW_SWEEPZ_WAVES_G1);
+    return IDRV ? RRLW_SWEEPZ_WAVES_IDRV : RRLW_SWEEPZ_WAVES_G1;
 }
 __host__ __device__ constexpr int sweepz_lds_bytes(int nb, int nsb, int NT, bool IDRV = false)
 {
@@ -3763,7 +3547,8 @@ template <int NQ, int MODE, bool IDRV = false, bool SPEC = false>
 __global__ __launch_bounds__(256 * sweepz_waves(NQ, IDRV), sweepz_waves(NQ, IDRV)) void k_sweepz(DevTables T, Workspace W, SweepArgs a)
 {
     static_assert(MODE >= 1 && MODE <= 4, "modes of the cloud-zone sweep");
-    constexpr int G = sweepz_g(NQ), NT = sweepz_nt(NQ), NG = 4 * G, NC = RRLW_SWEEPC_CODES, NVAL = IDRV ? 4 : 2;
+    // G: quads per thread.  One; the arrays and loops over G are k_sweepc's form of the level body, kept (profiles/switch_retirement.md).
+    constexpr int G = 1, NT = sweepz_nt(NQ), NG = 4 * G, NC = RRLW_SWEEPC_CODES, NVAL = IDRV ? 4 : 2;
     constexpr int NS2 = MODE == 2 ? NG : 1;          // rtrnmr's extra state
     constexpr int NSD = IDRV ? NG : 1;               // d/dT state
     extern __shared__ __align__(16) unsigned char smem[];
@@ -3926,18 +3711,14 @@ __global__ __launch_bounds__(256 * sweepz_waves(NQ, IDRV), sweepz_waves(NQ, IDRV
 
     SweepzLev cur;
     cur.w = 0u;
-    // code slots: NC levels of the gas codes in flight, NCT of the total (gas + cloud) ones (a second slot of those put the rtrnmr
+    // code slots: NC levels of the gas codes in flight, one of the total (gas + cloud) ones (a second slot of those put the rtrnmr
     // instantiations 3-5 registers over their 168: scratch reloads count in vmcnt and drain the prefetches)
-    constexpr int NCT = RRLW_SWEEPZ_CT_SLOTS;
-    static_assert(NCT == 1 || NCT == NC, "slots of the total-optical-depth codes");
-    pk4 cc[G][NC], ct[G][NCT];
+    pk4 cc[G][NC], ct[G];
     // One level.  DN: downward (Planck difference towards the interface below, partial of level lev - 1, istcldd = flag bit 1), else
     // upward (istcld = bit 2).  The overlap factors of the level are requested first and used last.
-    int ki = 0;
     auto level = [&](auto bin_tag, auto dn_tag, int lev, int slot) __attribute__((always_inline)) {
         constexpr bool BIN = decltype(bin_tag)::value, DN = decltype(dn_tag)::value;
         constexpr int dir = DN ? -1 : 1;
-        ki_salu(ki);
         double2 f0 = make_double2(0., 0.), f1 = f0, f2 = f0;
         double efcl = 0.0;
         unsigned mlo = 0u, mhi = 0u;
@@ -3982,19 +3763,19 @@ __global__ __launch_bounds__(256 * sweepz_waves(NQ, IDRV), sweepz_waves(NQ, IDRV
         for (int k = 0; k < G; k++) {
             pk4 pk, pkt;
 #pragma unroll
-            for (int c = 0; c < NC; c++) if (c == slot) { pk = cc[k][c]; pkt = ct[k][NCT == 1 ? 0 : c]; }
+            for (int c = 0; c < NC; c++) if (c == slot) { pk = cc[k][c]; pkt = ct[k]; }
             const scr4 ck = unpack4(pk), ckt = unpack4(pkt);
             float2 e[4], et[4];
 #pragma unroll
-            for (int jj = 0; jj < 4; jj++) e[jj] = RRLW_LUT_ENTRY(s_lut, code_index(ck.v[jj]));
+            for (int jj = 0; jj < 4; jj++) e[jj] = s_lut[code_index(ck.v[jj])];
             if (anycld) {
 #pragma unroll
-                for (int jj = 0; jj < 4; jj++) et[jj] = RRLW_LUT_ENTRY(s_lut, min(code_index(ckt.v[jj]), (unsigned)NTBL));
+                for (int jj = 0; jj < 4; jj++) et[jj] = s_lut[min(code_index(ckt.v[jj]), (unsigned)NTBL)];
             }
             {
-                const pk4 nx = ld_c(sC, lev + NC * dir, k), nxt = ld_c(sCt, lev + NCT * dir, k);
+                const pk4 nx = ld_c(sC, lev + NC * dir, k), nxt = ld_c(sCt, lev + dir, k);
 #pragma unroll
-                for (int c = 0; c < NC; c++) if (c == slot) { cc[k][c] = nx; ct[k][NCT == 1 ? 0 : c] = nxt; }
+                for (int c = 0; c < NC; c++) if (c == slot) { cc[k][c] = nx; ct[k] = nxt; }
             }
 #pragma unroll
             for (int jj = 0; jj < 4; jj++) {
@@ -4067,8 +3848,8 @@ __global__ __launch_bounds__(256 * sweepz_waves(NQ, IDRV), sweepz_waves(NQ, IDRV
             qsc[k] = (radc[4 * k] + radc[4 * k + 1]) + (radc[4 * k + 2] + radc[4 * k + 3]);
         }
         if constexpr (DN) seen = seen || cloudy;
-        if constexpr (G == 1) { red_put(slot, 0, qs[0]); red_put(slot, 1, qsc[0]); }
-        else { red_put(slot, 0, qs[0] + qs[1]); red_put(slot, 1, qsc[0] + qsc[1]); }
+        red_put(slot, 0, qs[0]);
+        red_put(slot, 1, qsc[0]);
         if constexpr (IDRV && !DN) {
             double ds = 0.0, dsc = 0.0;
 #pragma unroll
@@ -4100,7 +3881,7 @@ __global__ __launch_bounds__(256 * sweepz_waves(NQ, IDRV), sweepz_waves(NQ, IDRV
             const scr4 ck = unpack4(pk);
             float2 e[4];
 #pragma unroll
-            for (int jj = 0; jj < 4; jj++) e[jj] = RRLW_LUT_ENTRY(s_lut, code_index(ck.v[jj]));
+            for (int jj = 0; jj < 4; jj++) e[jj] = s_lut[code_index(ck.v[jj])];
             {
                 const pk4 nx = ld_c(sC, lev + NC * dir, k);
 #pragma unroll
@@ -4127,8 +3908,8 @@ __global__ __launch_bounds__(256 * sweepz_waves(NQ, IDRV), sweepz_waves(NQ, IDRV
             qs[k] = (rad[4 * k] + rad[4 * k + 1]) + (rad[4 * k + 2] + rad[4 * k + 3]);
             qsc[k] = (radc[4 * k] + radc[4 * k + 1]) + (radc[4 * k + 2] + radc[4 * k + 3]);
         }
-        if constexpr (G == 1) { red_put(slot, 0, qs[0]); red_put(slot, 1, qsc[0]); }
-        else { red_put(slot, 0, qs[0] + qs[1]); red_put(slot, 1, qsc[0] + qsc[1]); }
+        red_put(slot, 0, qs[0]);
+        red_put(slot, 1, qsc[0]);
         if constexpr (IDRV && !DN) {
             double ds = 0.0, dsc = 0.0;
 #pragma unroll
@@ -4151,7 +3932,7 @@ __global__ __launch_bounds__(256 * sweepz_waves(NQ, IDRV), sweepz_waves(NQ, IDRV
 #pragma unroll
             for (int k = 0; k < G; k++) {
                 cc[k][c] = ld_c(sC, first + c * dir, k);
-                if constexpr (!LITE) { if (c < NCT) ct[k][c] = ld_c(sCt, first + c * dir, k); }
+                if constexpr (!LITE) { if (c == 0) ct[k] = ld_c(sCt, first, k); }
             }
         }
         auto one = [&](int lev, int slot) __attribute__((always_inline)) {
@@ -4255,11 +4036,9 @@ __global__ __launch_bounds__(64 * N1_WAVES) void k_n1(DevTables T, Workspace W, 
     double *s_dn = reinterpret_cast<double *>(wbase + 16 * 32), *s_up = s_dn + (nlay + 1);
     {   // stage: transmittance table, every band's Planck row and fraction rows
         const int tid = threadIdx.x, nth = 64 * N1_WAVES;
-#ifndef RRLW_SWEEP_EXPF
         const double2 *src = reinterpret_cast<const double2 *>(T.stat + T.sl.lutf);
         double2 *dst = reinterpret_cast<double2 *>(smem);
         for (int i = tid; i < SWEEP_LUT_BYTES / 16; i += nth) dst[i] = src[i];
-#endif
         for (int i = tid; i < 16 * 181; i += nth) s_pl[i / 181][i % 181] = T.stat[T.sl.totplnk + i];
         for (int i = tid; i < 16 * 16 * 16; i += nth) {
             const int b = i >> 8, r = (i >> 4) & 15, g = i & 15;
@@ -4334,7 +4113,7 @@ __global__ __launch_bounds__(64 * N1_WAVES) void k_n1(DevTables T, Workspace W, 
         for (int p = 0; p < NP1; p++) {
             const scr_t cj = ok[p] ? codes[coff[p] + (size_t)(lev - 1) * ncb * 4] : (scr_t)0;
             double atr, tfn;
-            decode(cj, RRLW_LUT_ENTRY(s_lut, code_index(cj)), atr, tfn);
+            decode(cj, s_lut[code_index(cj)], atr, tfn);
             const int b = bnd[p];
             const double blay = s_pk[4 * b], dpl = s_pk[4 * b + 1], fpl = s_pk[4 * b + 2];
             const int r0 = (int)s_pk[4 * b + 3];

@@ -2,7 +2,7 @@
 """Debugging aid (profiles/round5_exec_hazard.md): read k_layer's cell codes back after a call with the narrow staging window only and after
 one with the wide window, and list the (record, layer, column) triples that differ.  Needs a tuning build with the read-back entry:
     tools/build_variant.sh dump "-DRRLW_TUNE -DRRLW_DBG_DUMP"
-    RRTMG_LW_ALLOW_TUNE_BUILD=1 RRTMG_LW_HIP_LIB=$PWD/exp/lib_dump.so python tools/dbg_codes.py [col0:ncol ...]"""
+    RRTMG_LW_HIP_LIB=$PWD/exp/lib_dump.so python tools/dbg_codes.py [col0:ncol ...]"""
 import sys, os, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -504,8 +504,8 @@ int rrtmg_lw_hip_gas_optics_columns(int ncol, int nlayers, int idrv,
  * The batch's arrays are staged in device memory the library owns (counted in rrtmg_lw_hip_workspace_bytes; per column of a batch the
  * float64 reference form of the call's arrays, taucld as one band sum per cell where inflglw >= 1; the fused McICA entry also holds play,
  * cldfr and alpha of the whole call for its generator).  The batches run one after the other on `stream`; such calls are not replayed as
- * graphs.  Out of scope: the host-pointer entries (their row scans compare 8-byte patterns; Fortran hosts are column-fastest anyway),
- * the explicit-sub-column McICA entries, the spectral outputs and the queue. */
+ * graphs.  Out of scope: the explicit-sub-column McICA entries, the spectral outputs and the queue; HOST arrays of a host built with
+ * 4-byte reals have entries of their own (the "_r4" section below; reference layout only - a Fortran host is column-fastest by nature). */
 typedef struct {
     int real_bytes;
     int layer_fastest;
@@ -579,6 +579,65 @@ int rrtmg_lw_hip_adjust_tsfc_device_as(const rrtmg_lw_hip_array_form *form, int 
     const void *uflx, const void *dflx, const void *duflx_dt,
     const void *uflxc, const void *dflxc, const void *duflxc_dt,
     void *uflx_adj, void *hr_adj, void *uflxc_adj, void *hrc_adj, void *stream);
+
+/* ---- Host arrays of a host built with 4-byte reals ("_r4") ----------------------------------------------------------------------------
+ * A host model that carries RRTMG_LW at the default real kind (no -r8) owns float arrays.  These four entries take them as they are:
+ * HOST pointers, every floating-point array of the call - inputs and outputs, alpha too - `float`.  Layout, argument order, the in/out
+ * behaviour of icld and irng, flags, NULL rules, error codes and error texts are those of the float64 entry each is named after.
+ * Results: what the float64 entry returns on the same values widened to double, each output rounded to nearest ((float)x), bit for bit.
+ * The solver works in float64 as always; the float64 entries are what they were.
+ *   rrtmg_lw_hip_run_nomcica_r4        as rrtmg_lw_hip_run_nomcica.  Takes the entry lock: a small call does NOT join the combining of
+ *                                      concurrent small calls (like the spectral entries).
+ *   rrtmg_lw_hip_run_mcica_r4          as rrtmg_lw_hip_run_mcica (explicit (140,ncol,nlay) sub-column arrays).
+ *   rrtmg_lw_hip_run_mcica_subcol_r4   as rrtmg_lw_hip_run_mcica_subcol (fused generator + solver); no combining either.
+ *   rrtmg_lw_hip_adjust_tsfc_r4        as rrtmg_lw_hip_adjust_tsfc: the arithmetic in float64 on the widened values, as
+ *                                      rrtmg_lw_hip_adjust_tsfc_device_as defines it for real_bytes = 4.
+ * All four take the entry lock, split their columns over the devices of rrtmg_lw_hip_init_devices and run through the pipeline of the
+ * float64 host entries with 4-byte elements: a row that holds one 4-byte pattern for all columns of a batch does not travel (its widened
+ * value is filled in on the device), every other row crosses as float32 - from where it lies when the array is registered, packed by the
+ * host threads when it is pageable - into a float32 landing area of the staging set and is widened there by one kernel per batch; the
+ * active outputs are rounded into the landing area by one kernel per batch and leave as float32.  With inflglw >= 1 the band sum of
+ * taucld is formed on the host in float64 on the widened values, in the reference's band order.  rrtmg_lw_hip_host_register /
+ * _is_registered / _static / _changed take byte ranges: pass 4 bytes per element.  An address declared static and later passed with the
+ * other element type is scanned anew.
+ * Workspace: the landing area - per column of a batch 4 bytes for every input value and every active output value - beside the float64
+ * staging arrays (8 bytes each), four staging sets; counted in rrtmg_lw_hip_workspace_bytes.
+ * Out of scope: the spectral outputs, the chunk queue, the prepared-column entries, the gas-optics entries, the stand-alone generator and
+ * get_alpha (the Fortran layer covers those two by conversion), and any array layout other than the reference's. */
+int rrtmg_lw_hip_run_nomcica_r4(
+    int ncol, int nlay, int *icld, int idrv,
+    const float *play, const float *plev, const float *tlay, const float *tlev, const float *tsfc,
+    const float *h2ovmr, const float *o3vmr, const float *co2vmr, const float *ch4vmr, const float *n2ovmr,
+    const float *o2vmr, const float *cfc11vmr, const float *cfc12vmr, const float *cfc22vmr,
+    const float *ccl4vmr, const float *emis, int inflglw, int iceflglw, int liqflglw,
+    const float *cldfr, const float *taucld, const float *cicewp, const float *cliqwp,
+    const float *reice, const float *reliq, const float *tauaer,
+    float *uflx, float *dflx, float *hr, float *uflxc, float *dflxc, float *hrc,
+    float *duflx_dt, float *duflxc_dt);
+int rrtmg_lw_hip_run_mcica_r4(
+    int ncol, int nlay, int *icld, int idrv,
+    const float *play, const float *plev, const float *tlay, const float *tlev, const float *tsfc,
+    const float *h2ovmr, const float *o3vmr, const float *co2vmr, const float *ch4vmr, const float *n2ovmr,
+    const float *o2vmr, const float *cfc11vmr, const float *cfc12vmr, const float *cfc22vmr,
+    const float *ccl4vmr, const float *emis, int inflglw, int iceflglw, int liqflglw,
+    const float *cldfmcl, const float *taucmcl, const float *ciwpmcl, const float *clwpmcl,
+    const float *reicmcl, const float *relqmcl, const float *tauaer,
+    float *uflx, float *dflx, float *hr, float *uflxc, float *dflxc, float *hrc,
+    float *duflx_dt, float *duflxc_dt);
+int rrtmg_lw_hip_run_mcica_subcol_r4(
+    int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng,
+    const float *play, const float *plev, const float *tlay, const float *tlev, const float *tsfc,
+    const float *h2ovmr, const float *o3vmr, const float *co2vmr, const float *ch4vmr, const float *n2ovmr,
+    const float *o2vmr, const float *cfc11vmr, const float *cfc12vmr, const float *cfc22vmr,
+    const float *ccl4vmr, const float *emis, int inflglw, int iceflglw, int liqflglw,
+    const float *cldfr, const float *taucld, const float *cicewp, const float *cliqwp,
+    const float *reice, const float *reliq, const float *alpha, const float *tauaer,
+    float *uflx, float *dflx, float *hr, float *uflxc, float *dflxc, float *hrc,
+    float *duflx_dt, float *duflxc_dt);
+int rrtmg_lw_hip_adjust_tsfc_r4(int ncol, int nlay, const float *plev, const float *dtsfc,
+    const float *uflx, const float *dflx, const float *duflx_dt,
+    const float *uflxc, const float *dflxc, const float *duflxc_dt,
+    float *uflx_adj, float *hr_adj, float *uflxc_adj, float *hrc_adj);
 
 /* PMC calibration: one kernel that reads `bytes` and writes `bytes` with 16 B per lane (known HBM traffic), so that a
  * rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE pass can fix the counters' unit and scale in the same session. */

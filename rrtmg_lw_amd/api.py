@@ -248,22 +248,36 @@ def cu_partition():
     return int(lib().rrtmg_lw_hip_cu_partition())
 
 
-def _f(a, shape):
-    a = np.asfortranarray(a, dtype=np.float64)
+def _f(a, shape, dtype=np.float64):
+    """`a` as a Fortran-ordered array of `dtype` (one that already is, is passed in place: a registered array stays registered)"""
+    a = np.asfortranarray(a, dtype=dtype)
     if tuple(a.shape) != tuple(shape):
         raise ValueError(f"array has shape {a.shape}, interface declares {shape}")
     return a
 
 
 def _p(a):
+    """the array's address (float32 arrays of the *_r4 entries too: the functions are called without argtypes, only the address passes)"""
     return a.ctypes.data_as(_dp)
 
 
-def _out_ok(a, shape, name):
-    """an array the library writes into in place: float64, Fortran-contiguous, writeable, exactly the interface's shape"""
-    if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.f_contiguous and a.flags.writeable and tuple(a.shape) == tuple(shape)):
-        raise ValueError(f"output array {name!r} must be a writeable float64 Fortran-ordered array of shape {tuple(shape)}")
+def _out_ok(a, shape, name, dtype=np.float64):
+    """an array the library writes into in place: of `dtype`, Fortran-contiguous, writeable, exactly the interface's shape"""
+    if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.flags.f_contiguous and a.flags.writeable and tuple(a.shape) == tuple(shape)):
+        raise ValueError(f"output array {name!r} must be a writeable {np.dtype(dtype).name} Fortran-ordered array of shape {tuple(shape)}")
     return a
+
+
+def _real(dtype, spectral=False):
+    """The element type of a host call: float64 (None: the default) or float32 - the *_r4 entries of the C ABI (include/rrtmg_lw_hip.h,
+    "_r4"): every array of the call is then float32, inputs are taken as Fortran-ordered float32 arrays, outputs are float32, and the
+    results are the float64 call's on the widened inputs, rounded.  No spectral outputs with float32."""
+    dt = np.dtype(np.float64 if dtype is None else dtype)
+    if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError(f"dtype must be numpy float64 or float32, not {dt}")
+    if dt == np.float32 and spectral:
+        raise ValueError("the spectral outputs are not available with dtype=float32")
+    return dt
 
 
 _SPEC = ("uflxs", "dflxs", "uflxcs", "dflxcs")
@@ -289,23 +303,25 @@ def _spec_dev(out):
 
 def rrtmg_lw(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr,
              cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp,
-             cliqwp, reice, reliq, tauaer, out=None, spectral=False):
+             cliqwp, reice, reliq, tauaer, out=None, spectral=False, dtype=None):
     """Non-McICA rrtmg_lw with host arrays.  Returns dict(uflx, dflx, hr, uflxc, dflxc, hrc[, duflx_dt, duflxc_dt], icld);
     `out` may hold preallocated (e.g. host_register'ed) Fortran-ordered output arrays.  spectral=True: the dict also holds the fluxes
-    per band, uflxs, dflxs, uflxcs, dflxcs of shape (ncol, nlay+1, 16) (_spec_ptrs)."""
-    a2 = [_f(x, (ncol, nlay)) for x in (play,)] + [_f(plev, (ncol, nlay + 1)), _f(tlay, (ncol, nlay)),
-                                                  _f(tlev, (ncol, nlay + 1)), _f(tsfc, (ncol,))]
-    gases = [_f(x, (ncol, nlay)) for x in (h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr)]
-    em = _f(emis, (ncol, NBND))
-    cld = [_f(cldfr, (ncol, nlay)), _f(taucld, (NBND, ncol, nlay)), _f(cicewp, (ncol, nlay)), _f(cliqwp, (ncol, nlay)),
-           _f(reice, (ncol, nlay)), _f(reliq, (ncol, nlay)), _f(tauaer, (ncol, nlay, NBND))]
+    per band, uflxs, dflxs, uflxcs, dflxcs of shape (ncol, nlay+1, 16) (_spec_ptrs).  dtype=np.float32: float32 arrays in and out
+    (_real); without it a float32 input is widened to float64 like any other convertible array."""
+    dt = _real(dtype, spectral)
+    a2 = [_f(x, (ncol, nlay), dt) for x in (play,)] + [_f(plev, (ncol, nlay + 1), dt), _f(tlay, (ncol, nlay), dt),
+                                                      _f(tlev, (ncol, nlay + 1), dt), _f(tsfc, (ncol,), dt)]
+    gases = [_f(x, (ncol, nlay), dt) for x in (h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr)]
+    em = _f(emis, (ncol, NBND), dt)
+    cld = [_f(cldfr, (ncol, nlay), dt), _f(taucld, (NBND, ncol, nlay), dt), _f(cicewp, (ncol, nlay), dt), _f(cliqwp, (ncol, nlay), dt),
+           _f(reice, (ncol, nlay), dt), _f(reliq, (ncol, nlay), dt), _f(tauaer, (ncol, nlay, NBND), dt)]
     if out is None:
-        out = _out_arrays(ncol, nlay, idrv)
+        out = _out_arrays(ncol, nlay, idrv, dt)
     else:
         for k in ("uflx", "dflx", "uflxc", "dflxc") + (("duflx_dt", "duflxc_dt") if idrv == 1 else ()):
-            _out_ok(out[k], (ncol, nlay + 1), k)
+            _out_ok(out[k], (ncol, nlay + 1), k, dt)
         for k in ("hr", "hrc"):
-            _out_ok(out[k], (ncol, nlay), k)
+            _out_ok(out[k], (ncol, nlay), k, dt)
     icld_c = C.c_int(int(icld))
     null = C.cast(None, _dp)
     args = [C.c_int(ncol), C.c_int(nlay), C.byref(icld_c), C.c_int(int(idrv))]
@@ -316,6 +332,8 @@ def rrtmg_lw(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr
     args += [_p(out["duflx_dt"]) if idrv == 1 else null, _p(out["duflxc_dt"]) if idrv == 1 else null]
     if spectral:
         _check(lib().rrtmg_lw_hip_run_nomcica_spectral(*args, *_spec_ptrs(out, ncol, nlay)))
+    elif dt == np.float32:
+        _check(lib().rrtmg_lw_hip_run_nomcica_r4(*args))
     else:
         _check(lib().rrtmg_lw_hip_run_nomcica(*args))
     out["icld"] = icld_c.value
@@ -328,12 +346,12 @@ _CLD_ORDER = ("cldfr", "taucld", "cicewp", "cliqwp", "reice", "reliq", "tauaer")
 _FLUX_OUT = ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc", "duflx_dt", "duflxc_dt")
 
 
-def rrtmg_lw_from_dict(d, icld=None, idrv=None, out=None, spectral=False):
+def rrtmg_lw_from_dict(d, icld=None, idrv=None, out=None, spectral=False, dtype=None):
     """Convenience: call rrtmg_lw with the dictionaries produced by rrtmg_lw_amd.synth.make_gcm_inputs."""
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     return rrtmg_lw(d["ncol"], d["nlay"], icld, idrv, *[d[k] for k in _GCM_ORDER], d["inflglw"], d["iceflglw"],
-                    d["liqflglw"], *[d[k] for k in _CLD_ORDER], out=out, spectral=spectral)
+                    d["liqflglw"], *[d[k] for k in _CLD_ORDER], out=out, spectral=spectral, dtype=dtype)
 
 
 class _ArrayFormC(C.Structure):
@@ -532,6 +550,7 @@ _ADJUST_CLEAR = ("uflxc", "dflxc", "duflxc_dt", "uflxc_adj", "hrc_adj")
 # the argument lists of the three C entries as this module passes them (tests/test_adjust_tsfc.py holds them against the header)
 _ADJUST_ARGTYPES = {
     "rrtmg_lw_hip_adjust_tsfc": [C.c_int, C.c_int] + [_dp] * 12,
+    "rrtmg_lw_hip_adjust_tsfc_r4": [C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 12,
     "rrtmg_lw_hip_adjust_tsfc_device": [C.c_int, C.c_int] + [C.c_void_p] * 13,
     "rrtmg_lw_hip_adjust_tsfc_device_as": [C.POINTER(_ArrayFormC), C.c_int, C.c_int] + [C.c_void_p] * 13,
 }
@@ -543,29 +562,34 @@ def _adjust_fn(name):
     return fn
 
 
-def adjust_tsfc(ncol, nlay, plev, dtsfc, uflx, dflx, duflx_dt, uflxc=None, dflxc=None, duflxc_dt=None, out=None):
+def adjust_tsfc(ncol, nlay, plev, dtsfc, uflx, dflx, duflx_dt, uflxc=None, dflxc=None, duflxc_dt=None, out=None, dtype=None):
     """The fluxes and heating rates of an idrv = 1 radiation call adjusted to a changed surface temperature (rrtmg_lw_hip_adjust_tsfc;
     reference src/rrtmg_lw.1col.f90:582-610), host arrays: uflx_adj = uflx + duflx_dt * dtsfc, hr_adj from the new net flux.  dtsfc
     (ncol,) is the current surface temperature minus the tsfc of that call; uflx, dflx, duflx_dt are its stored, unadjusted results.
     The clear-sky arrays uflxc, dflxc, duflxc_dt are all given or all None.  Returns dict(uflx_adj (ncol, nlay+1), hr_adj (ncol, nlay)
-    [, uflxc_adj, hrc_adj]); `out` may hold preallocated (e.g. host_register'ed) Fortran-ordered arrays of those names."""
+    [, uflxc_adj, hrc_adj]); `out` may hold preallocated (e.g. host_register'ed) Fortran-ordered arrays of those names.
+    dtype=np.float32: float32 arrays in and out (rrtmg_lw_hip_adjust_tsfc_r4; _real)."""
     ncol, nlay = int(ncol), int(nlay)
+    dt = _real(dtype)
+    r4 = dt == np.float32
+    ptr = (lambda a: a.ctypes.data_as(C.POINTER(C.c_float))) if r4 else _p
     clear = (uflxc, dflxc, duflxc_dt)
     if any(x is None for x in clear) and not all(x is None for x in clear):
         raise ValueError("adjust_tsfc: uflxc, dflxc and duflxc_dt must be all None or all arrays")
     has_c = clear[0] is not None
     lev, lay = (ncol, nlay + 1), (ncol, nlay)
-    null = C.cast(None, _dp)
-    ins = [_f(plev, lev), _f(dtsfc, (ncol,))] + [_f(x, lev) for x in (uflx, dflx, duflx_dt)] + ([_f(x, lev) for x in clear] if has_c else [])
+    null = C.cast(None, C.POINTER(C.c_float) if r4 else _dp)
+    ins = [_f(plev, lev, dt), _f(dtsfc, (ncol,), dt)] + [_f(x, lev, dt) for x in (uflx, dflx, duflx_dt)] + ([_f(x, lev, dt) for x in clear] if has_c else [])
     out = {} if out is None else out
     shapes = dict(uflx_adj=lev, hr_adj=lay, uflxc_adj=lev, hrc_adj=lay)
     names = _ADJUST_OUT if has_c else _ADJUST_OUT[:2]
     for k in names:
         if k not in out:
-            out[k] = np.empty(shapes[k], order="F")
-        _out_ok(out[k], shapes[k], k)
-    o = [_p(out[k]) if k in names else null for k in _ADJUST_OUT]
-    _check(_adjust_fn("rrtmg_lw_hip_adjust_tsfc")(ncol, nlay, *[_p(x) for x in ins], *([null] * 3 if not has_c else []), *o))
+            out[k] = np.empty(shapes[k], dtype=dt, order="F")
+        _out_ok(out[k], shapes[k], k, dt)
+    o = [ptr(out[k]) if k in names else null for k in _ADJUST_OUT]
+    fn = _adjust_fn("rrtmg_lw_hip_adjust_tsfc_r4" if r4 else "rrtmg_lw_hip_adjust_tsfc")
+    _check(fn(ncol, nlay, *[ptr(x) for x in ins], *([null] * 3 if not has_c else []), *o))
     return out
 
 
@@ -586,13 +610,13 @@ def adjust_tsfc_device(arrays, out, stream=None, form=None):
 # ---------------------------------------------------------------------------------------------------
 # McICA flavour: reference src/rrtmg_lw_rad.f90:99-108, src/mcica_subcol_gen_lw.f90:68,183
 # ---------------------------------------------------------------------------------------------------
-def _out_arrays(ncol, nlay, idrv):
-    out = {k: np.empty((ncol, nlay + 1), order="F") for k in ("uflx", "dflx", "uflxc", "dflxc")}
-    out["hr"] = np.empty((ncol, nlay), order="F")
-    out["hrc"] = np.empty((ncol, nlay), order="F")
+def _out_arrays(ncol, nlay, idrv, dtype=np.float64):
+    out = {k: np.empty((ncol, nlay + 1), dtype=dtype, order="F") for k in ("uflx", "dflx", "uflxc", "dflxc")}
+    out["hr"] = np.empty((ncol, nlay), dtype=dtype, order="F")
+    out["hrc"] = np.empty((ncol, nlay), dtype=dtype, order="F")
     if idrv == 1:
-        out["duflx_dt"] = np.empty((ncol, nlay + 1), order="F")
-        out["duflxc_dt"] = np.empty((ncol, nlay + 1), order="F")
+        out["duflx_dt"] = np.empty((ncol, nlay + 1), dtype=dtype, order="F")
+        out["duflxc_dt"] = np.empty((ncol, nlay + 1), dtype=dtype, order="F")
     return out
 
 
@@ -602,27 +626,31 @@ def _out_ptrs(out, idrv):
            [_p(out["duflx_dt"]) if idrv == 1 else null, _p(out["duflxc_dt"]) if idrv == 1 else null]
 
 
-def _gcm_arrays(ncol, nlay, play, plev, tlay, tlev, tsfc, gases, emis):
-    return [_f(play, (ncol, nlay)), _f(plev, (ncol, nlay + 1)), _f(tlay, (ncol, nlay)), _f(tlev, (ncol, nlay + 1)),
-            _f(tsfc, (ncol,))] + [_f(x, (ncol, nlay)) for x in gases] + [_f(emis, (ncol, NBND))]
+def _gcm_arrays(ncol, nlay, play, plev, tlay, tlev, tsfc, gases, emis, dt=np.float64):
+    return [_f(play, (ncol, nlay), dt), _f(plev, (ncol, nlay + 1), dt), _f(tlay, (ncol, nlay), dt), _f(tlev, (ncol, nlay + 1), dt),
+            _f(tsfc, (ncol,), dt)] + [_f(x, (ncol, nlay), dt) for x in gases] + [_f(emis, (ncol, NBND), dt)]
 
 
 def rrtmg_lw_mcica(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr,
                    cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw, cldfmcl, taucmcl, ciwpmcl,
-                   clwpmcl, reicmcl, relqmcl, tauaer, spectral=False, out=None):
+                   clwpmcl, reicmcl, relqmcl, tauaer, spectral=False, out=None, dtype=None):
     """McICA rrtmg_lw (src/rrtmg_lw_rad.f90:99-108) with host arrays; sub-column arrays are (140, ncol, nlay).
-    spectral=True: the fluxes per band as well (see rrtmg_lw); `out`: a dict of preallocated spectral outputs to fill."""
+    spectral=True: the fluxes per band as well (see rrtmg_lw); `out`: a dict of preallocated spectral outputs to fill.
+    dtype=np.float32: float32 arrays in and out (rrtmg_lw_hip_run_mcica_r4; _real)."""
+    dt = _real(dtype, spectral)
     a = _gcm_arrays(ncol, nlay, play, plev, tlay, tlev, tsfc,
-                    (h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr), emis)
+                    (h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr), emis, dt)
     ng = gpoints()
-    cld = [_f(cldfmcl, (ng, ncol, nlay)), _f(taucmcl, (ng, ncol, nlay)), _f(ciwpmcl, (ng, ncol, nlay)),
-           _f(clwpmcl, (ng, ncol, nlay)), _f(reicmcl, (ncol, nlay)), _f(relqmcl, (ncol, nlay)), _f(tauaer, (ncol, nlay, NBND))]
-    out = dict(out or {}, **_out_arrays(ncol, nlay, idrv))
+    cld = [_f(cldfmcl, (ng, ncol, nlay), dt), _f(taucmcl, (ng, ncol, nlay), dt), _f(ciwpmcl, (ng, ncol, nlay), dt),
+           _f(clwpmcl, (ng, ncol, nlay), dt), _f(reicmcl, (ncol, nlay), dt), _f(relqmcl, (ncol, nlay), dt), _f(tauaer, (ncol, nlay, NBND), dt)]
+    out = dict(out or {}, **_out_arrays(ncol, nlay, idrv, dt))
     icld_c = C.c_int(int(icld))
     args = [C.c_int(ncol), C.c_int(nlay), C.byref(icld_c), C.c_int(int(idrv))] + [_p(x) for x in a]
     args += [C.c_int(int(inflglw)), C.c_int(int(iceflglw)), C.c_int(int(liqflglw))] + [_p(x) for x in cld] + _out_ptrs(out, idrv)
     if spectral:
         _check(lib().rrtmg_lw_hip_run_mcica_spectral(*args, *_spec_ptrs(out, ncol, nlay)))
+    elif dt == np.float32:
+        _check(lib().rrtmg_lw_hip_run_mcica_r4(*args))
     else:
         _check(lib().rrtmg_lw_hip_run_mcica(*args))
     out["icld"] = icld_c.value
@@ -632,11 +660,11 @@ def rrtmg_lw_mcica(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, h2ovmr,
 _MC_ORDER = ("cldfmcl", "taucmcl", "ciwpmcl", "clwpmcl", "reicmcl", "relqmcl", "tauaer")
 
 
-def rrtmg_lw_mcica_from_dict(d, icld=None, idrv=None, spectral=False, out=None):
+def rrtmg_lw_mcica_from_dict(d, icld=None, idrv=None, spectral=False, out=None, dtype=None):
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     return rrtmg_lw_mcica(d["ncol"], d["nlay"], icld, idrv, *[d[k] for k in _GCM_ORDER], d["inflglw"], d["iceflglw"],
-                          d["liqflglw"], *[d[k] for k in _MC_ORDER], spectral=spectral, out=out)
+                          d["liqflglw"], *[d[k] for k in _MC_ORDER], spectral=spectral, out=out, dtype=dtype)
 
 
 def get_alpha(ncol, nlay, icld, idcor, decorr_con, dz, lat, juldat, cldfrac):
@@ -674,20 +702,25 @@ def mcica_subcol_lw(ncol, nlay, icld, permuteseed, irng, play, cldfrac, ciwp, cl
 
 def rrtmg_lw_mcica_subcol(ncol, nlay, icld, idrv, permuteseed, irng, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr,
                           ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw,
-                          cldfr, taucld, cicewp, cliqwp, reice, reliq, alpha, tauaer, spectral=False, out=None):
+                          cldfr, taucld, cicewp, cliqwp, reice, reliq, alpha, tauaer, spectral=False, out=None, dtype=None):
     """mcica_subcol_lw followed by the McICA rrtmg_lw in one call; the sub-columns stay on the device as bit masks.
-    spectral=True: the fluxes per band as well (see rrtmg_lw); `out`: a dict of preallocated spectral outputs to fill."""
+    spectral=True: the fluxes per band as well (see rrtmg_lw); `out`: a dict of preallocated spectral outputs to fill.
+    dtype=np.float32: float32 arrays in and out, alpha too (rrtmg_lw_hip_run_mcica_subcol_r4; _real)."""
+    dt = _real(dtype, spectral)
     a = _gcm_arrays(ncol, nlay, play, plev, tlay, tlev, tsfc,
-                    (h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr), emis)
-    cld = [_p(_f(cldfr, (ncol, nlay))), _p(_f(taucld, (NBND, ncol, nlay))), _p(_f(cicewp, (ncol, nlay))), _p(_f(cliqwp, (ncol, nlay))),
-           _p(_f(reice, (ncol, nlay))), _p(_f(reliq, (ncol, nlay))),
-           _p(_f(alpha, (ncol, nlay))) if alpha is not None else C.cast(None, _dp), _p(_f(tauaer, (ncol, nlay, NBND)))]
-    out = dict(out or {}, **_out_arrays(ncol, nlay, idrv))
+                    (h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr), emis, dt)
+    keep = [_f(cldfr, (ncol, nlay), dt), _f(taucld, (NBND, ncol, nlay), dt), _f(cicewp, (ncol, nlay), dt), _f(cliqwp, (ncol, nlay), dt),
+            _f(reice, (ncol, nlay), dt), _f(reliq, (ncol, nlay), dt), _f(alpha, (ncol, nlay), dt) if alpha is not None else None,
+            _f(tauaer, (ncol, nlay, NBND), dt)]
+    cld = [_p(x) if x is not None else C.cast(None, _dp) for x in keep]
+    out = dict(out or {}, **_out_arrays(ncol, nlay, idrv, dt))
     icld_c, irng_c = C.c_int(int(icld)), C.c_int(int(irng))
     args = [C.c_int(ncol), C.c_int(nlay), C.byref(icld_c), C.c_int(int(idrv)), C.c_int(int(permuteseed)), C.byref(irng_c)]
     args += [_p(x) for x in a] + [C.c_int(int(inflglw)), C.c_int(int(iceflglw)), C.c_int(int(liqflglw))] + cld + _out_ptrs(out, idrv)
     if spectral:
         _check(lib().rrtmg_lw_hip_run_mcica_subcol_spectral(*args, *_spec_ptrs(out, ncol, nlay)))
+    elif dt == np.float32:
+        _check(lib().rrtmg_lw_hip_run_mcica_subcol_r4(*args))
     else:
         _check(lib().rrtmg_lw_hip_run_mcica_subcol(*args))
     out["icld"] = icld_c.value
@@ -695,12 +728,12 @@ def rrtmg_lw_mcica_subcol(ncol, nlay, icld, idrv, permuteseed, irng, play, plev,
     return out
 
 
-def rrtmg_lw_mcica_subcol_from_dict(d, permuteseed, irng, alpha=None, icld=None, idrv=None, spectral=False, out=None):
+def rrtmg_lw_mcica_subcol_from_dict(d, permuteseed, irng, alpha=None, icld=None, idrv=None, spectral=False, out=None, dtype=None):
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     return rrtmg_lw_mcica_subcol(d["ncol"], d["nlay"], icld, idrv, permuteseed, irng, *[d[k] for k in _GCM_ORDER], d["inflglw"],
                                  d["iceflglw"], d["liqflglw"], d["cldfr"], d["taucld"], d["cicewp"], d["cliqwp"], d["reice"],
-                                 d["reliq"], alpha, d["tauaer"], spectral=spectral, out=out)
+                                 d["reliq"], alpha, d["tauaer"], spectral=spectral, out=out, dtype=dtype)
 
 
 def rrtmg_lw_mcica_subcol_device(d, out, permuteseed, irng, alpha=None, icld=None, idrv=None, stream=None, form=None):

@@ -22,6 +22,7 @@
 #include "../../include/rrtmg_lw_hip.h"
 #include "kernels.hip"
 #include "mtjump.hpp"
+#include "hostrows.hpp"
 
 namespace {
 
@@ -111,8 +112,12 @@ struct State {
     size_t h_tot_doubles = 0;
     // pinned host staging of the host-pointer entries, HOST_SETS sets like the device staging: `in` = the rows of the caller's PAGEABLE input
     // arrays that travel (packed by the host threads, then one DMA per run of rows), `out` = the pageable output arrays' rows (DMA, then
-    // unpacked by the host threads), `fill` = the table of k_fill_rows (rows that do not travel)
-    struct HostSet { char *in = nullptr; size_t in_cap = 0; char *out = nullptr; size_t out_cap = 0; char *fill = nullptr; size_t fill_cap = 0; } hset[HOST_SETS];
+    // unpacked by the host threads), `fill` = the table of k_fill_rows (rows that do not travel); the *_r4 entries: `widen` / `narrow` =
+    // the tables of k_widen_rows (float32 input rows that have landed) and k_narrow_rows (the active output rows)
+    struct HostSet {
+        char *in = nullptr; size_t in_cap = 0; char *out = nullptr; size_t out_cap = 0; char *fill = nullptr; size_t fill_cap = 0;
+        char *widen = nullptr; size_t widen_cap = 0; char *narrow = nullptr; size_t narrow_cap = 0;
+    } hset[HOST_SETS];
     hipEvent_t ev_h2d[HOST_SETS] = {}, ev_cmp[HOST_SETS] = {}, ev_d2h[HOST_SETS] = {};
     KissTable kiss;             // the kissvec generator's jump table of the last (draws per sub-column, permuteseed) pair, on this device
     std::string err;
@@ -150,7 +155,10 @@ struct CallDesc {
     int idrv, inflg, iceflg, liqflg;
     int permuteseed = 0; int *irng = nullptr;     // the fused generator + solver entries
     bool spectral = false;                        // a *_spectral entry: uflxs and dflxs are required (check_spec)
+    size_t esz = 8;                               // bytes per element of the caller's HOST arrays: 4 in the *_r4 entries, whose float arrays travel in
+                                                  // GcmIn / FluxOut as addresses only (nothing above the staging layer reads through them)
 };
+CallDesc real4(CallDesc d) { d.esz = 4; return d; }
 CallDesc spectral(CallDesc d) { d.spectral = true; return d; }
 
 // The scalars of a batch below the entry points, as CallDesc and the array structs are for a call: what is fixed for the call, and the
@@ -1276,15 +1284,21 @@ struct HostIn {
     const unsigned char *known = nullptr;                 // ... rows the prep step has already read in full and found to hold one pattern (known_bits): not scanned again
     const uint64_t *known_bits = nullptr;
     unsigned long long static_gen = 0;                    // != 0: the caller declared the array static (rrtmg_lw_hip_host_static): row scans are cached per batch
+    // bytes per element of h (4: a *_r4 entry's float array behind the double pointer) and of the batch's src (8 again where the entry
+    // names its own float64 scratch, tauctot); land: the array's rows in the staging set's float32 landing area, where 4-byte rows arrive
+    size_t esz = 8, src_esz = 8;
+    float *land = nullptr;
 };
-struct HostOut { double *h; size_t rows; double *d; bool active; bool pinned = false; };
+struct HostOut { double *h; size_t rows; double *d; bool active; bool pinned = false; size_t esz = 8; float *land = nullptr; };
+using hostrows::land_stride;
+using hostrows::widened_bits;
 // Where input `a` stands in a call's staged list: tauaer before the cloud arrays (the order of the rows in the device buffer and of the copies)
 constexpr int staged_at(int a) { return a < A_CLDFR ? a : a == A_TAUAER ? (int)A_CLDFR : a + 1; }
 
 // The staged inputs of a host-pointer call, the first n of rrtmg_lw's arrays (gas optics: the 16 up to emis), and their null checks.
 // The cloud arrays travel only with `cloud` - the McICA entry's sub-column arrays `m` in their places - and taucld with tau_inner values
 // per (column, layer).
-int host_ins(std::vector<HostIn> &ins, const GcmIn &g, const McIn *m, size_t L, bool cloud, size_t tau_inner, int n = NA_GCM, const char *who = "")
+int host_ins(std::vector<HostIn> &ins, const GcmIn &g, const McIn *m, size_t L, bool cloud, size_t tau_inner, int n = NA_GCM, const char *who = "", size_t esz = 8)
 {
     const double *p[NA_IN];
     gcm_pointers(g, nullptr, p);
@@ -1294,6 +1308,7 @@ int host_ins(std::vector<HostIn> &ins, const GcmIn &g, const McIn *m, size_t L, 
         // (McICA: cldfmcl, taucmcl, ciwpmcl, clwpmcl are (ngpt,ncol,nlay); reicmcl and relqmcl (ncol,nlay) like reice and reliq)
         const size_t inner = m && a >= A_CLDFR && a <= A_CLIQWP ? (size_t)NGPT : a == A_TAUCLD ? tau_inner : CALL_ARRAYS[a].inner;
         ins[staged_at(a)] = HostIn{CALL_ARRAYS[a].cloud && !cloud ? nullptr : p[a], inner, rows_of(a, L), nullptr};
+        ins[staged_at(a)].esz = esz;
     }
     for (int a = 0; a < n; a++) if (!CALL_ARRAYS[a].cloud && !p[a]) return fail(RRTMG_LW_HIP_EARG, "%snull input array (argument %d)", who, a);
     for (int a = 0; a < n; a++) if (cloud && CALL_ARRAYS[a].cloud && !p[a]) return fail(RRTMG_LW_HIP_EARG, m ? "null McICA cloud array" : "null cloud array");
@@ -1314,13 +1329,14 @@ void skip_cloudfree(std::vector<HostIn> &ins, const unsigned char *cloudfree, co
     for (int a = A_TAUCLD; a <= A_RELIQ; a++) ins[staged_at(a)].skip = cloudfree;
 }
 // The staged outputs: the eight broadband arrays (the derivatives active with idrv = 1), then the spectral four (no rows when absent)
-std::vector<HostOut> host_outs(const FluxOut &o, size_t L, int idrv)
+std::vector<HostOut> host_outs(const FluxOut &o, size_t L, int idrv, size_t esz = 8)
 {
     double *p[NA_CALL];
     flux_pointers(o, p);
     std::vector<HostOut> outs;
     for (int a = A_UFLX; a < A_UFLXS; a++) outs.push_back({p[a], rows_of(a, L), nullptr, a < A_DUFLX_DT || idrv == 1});
     for (int a = A_UFLXS; a < NA_CALL; a++) outs.push_back({p[a], p[a] ? rows_of(a, L) : 0, nullptr, p[a] != nullptr});
+    for (auto &a : outs) a.esz = esz;
     return outs;
 }
 FluxOut staged_flux(const std::vector<HostOut> &v)
@@ -1462,16 +1478,19 @@ void host_parallel(size_t work_bytes, F f)
 // With thr = cldmin: a layer of the cloud fraction without cloud in any column of the batch - cldprop / cldprmc then read nothing else of that
 // layer (src/rrtmg_lw_cldprop.f90:185-186, src/rrtmg_lw_cldprmc.f90:182-183), so the other cloud arrays' rows of that layer need not be read here.
 // uni / bits (optional): rows that were read to their end (the ones below the threshold) and hold ONE 8-byte pattern - stage_rows need not read them again.
-void rows_below(const double *h, size_t inner, size_t rows, size_t ncol, size_t col0, size_t nb, double thr, unsigned char *flags,
+// T = float (the *_r4 entries): 4-byte patterns, compared with the widened threshold as the widened values would be; bits: the widened value's.
+template <class T>
+void rows_below(const T *h, size_t inner, size_t rows, size_t ncol, size_t col0, size_t nb, double thr, unsigned char *flags,
                 unsigned char *uni = nullptr, uint64_t *bits = nullptr)
 {
-    host_parallel(inner * rows * nb * 8, [&](int t, int nt) {
+    using U = hostrows::Pattern<T>;
+    host_parallel(inner * rows * nb * sizeof(T), [&](int t, int nt) {
         for (size_t r = (size_t)t; r < rows; r += (size_t)nt) {
-            const double *p = h + inner * (col0 + ncol * r);
-            const uint64_t *u = reinterpret_cast<const uint64_t *>(p);
+            const T *p = h + inner * (col0 + ncol * r);
+            const U *u = reinterpret_cast<const U *>(p);
             const size_t n = inner * nb;
-            const uint64_t v = u[0];
-            uint64_t acc = 0;
+            const U v = u[0];
+            U acc = 0;
             bool below = true;
             size_t i = 0;
             for (; i + 64 <= n && below; i += 64) {
@@ -1481,7 +1500,7 @@ void rows_below(const double *h, size_t inner, size_t rows, size_t ncol, size_t 
             }
             for (; i < n && below; i++) { below = p[i] < thr; acc |= u[i] ^ v; }
             flags[r] = below ? 1 : 0;
-            if (uni) { uni[r] = (below && acc == 0) ? 1 : 0; bits[r] = v; }
+            if (uni) { uni[r] = (below && acc == 0) ? 1 : 0; bits[r] = widened_bits(p[0]); }
         }
     });
 }
@@ -1515,10 +1534,11 @@ struct StaticRange { const char *p; size_t bytes; unsigned long long gen; };
 std::vector<StaticRange> g_static;
 unsigned long long g_static_gen = 1;
 struct ScanKey {
-    const void *base; size_t ncol, inner, rows, col0, nb;
+    const void *base; size_t ncol, inner, rows, col0, nb, esz;          // esz: an address seen again with another element type is another array
     bool operator<(const ScanKey &o) const
     {
         if (base != o.base) return base < o.base;
+        if (esz != o.esz) return esz < o.esz;
         if (ncol != o.ncol) return ncol < o.ncol;
         if (inner != o.inner) return inner < o.inner;
         if (rows != o.rows) return rows < o.rows;
@@ -1622,8 +1642,13 @@ int ensure_copy_streams()
 //  * rows of a PAGEABLE array are packed into the pinned set by the host threads and leave as one asynchronous DMA per run of rows
 //    (the runtime's own pageable path is one blocking, single-threaded staging copy per call); rows of a pinned array leave from
 //    where they lie.
+//  * rows of 4-byte values (src_esz = 4, the *_r4 entries) are scanned as 4-byte patterns - the fill writes the widened value -, travel
+//    as they are into the staging set's float32 landing area (HostIn::land), every row on a 16-byte boundary there and in the pinned set,
+//    and are widened into the float64 array by ONE k_widen_rows launch behind the DMAs (its table: pinned set k, one entry per row).
 // The pinned set k is free: the caller has waited for the DMAs of the batch that used it last.
 struct StagedRow { unsigned arr, row; bool uniform; uint64_t bits; size_t off; };
+// workgroups per table entry of k_widen_rows / k_narrow_rows for rows of up to w values
+unsigned cvt_blocks(size_t w) { return (unsigned)std::min<size_t>(CVT_BLOCKS, std::max<size_t>(1, (w + 256 * CVT_LANE - 1) / (256 * CVT_LANE))); }
 int stage_rows(std::vector<HostIn> &ins, size_t nb, int k, hipStream_t s)
 {
     static thread_local std::vector<StagedRow> tl_rows;
@@ -1636,9 +1661,9 @@ int stage_rows(std::vector<HostIn> &ins, size_t nb, int k, hipStream_t s)
         const HostIn &a = ins[ai];
         if (!a.h) continue;
         for (size_t r = 0; r < a.rows; r++) rows.push_back({(unsigned)ai, (unsigned)r, false, 0, 0});
-        bytes += a.inner * a.rows * nb * 8;
+        bytes += a.inner * a.rows * nb * a.src_esz;
     }
-    auto row_src = [&](const StagedRow &q) { const HostIn &a = ins[q.arr]; return a.src + a.inner * (a.src_col0 + a.src_ncol * q.row); };
+    auto row_src = [&](const StagedRow &q) { const HostIn &a = ins[q.arr]; return (const char *)a.src + a.src_esz * a.inner * (a.src_col0 + a.src_ncol * q.row); };
     // cached scans of the arrays declared static (the entry of this array and batch; filled below on a miss)
     std::vector<ScanVal *> cache(ins.size(), nullptr);
     std::vector<unsigned char> cache_hit(ins.size(), 0);
@@ -1647,7 +1672,7 @@ int stage_rows(std::vector<HostIn> &ins, size_t nb, int k, hipStream_t s)
         for (size_t ai = 0; ai < ins.size(); ai++) {
             const HostIn &a = ins[ai];
             if (!a.h || a.static_gen == 0 || a.src != a.h) continue;          // (an array the entry reduces on the host, tauctot, is formed anew per call)
-            ScanVal &v = g_scan[ScanKey{a.h, a.src_ncol, a.inner, a.rows, a.src_col0, nb}];
+            ScanVal &v = g_scan[ScanKey{a.h, a.src_ncol, a.inner, a.rows, a.src_col0, nb, a.esz}];
             if (v.gen == a.static_gen && v.state.size() == a.rows) cache_hit[ai] = 1;
             else { v.gen = a.static_gen; v.state.assign(a.rows, 0); v.bits.assign(a.rows, 0); }
             cache[ai] = &v;                                                     // (map nodes do not move; entries are dropped under the entry lock only)
@@ -1659,33 +1684,36 @@ int stage_rows(std::vector<HostIn> &ins, size_t nb, int k, hipStream_t s)
             if (ins[q.arr].skip && ins[q.arr].skip[q.row]) { q.uniform = true; q.bits = 0; continue; }
             if (ins[q.arr].known && ins[q.arr].known[q.row]) { q.uniform = true; q.bits = ins[q.arr].known_bits[q.row]; continue; }
             if (cache_hit[q.arr] && cache[q.arr]->state[q.row] != 0) { q.uniform = cache[q.arr]->state[q.row] == 1; q.bits = cache[q.arr]->bits[q.row]; continue; }
-            const uint64_t *p = reinterpret_cast<const uint64_t *>(row_src(q));
             const size_t n = ins[q.arr].inner * nb;
-            const uint64_t v = p[0];
-            uint64_t acc = 0;
-            size_t i = 0;
-            for (; i + 64 <= n && acc == 0; i += 64)
-                for (size_t e = 0; e < 64; e++) acc |= p[i + e] ^ v;
-            for (; i < n && acc == 0; i++) acc |= p[i] ^ v;
-            q.uniform = acc == 0;
-            q.bits = v;
-            if (cache[q.arr]) { cache[q.arr]->bits[q.row] = v; cache[q.arr]->state[q.row] = q.uniform ? 1 : 2; }      // (one thread per row)
+            // (a float row is uniform when its 4-byte patterns are equal; q.bits: the widened value's, what the fill writes)
+            if (ins[q.arr].src_esz == 4) q.uniform = hostrows::row_uniform(reinterpret_cast<const float *>(row_src(q)), n, &q.bits);
+            else q.uniform = hostrows::row_uniform(reinterpret_cast<const double *>(row_src(q)), n, &q.bits);
+            if (cache[q.arr]) { cache[q.arr]->bits[q.row] = q.bits; cache[q.arr]->state[q.row] = q.uniform ? 1 : 2; }      // (one thread per row)
         }
     });
     size_t need = 0;
-    for (auto &q : rows)
-        if (!q.uniform && !ins[q.arr].src_pinned) { q.off = need; need += ins[q.arr].inner * nb * 8; }
+    size_t nwiden = 0;
+    for (auto &q : rows) {
+        const HostIn &a = ins[q.arr];
+        if (q.uniform) continue;
+        if (a.src_esz == 4) nwiden++;
+        if (a.src_pinned) continue;
+        if (a.src_esz == 4) { need = align_up(need, 16); q.off = need; need += land_stride(a.inner * nb); }       // (as the row lies in the landing area)
+        else { q.off = need; need += a.inner * nb * 8; }
+    }
     auto &hs = G.hset[k];
     if (int rc = ensure_hostbuf(&hs.in, &hs.in_cap, need)) return rc;
     if (need)
         host_parallel(2 * need, [&](int t, int nt) {
             for (size_t j = (size_t)t; j < rows.size(); j += (size_t)nt) {
                 const StagedRow &q = rows[j];
-                if (!q.uniform && !ins[q.arr].src_pinned) memcpy(hs.in + q.off, row_src(q), ins[q.arr].inner * nb * 8);
+                if (!q.uniform && !ins[q.arr].src_pinned) memcpy(hs.in + q.off, row_src(q), ins[q.arr].inner * nb * ins[q.arr].src_esz);
             }
         });
     RowFill *tab = reinterpret_cast<RowFill *>(hs.fill);
-    size_t nf = 0;
+    if (int rc = ensure_hostbuf(&hs.widen, &hs.widen_cap, nwiden * sizeof(RowCvt))) return rc;          // (the pipeline has sized it for every row)
+    RowCvt *wtab = reinterpret_cast<RowCvt *>(hs.widen);
+    size_t nf = 0, nw = 0, wmax = 0;
     for (size_t j = 0; j < rows.size();) {
         const StagedRow &q = rows[j];
         const HostIn &a = ins[q.arr];
@@ -1697,6 +1725,15 @@ int stage_rows(std::vector<HostIn> &ins, size_t nb, int k, hipStream_t s)
         if (q.uniform) {
             for (size_t done = 0; done < nr * w; done += FILL_MAX)
                 tab[nf++] = RowFill{reinterpret_cast<unsigned long long *>(dst + done), std::min<unsigned long long>(FILL_MAX, nr * w - done), q.bits};
+        } else if (a.src_esz == 4) {
+            // float32 rows travel as they are into the landing area (a pinned array's from where they lie, 4-byte widths; a pageable
+            // array's from the pinned set, packed at the landing area's row stride) and are widened there, one table entry per row
+            const size_t st = land_stride(w);
+            float *land = a.land + st / 4 * q.row;
+            if (a.src_pinned) HIP_TRY(hipMemcpy2DAsync(land, st, row_src(q), a.inner * a.src_ncol * 4, w * 4, nr, hipMemcpyHostToDevice, s));
+            else HIP_TRY(hipMemcpyAsync(land, hs.in + q.off, nr * st, hipMemcpyHostToDevice, s));
+            for (size_t r = 0; r < nr; r++) wtab[nw++] = RowCvt{dst + w * r, land + st / 4 * r, w};
+            wmax = std::max(wmax, w);
         } else if (a.src_pinned) {
             HIP_TRY(hipMemcpy2DAsync(dst, w * 8, row_src(q), a.inner * a.src_ncol * 8, w * 8, nr, hipMemcpyHostToDevice, s));
         } else {
@@ -1706,6 +1743,8 @@ int stage_rows(std::vector<HostIn> &ins, size_t nb, int k, hipStream_t s)
     }
     for (size_t f0 = 0; f0 < nf; f0 += 65535)
         hipLaunchKernelGGL(k_fill_rows, dim3(FILL_BLOCKS, (unsigned)std::min<size_t>(65535, nf - f0)), dim3(256), 0, s, (const RowFill *)(tab + f0));
+    for (size_t f0 = 0; f0 < nw; f0 += 65535)
+        LAUNCH("k_widen_rows", k_widen_rows, dim3(cvt_blocks(wmax), (unsigned)std::min<size_t>(65535, nw - f0)), dim3(256), s, (const RowCvt *)(wtab + f0));
     return 0;
 }
 
@@ -1744,37 +1783,69 @@ template <class Body, class Prep>
 int host_pipeline_run(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &ins, std::vector<HostOut> &outs, Body body, Prep prep, std::vector<hipEvent_t> &tev)
 {   // columns [c0, c1) of arrays that are ncol columns wide
     if (int rc = ensure_copy_streams()) return rc;
-    size_t set = 0, nrows = 0, out_pageable = 0;
+    // (4-byte arrays, the *_r4 entries: behind a set's float64 arrays its float32 landing area - the input rows that travel arrive there and
+    // are widened into the float64 arrays, the active output rows are narrowed into it and leave from there; `land` its bytes)
+    size_t set = 0, nrows = 0, out_pageable = 0, land = 0, widen_rows = 0, narrow_rows = 0;
     for (auto &a : ins) {
         set += a.h ? a.inner * a.rows * (size_t)nbmax : 0;
         nrows += a.h ? a.rows + a.inner * a.rows * (size_t)nbmax / FILL_MAX + 1 : 0;
-        a.pinned = a.h && host_range_pinned(a.h, a.inner * (size_t)ncol * a.rows * 8);
-        a.static_gen = a.h ? static_gen_of(a.h, a.inner * (size_t)ncol * a.rows * 8) : 0;
+        a.pinned = a.h && host_range_pinned(a.h, a.inner * (size_t)ncol * a.rows * a.esz);
+        a.static_gen = a.h ? static_gen_of(a.h, a.inner * (size_t)ncol * a.rows * a.esz) : 0;
+        if (a.h && a.esz == 4) { land += a.rows * land_stride(a.inner * (size_t)nbmax); widen_rows += a.rows; }
     }
     for (auto &a : outs) {
         set += a.rows * (size_t)nbmax;
-        a.pinned = a.active && a.h && host_range_pinned(a.h, (size_t)ncol * a.rows * 8);
-        if (a.active && a.h && !a.pinned) out_pageable += a.rows * (size_t)nbmax * 8;
+        a.pinned = a.active && a.h && host_range_pinned(a.h, (size_t)ncol * a.rows * a.esz);
+        if (a.active && a.h && !a.pinned) out_pageable += a.esz == 4 ? a.rows * land_stride((size_t)nbmax) : a.rows * (size_t)nbmax * 8;
+        if (a.active && a.h && a.esz == 4) { land += a.rows * land_stride((size_t)nbmax); narrow_rows += a.rows; }
     }
-    set = align_up(set * 8, 256);
+    const size_t set64 = align_up(set * 8, 256);
+    set = set64 + align_up(land, 256);
     if (int rc = ensure_stage(HOST_SETS * set + 4096)) return rc;
     for (auto &hs : G.hset) {
         if (int rc = ensure_hostbuf(&hs.fill, &hs.fill_cap, nrows * sizeof(RowFill))) return rc;
         if (int rc = ensure_hostbuf(&hs.out, &hs.out_cap, out_pageable)) return rc;
+        if (int rc = ensure_hostbuf(&hs.widen, &hs.widen_cap, widen_rows * sizeof(RowCvt))) return rc;
+        if (int rc = ensure_hostbuf(&hs.narrow, &hs.narrow_cap, narrow_rows * sizeof(RowCvt))) return rc;
     }
     auto bind = [&](int k) {                 // point the descriptors at staging set k
         double *p = (double *)((char *)G.stage_base + (size_t)k * set);
         for (auto &a : ins) { a.d = a.h ? p : nullptr; p += a.h ? a.inner * a.rows * (size_t)nbmax : 0; }
         for (auto &a : outs) { a.d = p; p += a.rows * (size_t)nbmax; }
+        if (land == 0) return;
+        char *q = (char *)G.stage_base + (size_t)k * set + set64;
+        for (auto &a : ins) { const bool on = a.h && a.esz == 4; a.land = on ? (float *)q : nullptr; q += on ? a.rows * land_stride(a.inner * (size_t)nbmax) : 0; }
+        for (auto &a : outs) { const bool on = a.active && a.h && a.esz == 4; a.land = on ? (float *)q : nullptr; q += on ? a.rows * land_stride((size_t)nbmax) : 0; }
     };
+    bool narrowed[HOST_SETS] = {};           // the narrow table of set k has been handed to a launch of this call
     struct Pending { bool on = false; int col0 = 0, nb = 0; } pend[HOST_SETS];
     auto copy_out = [&](int k, int col0, int nb) -> int {
         bind(k);
         HIP_TRY(hipStreamWaitEvent(G.cp_out, G.ev_cmp[k], 0));
         char *p = G.hset[k].out;
         bool any = false;
+        if (narrow_rows) {
+            // the active float32 outputs: their staged float64 rows rounded into the landing area by one launch behind the batch's kernels
+            // (the table is this set's own: the launch that read it last has ended once the D2H behind it has)
+            if (narrowed[k]) HIP_TRY(hipEventSynchronize(G.ev_d2h[k]));
+            RowCvt *ntab = reinterpret_cast<RowCvt *>(G.hset[k].narrow);
+            size_t nn = 0;
+            for (auto &a : outs)
+                for (size_t r = 0; a.land && r < a.rows; r++) ntab[nn++] = RowCvt{a.d + (size_t)nb * r, a.land + land_stride((size_t)nb) / 4 * r, (unsigned long long)nb};
+            for (size_t f0 = 0; f0 < nn; f0 += 65535)
+                LAUNCH("k_narrow_rows", k_narrow_rows, dim3(cvt_blocks((size_t)nb), (unsigned)std::min<size_t>(65535, nn - f0)), dim3(256), G.cp_out, (const RowCvt *)(ntab + f0));
+            narrowed[k] = true;
+        }
         for (auto &a : outs) {
             if (!a.active || !a.h) continue;
+            if (a.esz == 4) {                // 4-byte rows out of the landing area
+                const size_t st = land_stride((size_t)nb);
+                if (a.pinned) { HIP_TRY(hipMemcpy2DAsync((char *)a.h + (size_t)col0 * 4, (size_t)ncol * 4, a.land, st, (size_t)nb * 4, a.rows, hipMemcpyDeviceToHost, G.cp_out)); continue; }
+                HIP_TRY(hipMemcpyAsync(p, a.land, a.rows * st, hipMemcpyDeviceToHost, G.cp_out));
+                p += a.rows * st;
+                any = true;
+                continue;
+            }
             const size_t w = (size_t)nb * 8, sp = (size_t)ncol * 8;
             if (a.pinned) { HIP_TRY(hipMemcpy2DAsync(a.h + col0, sp, a.d, w, w, a.rows, hipMemcpyDeviceToHost, G.cp_out)); continue; }
             HIP_TRY(hipMemcpyAsync(p, a.d, a.rows * w, hipMemcpyDeviceToHost, G.cp_out));
@@ -1796,22 +1867,24 @@ int host_pipeline_run(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &
         pend[k].on = false;
         HIP_TRY(hipEventSynchronize(G.ev_d2h[k]));
         const size_t nb = (size_t)pend[k].nb, col0 = (size_t)pend[k].col0;
-        struct Seg { double *dst; const double *src; size_t rows; };
+        struct Seg { char *dst; const char *src; size_t rows, dpitch, spitch, w; };          // (bytes: rows of 8- or of 4-byte values)
         std::vector<Seg> segs;
-        size_t tot = 0;
+        size_t tot = 0, bytes = 0;
         const char *p = G.hset[k].out;
         for (auto &a : outs) {
             if (!a.active || !a.h || a.pinned) continue;
-            segs.push_back({a.h + col0, (const double *)p, a.rows});
-            p += a.rows * nb * 8;
+            const size_t sp = a.esz == 4 ? land_stride(nb) : nb * 8;
+            segs.push_back({(char *)a.h + col0 * a.esz, p, a.rows, (size_t)ncol * a.esz, sp, nb * a.esz});
+            p += a.rows * sp;
             tot += a.rows;
+            bytes += a.rows * nb * a.esz;
         }
-        host_parallel(2 * tot * nb * 8, [&](int t, int nt) {
+        host_parallel(2 * bytes, [&](int t, int nt) {
             const size_t r0 = tot * (size_t)t / (size_t)nt, r1 = tot * (size_t)(t + 1) / (size_t)nt;
             size_t base = 0;
             for (auto &sg : segs) {
-                for (size_t r = std::max(r0, base); r < std::min(r1, base + sg.rows); r++)
-                    memcpy(sg.dst + (size_t)ncol * (r - base), sg.src + nb * (r - base), nb * 8);
+                const size_t a0 = std::max(r0, base), a1 = std::min(r1, base + sg.rows);
+                if (a0 < a1) hostrows::copy_rows(sg.dst, sg.dpitch, sg.src, sg.spitch, sg.w, a0 - base, a1 - base);
                 base += sg.rows;
             }
         });
@@ -1832,7 +1905,7 @@ int host_pipeline_run(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &
             if (int rc = unpack(k, true)) return rc;
             clk.lap(1);
         }
-        for (auto &a : ins) { a.src = a.h; a.src_ncol = (size_t)ncol; a.src_col0 = (size_t)col0; a.src_pinned = a.pinned; a.skip = nullptr; a.known = nullptr; a.known_bits = nullptr; }
+        for (auto &a : ins) { a.src = a.h; a.src_ncol = (size_t)ncol; a.src_col0 = (size_t)col0; a.src_pinned = a.pinned; a.src_esz = a.esz; a.skip = nullptr; a.known = nullptr; a.known_bits = nullptr; }
         // the entry's own host work for this batch (reductions into its pinned scratch set k, which it then names as an array's source)
         if (int rc = prep(k, col0, nb, G.cp_in)) return rc;
         clk.lap(2);
@@ -2293,6 +2366,8 @@ static void finalize_state()
         if (hs.in) (void)hipHostFree(hs.in);
         if (hs.out) (void)hipHostFree(hs.out);
         if (hs.fill) (void)hipHostFree(hs.fill);
+        if (hs.widen) (void)hipHostFree(hs.widen);
+        if (hs.narrow) (void)hipHostFree(hs.narrow);
     }
     G = State();
 }
@@ -2614,6 +2689,24 @@ static int nomcica_device(const CallDesc &d, const GcmIn &g, const FluxOut &out,
 #define CLOUD_NAMES cldfr, taucld, cicewp, cliqwp, reice, reliq
 #define OUT_NAMES uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt
 #define SPEC_NAMES nullptr, nullptr, uflxs, dflxs, uflxcs, dflxcs          /* (fnet, fnetc: the column entry's) */
+// ... and with float arrays (the *_r4 entries); AS_: an array of another element type as the address GcmIn / FluxOut carry
+#define GCM_PARAMS_R4                                                                                           \
+    const float *play, const float *plev, const float *tlay, const float *tlev, const float *tsfc,              \
+    const float *h2ovmr, const float *o3vmr, const float *co2vmr, const float *ch4vmr, const float *n2ovmr,     \
+    const float *o2vmr, const float *cfc11vmr, const float *cfc12vmr, const float *cfc22vmr,                    \
+    const float *ccl4vmr, const float *emis
+#define OUT_PARAMS_R4                                                                                           \
+    float *uflx, float *dflx, float *hr, float *uflxc, float *dflxc, float *hrc, float *duflx_dt, float *duflxc_dt
+#define CLOUD_PARAMS_R4                                                                                         \
+    const float *cldfr, const float *taucld, const float *cicewp, const float *cliqwp, const float *reice, const float *reliq
+#define NOMCICA_PARAMS_R4                                                                                       \
+    int ncol, int nlay, int *icld, int idrv, GCM_PARAMS_R4, int inflglw, int iceflglw, int liqflglw, CLOUD_PARAMS_R4, const float *tauaer, OUT_PARAMS_R4
+#define AS_(name) (const double *)name
+#define GCM_NAMES_AS                                                                                            \
+    AS_(play), AS_(plev), AS_(tlay), AS_(tlev), AS_(tsfc), AS_(h2ovmr), AS_(o3vmr), AS_(co2vmr), AS_(ch4vmr), AS_(n2ovmr), AS_(o2vmr), \
+    AS_(cfc11vmr), AS_(cfc12vmr), AS_(cfc22vmr), AS_(ccl4vmr), AS_(emis)
+#define CLOUD_NAMES_AS AS_(cldfr), AS_(taucld), AS_(cicewp), AS_(cliqwp), AS_(reice), AS_(reliq)
+#define OUT_NAMES_AS (double *)uflx, (double *)dflx, (double *)hr, (double *)uflxc, (double *)dflxc, (double *)hrc, (double *)duflx_dt, (double *)duflxc_dt
 
 int rrtmg_lw_hip_run_nomcica_device(NOMCICA_PARAMS, void *stream)
 {
@@ -2646,7 +2739,7 @@ int nomcica_host_range(const CallDesc &d, int icld, int c0, int c1, const GcmIn 
     //  * rows that hold one value for all columns of a batch - zero aerosol / cloud rows, well-mixed gases - are not copied (stage_rows).
     const bool use_tot = cloud && d.inflg != 0;
     std::vector<HostIn> ins;
-    if (int rc = host_ins(ins, g, nullptr, L, cloud, use_tot ? 1 : NBND)) return rc;
+    if (int rc = host_ins(ins, g, nullptr, L, cloud, use_tot ? 1 : NBND, NA_GCM, "", d.esz)) return rc;
     if (use_tot && G.h_tot_doubles < HOST_SETS * L * (size_t)nbmax) {
         if (G.h_tot) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipHostFree(G.h_tot)); G.h_tot = nullptr; G.h_tot_doubles = 0; }
         HIP_TRY(hipHostMalloc((void **)&G.h_tot, HOST_SETS * L * (size_t)nbmax * sizeof(double), hipHostMallocDefault));
@@ -2656,13 +2749,14 @@ int nomcica_host_range(const CallDesc &d, int icld, int c0, int c1, const GcmIn 
     std::vector<uint64_t> cf_bits(L, 0);
     auto prep = [&](int k, int col0, int nb, hipStream_t) -> int {
         if (!cloud) return 0;
-        rows_below(g.cldfr, 1, L, (size_t)ncol, (size_t)col0, (size_t)nb, 1.e-20, cloudfree.data(), cf_uni.data(), cf_bits.data());
+        if (d.esz == 4) rows_below((const float *)g.cldfr, 1, L, (size_t)ncol, (size_t)col0, (size_t)nb, 1.e-20, cloudfree.data(), cf_uni.data(), cf_bits.data());
+        else rows_below(g.cldfr, 1, L, (size_t)ncol, (size_t)col0, (size_t)nb, 1.e-20, cloudfree.data(), cf_uni.data(), cf_bits.data());
         skip_cloudfree(ins, cloudfree.data(), cf_uni.data(), cf_bits.data());
         if (!use_tot) return 0;
         double *tot = G.h_tot + (size_t)k * L * (size_t)nbmax;        // (the pipeline has waited for the copies that read scratch set k last)
         size_t cloudy_layers = 0;
         for (size_t l = 0; l < L; l++) cloudy_layers += cloudfree[l] ? 0 : 1;
-        host_parallel((size_t)NBND * cloudy_layers * (size_t)nb * 8, [&](int t, int nt) {
+        host_parallel((size_t)NBND * cloudy_layers * (size_t)nb * d.esz, [&](int t, int nt) {
             // (pieces of 4 096 columns of a layer, dealt round-robin: the cloudy layers are few)
             const size_t piece = 4096, per = ((size_t)nb + piece - 1) / piece;
             size_t task = 0;
@@ -2671,6 +2765,12 @@ int nomcica_host_range(const CallDesc &d, int icld, int c0, int c1, const GcmIn 
                 for (size_t pc = 0; pc < per; pc++, task++) {
                     if (task % (size_t)nt != (size_t)t) continue;
                     const size_t c1 = std::min((size_t)nb, (pc + 1) * piece);
+                    // (float bands: each widened, added in float64 in the same order - the float64 entry's sum on the widened array)
+                    if (d.esz == 4) {
+                        const float *p = (const float *)g.taucld + (size_t)NBND * ((size_t)col0 + pc * piece + (size_t)ncol * lay);
+                        for (size_t c = pc * piece; c < c1; c++, p += NBND) tot[lay * (size_t)nb + c] = hostrows::band_sum(p, NBND);
+                        continue;
+                    }
                     for (size_t c = pc * piece; c < c1; c++) {
                         const double *p = g.taucld + (size_t)NBND * ((size_t)col0 + c + (size_t)ncol * lay);
                         double sum = 0.0;
@@ -2681,11 +2781,11 @@ int nomcica_host_range(const CallDesc &d, int icld, int c0, int c1, const GcmIn 
             }
         });
         HostIn &tc = ins[staged_at(A_TAUCLD)];
-        tc.src = tot; tc.src_ncol = (size_t)nb; tc.src_col0 = 0; tc.src_pinned = true;      // rows of nb sums, from the pinned scratch
+        tc.src = tot; tc.src_ncol = (size_t)nb; tc.src_col0 = 0; tc.src_pinned = true; tc.src_esz = 8;      // rows of nb float64 sums, from the pinned scratch
         return 0;
     };
     if (!have_outs(o)) return fail(RRTMG_LW_HIP_EARG, "null output array");
-    std::vector<HostOut> outs = host_outs(o, L, idrv);
+    std::vector<HostOut> outs = host_outs(o, L, idrv, d.esz);
     auto body = [&](hipStream_t s, int nb, int, std::vector<HostIn> &in, std::vector<HostOut> &out_) -> int {
         GcmIn gd = staged_gcm(in);
         if (use_tot) { gd.tauctot = gd.taucld; gd.taucld = nullptr; }
@@ -2753,6 +2853,14 @@ int rrtmg_lw_hip_run_nomcica_spectral(NOMCICA_PARAMS, SPEC_PARAMS)
 {
     ENTRY_LOCK;
     return nomcica_host(spectral({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw}), {GCM_NAMES, CLOUD_NAMES, tauaer}, {OUT_NAMES, SPEC_NAMES});
+}
+
+// float32 host arrays (the header's "_r4" section): the same call with 4-byte elements below the entry; takes the entry lock like the
+// spectral entry, a small call does not join the combining one
+int rrtmg_lw_hip_run_nomcica_r4(NOMCICA_PARAMS_R4)
+{
+    ENTRY_LOCK;
+    return nomcica_host(real4({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw}), {GCM_NAMES_AS, CLOUD_NAMES_AS, AS_(tauaer)}, {OUT_NAMES_AS});
 }
 
 // calls and device passes of the combining entry since the library was loaded (a pass serves one or more calls)
@@ -3365,13 +3473,13 @@ static int mcica_host(const CallDesc &d, const GcmIn &g, const McIn &m, const Fl
     if (int rc = check_common(ncol, nlay)) return rc;
     HIP_TRY(hipDeviceSynchronize());        // asynchronous device-entry work of earlier calls shares the workspace
     // the sub-column arrays are 4 x 140 x nlay doubles per column: bound the batch so that staging stays below ~4 GB
-    const int mcmax = (int)std::max<size_t>(64, ((size_t)1 << 30) / ((size_t)4 * NGPT * nlay * 8));        // (HOST_SETS staging sets of 1 GiB)
+    const int mcmax = (int)std::max<size_t>(64, ((size_t)1 << 30) / ((size_t)4 * NGPT * nlay * (8 + (d.esz == 4 ? 4 : 0))));        // (HOST_SETS staging sets of 1 GiB; float32 arrays: with their landing area)
     const int nbmax = balanced_batch(c1 - c0, std::min(std::min(eff_batch(nlay), HOST_BATCH), cloud ? mcmax : HOST_BATCH));
     if (int rc = ensure_workspace(nlay, nbmax, cloud, cloud, idrv, mode)) return rc;
     const size_t L = (size_t)nlay;
     std::vector<HostIn> ins;
-    if (int rc = host_ins(ins, g, &m, L, cloud, NGPT)) return rc;
-    std::vector<HostOut> outs = host_outs(out, L, idrv);
+    if (int rc = host_ins(ins, g, &m, L, cloud, NGPT, NA_GCM, "", d.esz)) return rc;
+    std::vector<HostOut> outs = host_outs(out, L, idrv, d.esz);
     auto body = [&](hipStream_t s, int nb, int, std::vector<HostIn> &in, std::vector<HostOut> &out_) -> int {
         GcmIn gd = staged_gcm(in);          // (the sub-column arrays stand in the cloud arrays' places)
         const McIn md{gd.cldfr, gd.taucld, gd.cicewp, gd.cliqwp, gd.reice, gd.reliq};
@@ -3383,7 +3491,8 @@ static int mcica_host(const CallDesc &d, const GcmIn &g, const McIn &m, const Fl
     std::vector<uint64_t> cf_bits(L, 0);
     auto prep = [&](int, int col0, int nb, hipStream_t) -> int {
         if (!cloud) return 0;
-        rows_below(m.cldfmcl, NGPT, L, (size_t)ncol, (size_t)col0, (size_t)nb, 1.e-20, cloudfree.data(), cf_uni.data(), cf_bits.data());
+        if (d.esz == 4) rows_below((const float *)m.cldfmcl, NGPT, L, (size_t)ncol, (size_t)col0, (size_t)nb, 1.e-20, cloudfree.data(), cf_uni.data(), cf_bits.data());
+        else rows_below(m.cldfmcl, NGPT, L, (size_t)ncol, (size_t)col0, (size_t)nb, 1.e-20, cloudfree.data(), cf_uni.data(), cf_bits.data());
         skip_cloudfree(ins, cloudfree.data(), cf_uni.data(), cf_bits.data());
         return 0;
     };
@@ -3395,6 +3504,13 @@ static int mcica_host(const CallDesc &d, const GcmIn &g, const McIn &m, const Fl
 int rrtmg_lw_hip_run_mcica(MCICA_PARAMS)
 {
     return mcica_host({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw}, {GCM_NAMES, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tauaer}, {cldfmcl, taucmcl, ciwpmcl, clwpmcl, reicmcl, relqmcl}, {OUT_NAMES});
+}
+int rrtmg_lw_hip_run_mcica_r4(int ncol, int nlay, int *icld, int idrv, GCM_PARAMS_R4, int inflglw, int iceflglw, int liqflglw,
+    const float *cldfmcl, const float *taucmcl, const float *ciwpmcl, const float *clwpmcl, const float *reicmcl, const float *relqmcl,
+    const float *tauaer, OUT_PARAMS_R4)
+{
+    return mcica_host(real4({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw}), {GCM_NAMES_AS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, AS_(tauaer)},
+                      {AS_(cldfmcl), AS_(taucmcl), AS_(ciwpmcl), AS_(clwpmcl), AS_(reicmcl), AS_(relqmcl)}, {OUT_NAMES_AS});
 }
 int rrtmg_lw_hip_run_mcica_spectral(MCICA_PARAMS, SPEC_PARAMS)
 {
@@ -3568,11 +3684,29 @@ static int mcica_subcol_host_range(const CallDesc &d, int icld_gen, int irng, in
     double *d_gen = nullptr;
     if (cloud) {
         if (!g.play || !g.cldfr || (two && !alpha)) return fail(RRTMG_LW_HIP_EARG, "null generator input");
-        HIP_TRY(hipMalloc((void **)&d_gen, nl * L * 8 * 3));
+        const bool r4 = d.esz == 4;
+        HIP_TRY(hipMalloc((void **)&d_gen, nl * L * (r4 ? 12 : 8) * 3));
         // (through the library's own pinned buffer: see bounce_h2d)
-        int rc = bounce_h2d_rows(d_gen, g.play + c0, nl * 8, n * 8, L);
-        if (rc == 0) rc = bounce_h2d_rows(d_gen + nl * L, g.cldfr + c0, nl * 8, n * 8, L);
-        if (rc == 0 && two) rc = bounce_h2d_rows(d_gen + 2 * nl * L, alpha + c0, nl * 8, n * 8, L);
+        int rc = 0;
+        if (r4) {
+            // float arrays: the three travel as float32 behind the float64 ones and are widened there (k_widen_rows, an entry each)
+            float *f_gen = reinterpret_cast<float *>(d_gen + 3 * nl * L);
+            const double *src[3] = {g.play, g.cldfr, two ? alpha : nullptr};
+            auto &hs = G.hset[0];
+            rc = ensure_hostbuf(&hs.widen, &hs.widen_cap, 3 * sizeof(RowCvt));
+            RowCvt *wtab = reinterpret_cast<RowCvt *>(hs.widen);
+            unsigned nw = 0;
+            for (size_t a = 0; a < 3 && rc == 0; a++) {
+                if (!src[a]) continue;
+                rc = bounce_h2d_rows(f_gen + a * nl * L, (const float *)src[a] + c0, nl * 4, n * 4, L);
+                wtab[nw++] = RowCvt{d_gen + a * nl * L, f_gen + a * nl * L, nl * L};
+            }
+            if (rc == 0) LAUNCH("k_widen_rows", k_widen_rows, dim3(cvt_blocks(nl * L), nw), dim3(256), s, (const RowCvt *)wtab);
+        } else {
+            rc = bounce_h2d_rows(d_gen, g.play + c0, nl * 8, n * 8, L);
+            if (rc == 0) rc = bounce_h2d_rows(d_gen + nl * L, g.cldfr + c0, nl * 8, n * 8, L);
+            if (rc == 0 && two) rc = bounce_h2d_rows(d_gen + 2 * nl * L, alpha + c0, nl * 8, n * 8, L);
+        }
         if (rc == 0) rc = generate_mask(s, nloc, nlay, icld_gen, d.permuteseed, irng, d_gen, d_gen + nl * L, two ? d_gen + 2 * nl * L : nullptr);
         if (rc == 0 && hipStreamSynchronize(s) != hipSuccess) rc = fail(RRTMG_LW_HIP_EHIP, "generator failed");
         (void)hipFree(d_gen);
@@ -3580,9 +3714,9 @@ static int mcica_subcol_host_range(const CallDesc &d, int icld_gen, int irng, in
     }
     // 2. column batches
     std::vector<HostIn> ins;
-    if (int rc = host_ins(ins, g, nullptr, L, cloud, NBND)) return rc;
+    if (int rc = host_ins(ins, g, nullptr, L, cloud, NBND, NA_GCM, "", d.esz)) return rc;
     if (!have_outs(out)) return fail(RRTMG_LW_HIP_EARG, "null output array");
-    std::vector<HostOut> outs = host_outs(out, L, idrv);
+    std::vector<HostOut> outs = host_outs(out, L, idrv, d.esz);
     auto body = [&](hipStream_t bs, int nb, int col0, std::vector<HostIn> &in, std::vector<HostOut> &out_) -> int {
         G.W.mask_col0 = (size_t)(col0 - c0);                      // staged arrays start at column 0, the mask holds the block's columns
         return run_batch<true>(bs, staged_batch(d, mode, nb), staged_gcm(in), ColIn{}, staged_flux(out_));
@@ -3631,6 +3765,14 @@ int rrtmg_lw_hip_run_mcica_subcol(SUBCOL_PARAMS)
     }
     ENTRY_LOCK;
     return mcica_subcol_host(d, g, alpha, out);
+}
+
+// float32 host arrays, alpha too: the entry lock, no combining (like the spectral entry)
+int rrtmg_lw_hip_run_mcica_subcol_r4(int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng, GCM_PARAMS_R4, int inflglw, int iceflglw, int liqflglw,
+    CLOUD_PARAMS_R4, const float *alpha, const float *tauaer, OUT_PARAMS_R4)
+{
+    ENTRY_LOCK;
+    return mcica_subcol_host(real4({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng}), {GCM_NAMES_AS, CLOUD_NAMES_AS, AS_(tauaer)}, AS_(alpha), {OUT_NAMES_AS});
 }
 
 // the same with spectral outputs: does not join the combining entry (the entry lock, like any other call)
@@ -3967,7 +4109,7 @@ int adjust_device(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, const Ad
 }
 
 // columns [c0, c1) of a host-pointer call on the calling thread's current device state (the fan-out's worker); no lock taken
-int adjust_host_range(int ncol, int c0, int c1, int nlay, const AdjustIn &in, const AdjustOut &o, bool clear)
+int adjust_host_range(int ncol, int c0, int c1, int nlay, const AdjustIn &in, const AdjustOut &o, bool clear, size_t esz = 8)
 {
     const size_t L = (size_t)nlay;
     const auto d = [](const void *p) { return static_cast<const double *>(p); };
@@ -3979,6 +4121,9 @@ int adjust_host_range(int ncol, int c0, int c1, int nlay, const AdjustIn &in, co
         outs.push_back(HostOut{static_cast<double *>(o.uflxc_adj), L + 1, nullptr, true});
         outs.push_back(HostOut{static_cast<double *>(o.hrc_adj), L, nullptr, true});
     }
+    // (esz = 4: the caller's arrays are float; the staged ones, widened, are float64 as ever, and so is the arithmetic)
+    for (auto &a : ins) a.esz = esz;
+    for (auto &a : outs) a.esz = esz;
     const int nbmax = balanced_batch(c1 - c0, std::min(eff_batch(nlay), HOST_BATCH));
     const rrtmg_lw_hip_array_form ref{8, 0, 0};
     auto body = [&](hipStream_t s, int nb, int, std::vector<HostIn> &i_, std::vector<HostOut> &o_) -> int {
@@ -4005,6 +4150,18 @@ int rrtmg_lw_hip_adjust_tsfc(int ncol, int nlay, const double *plev, const doubl
     return fan_out(ncol, [&](int c0, int c1) { return adjust_host_range(ncol, c0, c1, nlay, in, o, clear); });
 }
 
+int rrtmg_lw_hip_adjust_tsfc_r4(int ncol, int nlay, const float *plev, const float *dtsfc,
+    const float *uflx, const float *dflx, const float *duflx_dt, const float *uflxc, const float *dflxc, const float *duflxc_dt,
+    float *uflx_adj, float *hr_adj, float *uflxc_adj, float *hrc_adj)
+{
+    ENTRY_LOCK;
+    const AdjustIn in{plev, dtsfc, uflx, dflx, duflx_dt, uflxc, dflxc, duflxc_dt};
+    const AdjustOut o{uflx_adj, hr_adj, uflxc_adj, hrc_adj};
+    bool clear = false;
+    if (int rc = check_adjust(ncol, nlay, 4, in, o, &clear)) return rc;
+    return fan_out(ncol, [&](int c0, int c1) { return adjust_host_range(ncol, c0, c1, nlay, in, o, clear, 4); });
+}
+
 int rrtmg_lw_hip_adjust_tsfc_device(int ncol, int nlay, const double *plev, const double *dtsfc,
     const double *uflx, const double *dflx, const double *duflx_dt, const double *uflxc, const double *dflxc, const double *duflxc_dt,
     double *uflx_adj, double *hr_adj, double *uflxc_adj, double *hrc_adj, void *stream)
@@ -4024,7 +4181,6 @@ int rrtmg_lw_hip_adjust_tsfc_device_as(const rrtmg_lw_hip_array_form *form, int 
     return adjust_device(*form, ncol, nlay, {plev, dtsfc, uflx, dflx, duflx_dt, uflxc, dflxc, duflxc_dt}, {uflx_adj, hr_adj, uflxc_adj, hrc_adj}, stream);
 }
 
-#define AS_(name) (const double *)name
 #define GCM_PARAMS_AS                                                                                           \
     const void *play, const void *plev, const void *tlay, const void *tlev, const void *tsfc,                   \
     const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *n2ovmr,          \
@@ -4032,11 +4188,6 @@ int rrtmg_lw_hip_adjust_tsfc_device_as(const rrtmg_lw_hip_array_form *form, int 
     const void *ccl4vmr, const void *emis
 #define CLOUD_PARAMS_AS const void *cldfr, const void *taucld, const void *cicewp, const void *cliqwp, const void *reice, const void *reliq
 #define OUT_PARAMS_AS void *uflx, void *dflx, void *hr, void *uflxc, void *dflxc, void *hrc, void *duflx_dt, void *duflxc_dt
-#define GCM_NAMES_AS                                                                                            \
-    AS_(play), AS_(plev), AS_(tlay), AS_(tlev), AS_(tsfc), AS_(h2ovmr), AS_(o3vmr), AS_(co2vmr), AS_(ch4vmr), AS_(n2ovmr), AS_(o2vmr), \
-    AS_(cfc11vmr), AS_(cfc12vmr), AS_(cfc22vmr), AS_(ccl4vmr), AS_(emis)
-#define CLOUD_NAMES_AS AS_(cldfr), AS_(taucld), AS_(cicewp), AS_(cliqwp), AS_(reice), AS_(reliq)
-#define OUT_NAMES_AS (double *)uflx, (double *)dflx, (double *)hr, (double *)uflxc, (double *)dflxc, (double *)hrc, (double *)duflx_dt, (double *)duflxc_dt
 
 int rrtmg_lw_hip_run_nomcica_device_as(const rrtmg_lw_hip_array_form *form, int ncol, int nlay, int *icld, int idrv, GCM_PARAMS_AS,
     int inflglw, int iceflglw, int liqflglw, CLOUD_PARAMS_AS, const void *tauaer, OUT_PARAMS_AS, void *stream)

@@ -4481,6 +4481,77 @@ __global__ __launch_bounds__(256) void k_fill_rows(const RowFill *__restrict__ t
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_widen_rows / k_narrow_rows : the *_r4 host-pointer entries (float32 host arrays).  A float32 row crosses PCIe as float32 into the
+//               staging set's landing area and is widened into the float64 row the solver reads; a staged float64 output row is rounded
+//               to nearest into the landing area and leaves as float32.  Entry blockIdx.y of the table (pinned host memory, like
+//               k_fill_rows') names one row: its float64 address d, its float32 address f and its n values; gridDim.x workgroups share it.
+//               A lane moves 16 bytes on the float32 side - four values - once the head has brought f to a 16-byte boundary (landing rows
+//               start on one: no head there), and the 32 bytes on the float64 side as two 16-byte accesses where d is on such a boundary
+//               too, as 8 + 16 + 8 where it is not (row r of a staged array starts at inner * nb * r doubles: on an 8-byte boundary only,
+//               every other row, when inner * nb is odd).  Head and tail - at most three values each - go value by value.
+// ------------------------------------------------------------------------------------------------
+struct RowCvt { double *d; float *f; unsigned long long n; };
+constexpr int CVT_BLOCKS = 64;                            // workgroups per table entry at most (the launch takes fewer for short rows)
+constexpr unsigned long long CVT_LANE = 16;               // values a lane is meant to move: what the launch sizes gridDim.x by
+__device__ __forceinline__ unsigned long long cvt_head(const float *f, unsigned long long n)
+{
+    const unsigned long long h = ((16u - (unsigned)(reinterpret_cast<uintptr_t>(f) & 15u)) & 15u) >> 2;
+    return h < n ? h : n;
+}
+__global__ __launch_bounds__(256) void k_widen_rows(const RowCvt *__restrict__ tab)
+{
+    const RowCvt e = tab[blockIdx.y];
+    const unsigned long long head = cvt_head(e.f, e.n), nv = (e.n - head) / 4;
+    const float *f = e.f + head;
+    double *d = e.d + head;
+    const bool d16 = (reinterpret_cast<uintptr_t>(d) & 15u) == 0;
+    for (unsigned long long v = (unsigned long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (unsigned long long)gridDim.x * 256) {
+        const float4 x = *reinterpret_cast<const float4 *>(f + 4 * v);
+        double *o = d + 4 * v;
+        if (d16) {
+            *reinterpret_cast<double2 *>(o) = make_double2((double)x.x, (double)x.y);
+            *reinterpret_cast<double2 *>(o + 2) = make_double2((double)x.z, (double)x.w);
+        } else {
+            o[0] = (double)x.x;
+            *reinterpret_cast<double2 *>(o + 1) = make_double2((double)x.y, (double)x.z);
+            o[3] = (double)x.w;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 4) {
+        const unsigned long long t = threadIdx.x, t1 = head + 4 * nv + t;
+        if (t < head) e.d[t] = (double)e.f[t];
+        if (t1 < e.n) e.d[t1] = (double)e.f[t1];
+    }
+}
+__global__ __launch_bounds__(256) void k_narrow_rows(const RowCvt *__restrict__ tab)
+{
+    const RowCvt e = tab[blockIdx.y];
+    const unsigned long long head = cvt_head(e.f, e.n), nv = (e.n - head) / 4;
+    float *f = e.f + head;
+    const double *d = e.d + head;
+    const bool d16 = (reinterpret_cast<uintptr_t>(d) & 15u) == 0;
+    for (unsigned long long v = (unsigned long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (unsigned long long)gridDim.x * 256) {
+        const double *i = d + 4 * v;
+        float4 x;
+        if (d16) {
+            const double2 a = *reinterpret_cast<const double2 *>(i), b = *reinterpret_cast<const double2 *>(i + 2);
+            x = make_float4((float)a.x, (float)a.y, (float)b.x, (float)b.y);
+        } else {
+            const double a = i[0];
+            const double2 b = *reinterpret_cast<const double2 *>(i + 1);
+            const double c = i[3];
+            x = make_float4((float)a, (float)b.x, (float)b.y, (float)c);
+        }
+        *reinterpret_cast<float4 *>(f + 4 * v) = x;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 4) {
+        const unsigned long long t = threadIdx.x, t1 = head + 4 * nv + t;
+        if (t < head) e.f[t] = (float)e.d[t];
+        if (t1 < e.n) e.f[t1] = (float)e.d[t1];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_form_in / k_form_out : the *_as entries (include/rrtmg_lw_hip.h, rrtmg_lw_hip_array_form).  One launch brings every input array of
 //               a column batch from the caller's form (float32 or float64; reference order or column-slowest C order; surface or top
 //               first) into the float64 reference form, nb columns wide, that the solver's kernels read; one launch takes the staged

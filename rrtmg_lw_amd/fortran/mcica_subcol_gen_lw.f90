@@ -13,6 +13,19 @@
 
       public :: get_alpha, mcica_subcol_lw
 
+!  Both names are generic over the real kind.  For real(4) arrays (a host built with 4-byte reals) this pair is a CONVENIENCE: the
+!  specifics convert through float64 temporaries around the same two entries and round the results, so the sub-column arrays are what the
+!  real(kind_rb) generator gives on the widened inputs, rounded.  The fast way for such a host is the fused generator + solver entry,
+!  rrtmg_lw_hip_run_mcica_subcol_r4 (include/rrtmg_lw_hip.h, "_r4"), which never forms the sub-column arrays.
+      integer, parameter, private :: r4 = c_float
+
+      interface get_alpha
+         module procedure get_alpha_r8, get_alpha_r4
+      end interface
+      interface mcica_subcol_lw
+         module procedure mcica_subcol_lw_r8, mcica_subcol_lw_r4
+      end interface
+
       interface
          function rrtmg_lw_hip_get_alpha(ncol, nlay, icld, idcor, decorr_con, dz, lat, juldat, cldfrac, alpha) &
                bind(C, name='rrtmg_lw_hip_get_alpha') result(rc)
@@ -38,7 +51,7 @@
 
       contains
 
-      subroutine get_alpha(iplon, ncol, nlayers, icld, idcor, decorr_con, &
+      subroutine get_alpha_r8(iplon, ncol, nlayers, icld, idcor, decorr_con, &
                            dz, lat, juldat, cldfrac, alpha)
 
       integer(kind=im), intent(in) :: iplon           ! column/longitude index (unused, as in the reference)
@@ -64,9 +77,9 @@
       if (rc /= 0) call rrtmg_lw_hip_abort('get_alpha')
       alpha(1:ncol, 1:nlayers) = a
 
-      end subroutine get_alpha
+      end subroutine get_alpha_r8
 
-      subroutine mcica_subcol_lw(iplon, ncol, nlay, icld, permuteseed, irng, play, &
+      subroutine mcica_subcol_lw_r8(iplon, ncol, nlay, icld, permuteseed, irng, play, &
                        cldfrac, ciwp, clwp, rei, rel, tauc, alpha, cldfmcl, &
                        ciwpmcl, clwpmcl, reicmcl, relqmcl, taucmcl)
 
@@ -105,6 +118,54 @@
       if (rc /= 0) call rrtmg_lw_hip_abort('mcica_subcol_lw')
       irng = int(irng_c, im)
 
-      end subroutine mcica_subcol_lw
+      end subroutine mcica_subcol_lw_r8
+
+!  The real(4) specifics (see the module comment): float64 temporaries of the sections (1:ncol, 1:nlay) around the specifics above.
+      subroutine get_alpha_r4(iplon, ncol, nlayers, icld, idcor, decorr_con, &
+                              dz, lat, juldat, cldfrac, alpha)
+      integer(kind=im), intent(in) :: iplon, ncol, nlayers, icld, idcor, juldat
+      real(kind=r4), intent(in) :: decorr_con
+      real(kind=r4), intent(in) :: dz(:,:), lat(:), cldfrac(:,:)
+      real(kind=r4), intent(out) :: alpha(:,:)
+      real(kind=rb), allocatable :: a(:,:)
+
+      allocate(a(ncol, nlayers))
+      a = real(alpha(1:ncol, 1:nlayers), rb)          ! untouched unless icld is 4 or 5
+      call get_alpha_r8(iplon, ncol, nlayers, icld, idcor, real(decorr_con, rb), real(dz(1:ncol, 1:nlayers), rb), &
+            real(lat(1:ncol), rb), juldat, real(cldfrac(1:ncol, 1:nlayers), rb), a)
+      alpha(1:ncol, 1:nlayers) = real(a, r4)
+
+      end subroutine get_alpha_r4
+
+      subroutine mcica_subcol_lw_r4(iplon, ncol, nlay, icld, permuteseed, irng, play, &
+                       cldfrac, ciwp, clwp, rei, rel, tauc, alpha, cldfmcl, &
+                       ciwpmcl, clwpmcl, reicmcl, relqmcl, taucmcl)
+      integer(kind=im), intent(in) :: iplon, ncol, nlay, icld, permuteseed
+      integer(kind=im), intent(inout) :: irng
+      real(kind=r4), intent(in) :: play(:,:), cldfrac(:,:), tauc(:,:,:), ciwp(:,:), clwp(:,:), rei(:,:), rel(:,:), alpha(:,:)
+      real(kind=r4), intent(out) :: cldfmcl(:,:,:), ciwpmcl(:,:,:), clwpmcl(:,:,:), taucmcl(:,:,:)
+      real(kind=r4), intent(out) :: relqmcl(:,:), reicmcl(:,:)
+      real(kind=rb), allocatable :: g1(:,:,:), g2(:,:,:), g3(:,:,:), g4(:,:,:), e1(:,:), e2(:,:)
+      integer :: ng
+
+      if (icld == 0) return                            ! src/mcica_subcol_gen_lw.f90:265
+      ng = int(rrtmg_lw_hip_gpoints())
+      if (size(cldfmcl,1) < ng .or. size(cldfmcl,2) < ncol .or. size(cldfmcl,3) < nlay) then
+         write(*,'(a,i0,a,i0,a,i0,a)') 'mcica_subcol_lw: the sub-column arrays are smaller than (', ng, ',', ncol, ',', nlay, ')'
+         error stop 1
+      endif
+      allocate(g1(ng, ncol, nlay), g2(ng, ncol, nlay), g3(ng, ncol, nlay), g4(ng, ncol, nlay), e1(ncol, nlay), e2(ncol, nlay))
+      call mcica_subcol_lw_r8(iplon, ncol, nlay, icld, permuteseed, irng, real(play(1:ncol, 1:nlay), rb), &
+            real(cldfrac(1:ncol, 1:nlay), rb), real(ciwp(1:ncol, 1:nlay), rb), real(clwp(1:ncol, 1:nlay), rb), &
+            real(rei(1:ncol, 1:nlay), rb), real(rel(1:ncol, 1:nlay), rb), real(tauc(1:16, 1:ncol, 1:nlay), rb), &
+            real(alpha(1:ncol, 1:nlay), rb), g1, g2, g3, e1, e2, g4)
+      cldfmcl(1:ng, 1:ncol, 1:nlay) = real(g1, r4)
+      ciwpmcl(1:ng, 1:ncol, 1:nlay) = real(g2, r4)
+      clwpmcl(1:ng, 1:ncol, 1:nlay) = real(g3, r4)
+      taucmcl(1:ng, 1:ncol, 1:nlay) = real(g4, r4)
+      reicmcl(1:ncol, 1:nlay) = real(e1, r4)
+      relqmcl(1:ncol, 1:nlay) = real(e2, r4)
+
+      end subroutine mcica_subcol_lw_r4
 
       end module mcica_subcol_gen_lw

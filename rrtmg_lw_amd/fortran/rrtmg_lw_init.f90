@@ -12,6 +12,28 @@
 
       implicit none
 
+!  Every public name that takes real arguments is generic over the real kind: the reference's real(kind_rb) (8 bytes) and, for a host built
+!  with 4-byte reals (no -r8), real(4).  The compiler picks the specific by the kind of the actuals; a host needs no build switch.  The
+!  real(4) specifics hand the library 4 bytes per element (pin, static) - rrtmg_lw of such arrays goes through the library's _r4 entries
+!  (include/rrtmg_lw_hip.h, "_r4") - and rrtmg_lw_ini widens its cpdair.
+      integer, parameter, private :: r4 = c_float
+
+      interface rrtmg_lw_ini
+         module procedure rrtmg_lw_ini_r8, rrtmg_lw_ini_r4
+      end interface
+      interface rrtmg_lw_pin
+         module procedure rrtmg_lw_pin_r8, rrtmg_lw_pin_r4
+      end interface
+      interface rrtmg_lw_unpin
+         module procedure rrtmg_lw_unpin_r8, rrtmg_lw_unpin_r4
+      end interface
+      interface rrtmg_lw_static
+         module procedure rrtmg_lw_static_r8, rrtmg_lw_static_r4
+      end interface
+      interface rrtmg_lw_changed
+         module procedure rrtmg_lw_changed_r8, rrtmg_lw_changed_r4
+      end interface
+
       interface
          function rrtmg_lw_hip_init(static_path, kdata_path, cpdair, device) bind(C, name='rrtmg_lw_hip_init') result(rc)
             import :: c_char, c_double, c_int
@@ -63,7 +85,7 @@
 
       contains
 
-      subroutine rrtmg_lw_ini(cpdair)
+      subroutine rrtmg_lw_ini_r8(cpdair)
       real(kind=rb), intent(in) :: cpdair     ! Specific heat capacity of dry air at constant pressure at 273 K (J kg-1 K-1)
       character(len=1024) :: spath, kpath, dev
       integer :: ls, lk, ld, idev, ios, ndev, i
@@ -107,7 +129,7 @@
          rc = rrtmg_lw_hip_init(spath(1:ls)//c_null_char, kpath(1:lk)//c_null_char, real(cpdair, c_double), int(idev, c_int))
       endif
       if (rc /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_ini')
-      end subroutine rrtmg_lw_ini
+      end subroutine rrtmg_lw_ini_r8
 
 !  Optional, for a host model whose profile / flux arrays live for the whole run: page-lock an array once (after rrtmg_lw_ini), and
 !  rrtmg_lw's copies of it are direct DMA - no packing through the library's pinned staging by host threads.
@@ -115,7 +137,7 @@
 !  `a` is a whole, contiguous real(rb) array of any rank (assumed rank: the dummy is the caller's array itself, never a compiler-made
 !  copy - a section or an expression would be registered at the address of a temporary that is gone on return), `n` its number of
 !  elements (optional check).  A non-contiguous actual stops the run with a message instead of pinning the wrong memory.
-      subroutine rrtmg_lw_pin(a, n)
+      subroutine rrtmg_lw_pin_r8(a, n)
       real(kind=rb), intent(in), target :: a(..)
       integer, intent(in), optional :: n
       if (size(a) < 1) return
@@ -130,21 +152,21 @@
          endif
       endif
       if (rrtmg_lw_hip_host_register(c_loc(a), int(size(a), c_long_long) * 8_c_long_long) /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_pin')
-      end subroutine rrtmg_lw_pin
+      end subroutine rrtmg_lw_pin_r8
 
-      subroutine rrtmg_lw_unpin(a)
+      subroutine rrtmg_lw_unpin_r8(a)
       real(kind=rb), intent(in), target :: a(..)
       if (.not. is_contiguous(a)) then
          write(*,*) 'rrtmg_lw_unpin: the array is not contiguous (pass the whole array that was pinned)'
          error stop 1
       endif
       if (rrtmg_lw_hip_host_unregister(c_loc(a)) /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_unpin')
-      end subroutine rrtmg_lw_unpin
+      end subroutine rrtmg_lw_unpin_r8
 
 !  Optional: declare an input array of rrtmg_lw STATIC - it keeps its contents from call to call (well-mixed gases, aerosol optical depths
 !  that are set once, emissivities): rrtmg_lw then looks at its rows once instead of on every call.  After changing such an array:
 !  call rrtmg_lw_changed(a); before deallocating it: call rrtmg_lw_changed(a, .false.).  `a` is the whole, contiguous array.
-      subroutine rrtmg_lw_static(a)
+      subroutine rrtmg_lw_static_r8(a)
       real(kind=rb), intent(in), target :: a(..)
       if (size(a) < 1) return
       if (.not. is_contiguous(a)) then
@@ -152,9 +174,9 @@
          error stop 1
       endif
       if (rrtmg_lw_hip_host_static(c_loc(a), int(size(a), c_long_long) * 8_c_long_long) /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_static')
-      end subroutine rrtmg_lw_static
+      end subroutine rrtmg_lw_static_r8
 
-      subroutine rrtmg_lw_changed(a, keep)
+      subroutine rrtmg_lw_changed_r8(a, keep)
       real(kind=rb), intent(in), target :: a(..)
       logical, intent(in), optional :: keep
       integer(c_int) :: k
@@ -167,7 +189,64 @@
          error stop 1
       endif
       if (rrtmg_lw_hip_host_changed(c_loc(a), k) /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_changed')
-      end subroutine rrtmg_lw_changed
+      end subroutine rrtmg_lw_changed_r8
+
+!  The real(4) specifics: the same checks, 4 bytes per element.
+      subroutine rrtmg_lw_ini_r4(cpdair)
+      real(kind=r4), intent(in) :: cpdair
+      call rrtmg_lw_ini_r8(real(cpdair, rb))
+      end subroutine rrtmg_lw_ini_r4
+
+      subroutine rrtmg_lw_pin_r4(a, n)
+      real(kind=r4), intent(in), target :: a(..)
+      integer, intent(in), optional :: n
+      if (size(a) < 1) return
+      if (.not. is_contiguous(a)) then
+         write(*,*) 'rrtmg_lw_pin: the array is not contiguous (pass the whole array, not a section)'
+         error stop 1
+      endif
+      if (present(n)) then
+         if (n /= size(a)) then
+            write(*,*) 'rrtmg_lw_pin: n differs from the size of the array'
+            error stop 1
+         endif
+      endif
+      if (rrtmg_lw_hip_host_register(c_loc(a), int(size(a), c_long_long) * 4_c_long_long) /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_pin')
+      end subroutine rrtmg_lw_pin_r4
+
+      subroutine rrtmg_lw_unpin_r4(a)
+      real(kind=r4), intent(in), target :: a(..)
+      if (.not. is_contiguous(a)) then
+         write(*,*) 'rrtmg_lw_unpin: the array is not contiguous (pass the whole array that was pinned)'
+         error stop 1
+      endif
+      if (rrtmg_lw_hip_host_unregister(c_loc(a)) /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_unpin')
+      end subroutine rrtmg_lw_unpin_r4
+
+      subroutine rrtmg_lw_static_r4(a)
+      real(kind=r4), intent(in), target :: a(..)
+      if (size(a) < 1) return
+      if (.not. is_contiguous(a)) then
+         write(*,*) 'rrtmg_lw_static: the array is not contiguous (pass the whole array, not a section)'
+         error stop 1
+      endif
+      if (rrtmg_lw_hip_host_static(c_loc(a), int(size(a), c_long_long) * 4_c_long_long) /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_static')
+      end subroutine rrtmg_lw_static_r4
+
+      subroutine rrtmg_lw_changed_r4(a, keep)
+      real(kind=r4), intent(in), target :: a(..)
+      logical, intent(in), optional :: keep
+      integer(c_int) :: k
+      k = 1_c_int
+      if (present(keep)) then
+         if (.not. keep) k = 0_c_int
+      endif
+      if (.not. is_contiguous(a)) then
+         write(*,*) 'rrtmg_lw_changed: the array is not contiguous (pass the whole array that was declared)'
+         error stop 1
+      endif
+      if (rrtmg_lw_hip_host_changed(c_loc(a), k) /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_changed')
+      end subroutine rrtmg_lw_changed_r4
 
 !  Turns a non-zero status of the C ABI into the reference's behaviour: print the message and stop.
       subroutine rrtmg_lw_hip_abort(where)

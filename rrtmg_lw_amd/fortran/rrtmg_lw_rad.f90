@@ -16,6 +16,16 @@
 
       public :: rrtmg_lw
 
+!  rrtmg_lw is generic over the real kind: the reference's real(kind_rb) and real(4), for a host built with 4-byte reals (no -r8).  The
+!  real(4) specific forwards to rrtmg_lw_hip_run_mcica_r4 (include/rrtmg_lw_hip.h, "_r4"): the arrays cross as float32, the solver works
+!  in float64 on the widened values and the results are rounded.  The same rules: sections (1:ncol, 1:nlay[+1]), exactly sized contiguous
+!  duflx_dt / duflxc_dt in place, extent checks.  The spectral optionals are on the real(kind_rb) specific only.
+      integer, parameter, private :: r4 = c_float
+
+      interface rrtmg_lw
+         module procedure rrtmg_lw_r8, rrtmg_lw_r4
+      end interface
+
       interface
          function rrtmg_lw_hip_run_mcica(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, &
                h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, &
@@ -31,6 +41,20 @@
             type(c_ptr), value :: duflx_dt, duflxc_dt
             integer(c_int) :: rc
          end function rrtmg_lw_hip_run_mcica
+         function rrtmg_lw_hip_run_mcica_r4(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, &
+               h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, &
+               inflglw, iceflglw, liqflglw, cldfmcl, taucmcl, ciwpmcl, clwpmcl, reicmcl, relqmcl, tauaer, &
+               uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt) bind(C, name='rrtmg_lw_hip_run_mcica_r4') result(rc)
+            import :: c_int, c_float, c_ptr
+            integer(c_int), value :: ncol, nlay, idrv, inflglw, iceflglw, liqflglw
+            integer(c_int), intent(inout) :: icld
+            real(c_float), intent(in) :: play(*), plev(*), tlay(*), tlev(*), tsfc(*), h2ovmr(*), o3vmr(*), co2vmr(*)
+            real(c_float), intent(in) :: ch4vmr(*), n2ovmr(*), o2vmr(*), cfc11vmr(*), cfc12vmr(*), cfc22vmr(*), ccl4vmr(*)
+            real(c_float), intent(in) :: emis(*), cldfmcl(*), taucmcl(*), ciwpmcl(*), clwpmcl(*), reicmcl(*), relqmcl(*), tauaer(*)
+            real(c_float), intent(out) :: uflx(*), dflx(*), hr(*), uflxc(*), dflxc(*), hrc(*)
+            type(c_ptr), value :: duflx_dt, duflxc_dt
+            integer(c_int) :: rc
+         end function rrtmg_lw_hip_run_mcica_r4
          function rrtmg_lw_hip_run_mcica_spectral(ncol, nlay, icld, idrv, play, plev, tlay, tlev, tsfc, &
                h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, &
                inflglw, iceflglw, liqflglw, cldfmcl, taucmcl, ciwpmcl, clwpmcl, reicmcl, relqmcl, tauaer, &
@@ -50,7 +74,7 @@
 
       contains
 
-      subroutine rrtmg_lw &
+      subroutine rrtmg_lw_r8 &
             (ncol    ,nlay    ,icld    ,idrv    , &
              play    ,plev    ,tlay    ,tlev    ,tsfc    , &
              h2ovmr  ,o3vmr   ,co2vmr  ,ch4vmr  ,n2ovmr  ,o2vmr , &
@@ -190,7 +214,104 @@
       if (allocated(s3)) uflxcs(1:ncol, 1:nlay+1, 1:16) = s3
       if (allocated(s4)) dflxcs(1:ncol, 1:nlay+1, 1:16) = s4
 
-      end subroutine rrtmg_lw
+      end subroutine rrtmg_lw_r8
+
+      ! the real(4) specific: the same body on float arrays, without the spectral optionals
+      subroutine rrtmg_lw_r4 &
+            (ncol    ,nlay    ,icld    ,idrv    , &
+             play    ,plev    ,tlay    ,tlev    ,tsfc    , &
+             h2ovmr  ,o3vmr   ,co2vmr  ,ch4vmr  ,n2ovmr  ,o2vmr , &
+             cfc11vmr,cfc12vmr,cfc22vmr,ccl4vmr ,emis    , &
+             inflglw ,iceflglw,liqflglw,cldfmcl , &
+             taucmcl ,ciwpmcl ,clwpmcl ,reicmcl ,relqmcl , &
+             tauaer  , &
+             uflx    ,dflx    ,hr      ,uflxc   ,dflxc,  hrc, &
+             duflx_dt,duflxc_dt)
+
+      integer(kind=im), intent(in) :: ncol            ! Number of horizontal columns
+      integer(kind=im), intent(in) :: nlay            ! Number of model layers
+      integer(kind=im), intent(inout) :: icld         ! Cloud overlap method
+      integer(kind=im), intent(in) :: idrv            ! Flag for calculation of dFdT
+      real(kind=r4), intent(in) :: play(:,:)          ! Layer pressures (hPa, mb)           (ncol,nlay)
+      real(kind=r4), intent(in) :: plev(:,:)          ! Interface pressures (hPa, mb)       (ncol,nlay+1)
+      real(kind=r4), intent(in) :: tlay(:,:)          ! Layer temperatures (K)
+      real(kind=r4), intent(in) :: tlev(:,:)          ! Interface temperatures (K)
+      real(kind=r4), intent(in) :: tsfc(:)            ! Surface temperature (K)
+      real(kind=r4), intent(in) :: h2ovmr(:,:), o3vmr(:,:), co2vmr(:,:), ch4vmr(:,:), n2ovmr(:,:), o2vmr(:,:)
+      real(kind=r4), intent(in) :: cfc11vmr(:,:), cfc12vmr(:,:), cfc22vmr(:,:), ccl4vmr(:,:)
+      real(kind=r4), intent(in) :: emis(:,:)          ! Surface emissivity                  (ncol,nbndlw)
+      integer(kind=im), intent(in) :: inflglw, iceflglw, liqflglw
+      real(kind=r4), intent(in) :: cldfmcl(:,:,:)     ! Cloud fraction [mcica]              (ngptlw,ncol,nlay)
+      real(kind=r4), intent(in) :: ciwpmcl(:,:,:), clwpmcl(:,:,:)
+      real(kind=r4), intent(in) :: reicmcl(:,:), relqmcl(:,:)      !                        (ncol,nlay)
+      real(kind=r4), intent(in) :: taucmcl(:,:,:)     ! In-cloud optical depth [mcica]      (ngptlw,ncol,nlay)
+      real(kind=r4), intent(in) :: tauaer(:,:,:)      ! Aerosol optical depth               (ncol,nlay,nbndlw)
+      real(kind=r4), intent(out) :: uflx(:,:), dflx(:,:), hr(:,:), uflxc(:,:), dflxc(:,:), hrc(:,:)
+      real(kind=r4), intent(out), optional, target :: duflx_dt(:,:), duflxc_dt(:,:)
+
+      integer(c_int) :: rc, icld_c
+      integer :: ng                                   ! ngptlw of the linked library (140, or 256)
+      real(c_float), allocatable, target :: d1(:,:), d2(:,:)
+      type(c_ptr) :: p1, p2
+      logical :: inplace
+
+      icld_c = int(icld, c_int)
+      ng = int(rrtmg_lw_hip_gpoints())
+      p1 = c_null_ptr
+      p2 = c_null_ptr
+      inplace = .false.
+      if (idrv == 1) then
+         if (.not. (present(duflx_dt) .and. present(duflxc_dt))) then
+            write(*,*) 'rrtmg_lw: idrv = 1 requires duflx_dt and duflxc_dt'
+            error stop 1
+         endif
+         ! exactly sized, contiguous actuals go across in place like every other array (and stay page-locked if the host pinned them:
+         ! rrtmg_lw_pin); an optional dummy cannot be passed as a section, so anything else goes through a temporary
+         inplace = size(duflx_dt,1) == ncol .and. size(duflx_dt,2) == nlay+1 .and. is_contiguous(duflx_dt) .and. &
+                   size(duflxc_dt,1) == ncol .and. size(duflxc_dt,2) == nlay+1 .and. is_contiguous(duflxc_dt)
+         if (inplace) then
+            p1 = c_loc(duflx_dt)
+            p2 = c_loc(duflxc_dt)
+         else
+            if (size(duflx_dt,1) < ncol .or. size(duflx_dt,2) < nlay+1 .or. size(duflxc_dt,1) < ncol .or. size(duflxc_dt,2) < nlay+1) then
+               write(*,*) 'rrtmg_lw: duflx_dt / duflxc_dt smaller than (ncol, nlay+1)'
+               error stop 1
+            endif
+            allocate(d1(ncol, nlay+1), d2(ncol, nlay+1))
+            p1 = c_loc(d1)
+            p2 = c_loc(d2)
+         endif
+      endif
+      ! sections (1:ncol, 1:nlay[+1]) as the reference's loops touch them (src/rrtmg_lw_rad.f90:785-924): oversized
+      ! (pcols > ncol) or strided actuals are packed / unpacked by the compiler, exactly-sized ones are passed in place
+      call check_extent('play', size(play,1), size(play,2), ncol, nlay)
+      call check_extent('plev', size(plev,1), size(plev,2), ncol, nlay+1)
+      call check_extent('tauaer', size(tauaer,1), size(tauaer,2), ncol, nlay)
+      call check_extent('cldfmcl', size(cldfmcl,2), size(cldfmcl,3), ncol, nlay)
+      if (size(cldfmcl,1) < ng) then
+         write(*,'(a,i0,a,i0,a)') 'rrtmg_lw: cldfmcl holds ', size(cldfmcl,1), ' sub-columns, the linked library has ', ng, ' g-points'
+         error stop 1
+      endif
+      call check_extent('uflx', size(uflx,1), size(uflx,2), ncol, nlay+1)
+      call check_extent('hr', size(hr,1), size(hr,2), ncol, nlay)
+      rc = rrtmg_lw_hip_run_mcica_r4(int(ncol, c_int), int(nlay, c_int), icld_c, int(idrv, c_int), &
+            play(1:ncol,1:nlay), plev(1:ncol,1:nlay+1), tlay(1:ncol,1:nlay), tlev(1:ncol,1:nlay+1), tsfc(1:ncol), &
+            h2ovmr(1:ncol,1:nlay), o3vmr(1:ncol,1:nlay), co2vmr(1:ncol,1:nlay), ch4vmr(1:ncol,1:nlay), &
+            n2ovmr(1:ncol,1:nlay), o2vmr(1:ncol,1:nlay), cfc11vmr(1:ncol,1:nlay), cfc12vmr(1:ncol,1:nlay), &
+            cfc22vmr(1:ncol,1:nlay), ccl4vmr(1:ncol,1:nlay), emis(1:ncol,1:16), &
+            int(inflglw, c_int), int(iceflglw, c_int), int(liqflglw, c_int), &
+            cldfmcl(1:ng,1:ncol,1:nlay), taucmcl(1:ng,1:ncol,1:nlay), ciwpmcl(1:ng,1:ncol,1:nlay), &
+            clwpmcl(1:ng,1:ncol,1:nlay), reicmcl(1:ncol,1:nlay), relqmcl(1:ncol,1:nlay), tauaer(1:ncol,1:nlay,1:16), &
+            uflx(1:ncol,1:nlay+1), dflx(1:ncol,1:nlay+1), hr(1:ncol,1:nlay), &
+            uflxc(1:ncol,1:nlay+1), dflxc(1:ncol,1:nlay+1), hrc(1:ncol,1:nlay), p1, p2)
+      if (rc /= 0) call rrtmg_lw_hip_abort('rrtmg_lw')
+      icld = int(icld_c, im)
+      if (idrv == 1 .and. .not. inplace) then
+         duflx_dt(1:ncol, 1:nlay+1) = d1
+         duflxc_dt(1:ncol, 1:nlay+1) = d2
+      endif
+
+      end subroutine rrtmg_lw_r4
 
       ! a spectral output (ncol,nlay+1,16): exactly sized, contiguous actuals go across in place (like duflx_dt);
       ! larger or strided ones through the temporary t, copied back after the call

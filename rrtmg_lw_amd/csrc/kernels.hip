@@ -592,7 +592,7 @@ __global__ __launch_bounds__(256) void k_cloudlay(DevTables T, Workspace W, GcmI
         else if (liqflag == 0) { liqmode = 0; liq_single = T.absliq0; liqind = 0; if (iceind == 1) iceind = 2; }
         else if (liqflag == 1) {
             const double radliq = (GCM ? g.reliq : c.rel)[gi];
-            if (radliq < 2.5 || radliq > 60.) err = E_LIQ_BOUNDS;
+            if ((radliq < 2.5 || radliq > 60.) && !err) err = E_LIQ_BOUNDS;      // (both sizes out: the reference stops at the ice check, :212-244)
             index_l = (int)(radliq - 1.5);
             if (index_l == 0) index_l = 1;
             if (index_l == 58) index_l = 57;
@@ -2227,10 +2227,10 @@ __global__ __launch_bounds__(256) void k_cloudmc(DevTables T, Workspace W, McIn 
                     if (inflag == 1) err = E_MC_INFLAG1;
                     else if (inflag == 2) {
                         double a_i = 0.0, a_l = 0.0;
-                        if (mciwp != 0.0 && iceflag >= 0 && iceflag <= 3) { a_i = ai; if (ice_err) err = ice_err; }
+                        if (mciwp != 0.0 && iceflag >= 0 && iceflag <= 3) { a_i = ai; if (ice_err && !err) err = ice_err; }      // the first stop in the reference's order
                         if (mclwp != 0.0) {
                             if (liqflag == 0) a_l = al;
-                            else if (liqflag == 1) { a_l = al; if (liq_err) err = liq_err; }
+                            else if (liqflag == 1) { a_l = al; if (liq_err && !err) err = liq_err; }       // (ice is checked first: cldprmc :204-254)
                         }
                         t = mciwp * a_i + mclwp * a_l;
                     }
@@ -2280,10 +2280,10 @@ __global__ __launch_bounds__(256) void k_cloudmc(DevTables T, Workspace W, McIn 
                     if (inflag == 1) err = E_MC_INFLAG1;                                     // :190-191
                     else if (inflag == 2) {
                         double a_i = 0.0, a_l = 0.0;
-                        if (ci[j] != 0.0 && iceflag >= 0 && iceflag <= 3) { a_i = ai; if (ice_err) err = ice_err; }
+                        if (ci[j] != 0.0 && iceflag >= 0 && iceflag <= 3) { a_i = ai; if (ice_err && !err) err = ice_err; }      // the first stop in the reference's order
                         if (cw[j] != 0.0) {
                             if (liqflag == 0) a_l = al;
-                            else if (liqflag == 1) { a_l = al; if (liq_err) err = liq_err; }
+                            else if (liqflag == 1) { a_l = al; if (liq_err && !err) err = liq_err; }       // (ice is checked first: cldprmc :204-254)
                         }
                         t = ci[j] * a_i + cw[j] * a_l;                                          // :267-268
                     }

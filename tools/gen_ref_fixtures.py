@@ -128,7 +128,29 @@ def gasstate():
     print("wrote the gas-state fixture to", G)
 
 
+def cloudstate():
+    """ref_cloudstate_L40.npz: the reference on every 31st column of every call of the designed cloud states' families A and B
+    (tests/cloud_states.py) - total-sky fluxes and heating rates of the GCM entry with maximum-random overlap, outputs only."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cloud_states as cs
+    from test_cloud_state_coverage import FIXTURE, FIXTURE_KEYS, _all_calls, fixture_columns
+    calls = _all_calls(cs.family_a(), cs.family_b())
+    ref = Reference("nomcica")
+    labels, outs = [], {k: [] for k in FIXTURE_KEYS}
+    for key, cols in fixture_columns(calls):
+        sub = cs.take(calls[key], cols)
+        o = ref.rrtmg_lw(sub["ncol"], sub["nlay"], 2, 0, sub)
+        assert all(np.isfinite(o[k]).all() for k in FIXTURE_KEYS)
+        labels += sub["labels"]
+        for k in FIXTURE_KEYS:
+            outs[k].append(o[k])
+    np.savez_compressed(FIXTURE, nlay=cs.NLAY, seed=cs.SEED, icld=2, labels=np.array(labels), **{k: np.concatenate(v) for k, v in outs.items()})
+    print("wrote the cloud-state fixture to", G, "-", len(labels), "columns,", os.path.getsize(FIXTURE), "bytes")
+
+
 def main():
+    if "--cloudstate" in sys.argv:  # only the designed cloud states' fixture
+        return cloudstate()
     if "--gasstate" in sys.argv:    # only the designed gas states' fixture
         return gasstate()
     if "--rrtatm" in sys.argv:      # only the IATM = 1 layering fixtures

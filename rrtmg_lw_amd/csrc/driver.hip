@@ -6,6 +6,7 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstdint>
 #include <cstdarg>
@@ -23,6 +24,7 @@
 #include "kernels.hip"
 #include "mtjump.hpp"
 #include "hostrows.hpp"
+#include "owned.hpp"
 
 namespace {
 
@@ -38,7 +40,32 @@ const int HOST_BATCH = []() { const char *e = getenv("RRTMG_LW_HOST_BATCH"); con
 // showed 11 ms of overlap between 44 ms of kernels and 52 ms of copies.
 constexpr int HOST_SETS = 4;
 
-struct KissTable { unsigned long long stride = 0; long long seed = -1; KissJump host[KJ_NGROUP + 1]; KissJump *dev = nullptr; };
+// ---- who owns what ------------------------------------------------------------------------------------------------------------------
+// Every GPU resource of the driver is held by an owner (owned.hpp) over one of these traits; the release calls appear here and nowhere
+// else in this file.  release / acquire hand the hipError_t back as an int: a growth site reports it through fail() (grow, drop), a
+// destructor or a move-assignment - finalize_state, a re-initialisation - ignores it.
+struct DevMemTraits {       // (an earlier launch may still use the buffer: the device is idle before it goes)
+    using handle = void *;
+    static int acquire(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static int release(void *p) { const hipError_t s = hipDeviceSynchronize(), f = hipFree(p); return (int)(s != hipSuccess ? s : f); }
+};
+struct PinnedTraits {
+    using handle = void *;
+    static int acquire(void **p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static int release(void *p) { return (int)hipHostFree(p); }
+};
+struct StreamTraits { using handle = hipStream_t; static int release(hipStream_t s) { return (int)hipStreamDestroy(s); } };
+struct EventTraits { using handle = hipEvent_t; static int release(hipEvent_t e) { return (int)hipEventDestroy(e); } };
+struct GraphTraits { using handle = hipGraph_t; static int release(hipGraph_t g) { return (int)hipGraphDestroy(g); } };
+struct GraphExecTraits { using handle = hipGraphExec_t; static int release(hipGraphExec_t g) { return (int)hipGraphExecDestroy(g); } };
+using DevBuf = owned::GrowBuf<DevMemTraits>;
+using PinnedBuf = owned::GrowBuf<PinnedTraits>;
+using Stream = owned::Owned<StreamTraits>;
+using Event = owned::Owned<EventTraits>;
+using Graph = owned::Owned<GraphTraits>;
+using GraphExec = owned::Owned<GraphExecTraits>;
+
+struct KissTable { unsigned long long stride = 0; long long seed = -1; KissJump host[KJ_NGROUP + 1]; DevBuf dev; };
 
 // Columns per internal batch when the caller has not chosen (rrtmg_lw_hip_set_batch(0) comes back to this): 262 144 at up to 96 layers,
 // the next lower power of two of 262 144 x 72 / nlay above (131 072 at 137 layers) - the workspace grows with the layers, the step
@@ -51,95 +78,92 @@ struct State {
     int device = -1;
     HostTables H;
     DevTables D;
-    double *d_ktab = nullptr, *d_stat = nullptr;
-    // workspace
+    DevBuf d_ktab, d_stat;
+    // workspace: the allocation, the view of it the kernels receive, and the call shapes it was built for (ensure_workspace) - value-reset
+    // wherever the allocation goes
     Workspace W{};
-    void *ws_base = nullptr;
-    size_t ws_bytes = 0;
-    int ws_nlay = 0, ws_ncolb = 0;
-    bool ws_cloud = false, ws_mc = false, ws_gdp = false, ws_efcl = false, ws_ovl = false;
+    DevBuf ws_buf;
+    struct WsShape {
+        int nlay = 0, ncolb = 0;
+        bool cloud = false, mc = false, gdp = false, efcl = false, ovl = false;
+        bool two_scr = false;        // it holds the second scratch set that split_sweep needs
+        int groups = 0;
+        size_t slabcols = 0;         // capacity of each partial slab array (gdn1 ..) in columns x slabs: `groups` wide slabs, or - a small batch whose
+                                     // bands leave a slab each (split sweeps) - sixteen narrow ones
+    } ws;
     // the gas-optics entries' own small workspace (k_colprep's per-column terms, k_optics' wide-window list): none of the solver's
     // codes, partials or cloud arrays
-    void *opt_base = nullptr;
-    size_t opt_bytes = 0;
+    DevBuf opt_buf;
     int opt_nlay = 0, opt_ncolb = 0;
     double *opt_percol = nullptr;
     int *opt_laytrop = nullptr, *opt_wide = nullptr;
-    int ws_groups = 0;
-    size_t ws_slabcols = 0;     // capacity of each partial slab array (gdn1 ..) in columns x slabs: ws_groups wide slabs, or - a small batch whose bands
-                                 // leave a slab each (split sweeps) - sixteen narrow ones
-    int *d_err = nullptr;
+    DevBuf d_err;
     // per-column / cloud-property arrays exist twice: k_colprep + k_cloudscan / k_cloudlay of batch i+1 run on `aux` while batch i is in k_layer/k_sweep
     struct PrepSet { double *percol; int *laytrop, *ncbands; double *odcld, *efcl; int *cflag; int *btop, *order, *hgrp, *hblk, *bbot, *hbot; double2 *ovl; int *perm, *wsort; double *tlayc, *tlevc, *cldfc; int *wide; } prep[2] = {};
     // the per-cell scratch written by k_layer and read by the sweeps exists twice as well: sweeps / k_flux of batch i (HBM-bound)
     // run on `sw` while k_layer of batch i+1 (latency-bound) runs on the caller's stream
     struct ScrSet { unsigned *scr[NSCR]; unsigned *fw; } scrset[2] = {};
-    hipStream_t aux = nullptr;
+    Stream aux;
     // streams of the sweep launches: `main` (the split pipeline's sweep stream) and q[0..2], on which the launches of the 3-, 2- and 1-quad
     // bands run beside the 4-quad launch.  Set 0 may use the whole chip; set 1 exists with a CU partition (rrtmg_lw_hip_set_cu_partition)
     // and is confined to the sweeps' share of the CUs.
-    struct SweepSet { hipStream_t main = nullptr, q[3] = {nullptr, nullptr, nullptr}; hipEvent_t go = nullptr, done[3] = {nullptr, nullptr, nullptr}; } swset[2];
+    struct SweepSet { Stream main, q[3]; Event go, done[3]; } swset[2];
     // k_layer's streams of the partitioned pipeline: lay_u the whole chip (first batch of a call: nothing runs beside it), lay_m its share
-    hipStream_t lay_u = nullptr, lay_m = nullptr;
+    Stream lay_u, lay_m;
     int cu_layer = 0;            // CUs of k_layer's share (0: no partition), set by rrtmg_lw_hip_set_cu_partition
     int cu_total = 0;
     bool sweep_fanout = true;
-    hipEvent_t ev_last = nullptr;           // end of the previous device-entry call (calls on different streams share the workspace)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;      // run_prep: k_colprep beside k_cloudscan in a single-batch call
+    Event ev_last;                          // end of the previous device-entry call (calls on different streams share the workspace)
+    Event ev_fork, ev_join;                               // run_prep: k_colprep beside k_cloudscan in a single-batch call
     bool ev_last_valid = false;
-    hipEvent_t ev_in = nullptr, ev_ready[2] = {nullptr, nullptr}, ev_layer[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
+    Event ev_in, ev_ready[2], ev_layer[2], ev_done[2];
     // McICA sub-column masks of all columns of the current call
-    unsigned *mask = nullptr;
-    size_t mask_bytes = 0;
-    double *d_rnd = nullptr;   // one slab of Mersenne-Twister deviates (irng = 1)
-    size_t rnd_bytes = 0;
+    DevBuf mask;
+    DevBuf d_rnd;              // one slab of Mersenne-Twister deviates (irng = 1)
     bool batch_set = false; // rrtmg_lw_hip_set_batch has named a size (otherwise: auto_batch(nlay))
     int batch = DEFAULT_BATCH;     // columns per internal batch: 0.06-0.16 MB of workspace per column at 72 layers by call shape (38 GB of the 288 for the benchmark's); measured per 1e6 cloudy columns (end of round 2): 131072: 63.1 ms, 262144: 62.7, 524288: 61.7-62.3, 1048576: 61.2 - within the run-to-run spread, not worth the memory
     bool split_sweep = false;    // run the sweeps / k_flux of batch i concurrently with k_layer of batch i+1 (device entries).  Off by default: a sweep
                                  // workgroup owns a CU (transmittance table in LDS), so the two do not share a CU (measured: 1-2 % gain for twice the code scratch)
     bool sweep_attrs = false;    // the sweeps' dynamic-LDS limit has been raised on this device
     bool n1 = false;             // rrtmg_lw_hip_set_n1_prototype(1): cloud-free calls take the north-star-mapping prototype k_n1 (measurement only)
-    bool ws_two_scr = false;     // the workspace holds the second scratch set that split_sweep needs
     // host-entry staging
-    void *stage_base = nullptr;
-    size_t stage_bytes = 0;
+    DevBuf stage_buf;
     // the *_as entries' staging: a batch's arrays in float64 reference form; play, cldfr, alpha of a whole fused McICA call for the generator
-    void *form_base = nullptr, *form_gen = nullptr;
-    size_t form_bytes = 0, form_gen_bytes = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t cp_in = nullptr, cp_out = nullptr;      // host-pointer entries: H2D and D2H copy streams
-    double *h_tot = nullptr;                            // pinned host scratch of the non-McICA host entry: tauctot of HOST_SETS column batches
-    size_t h_tot_doubles = 0;
+    DevBuf form_buf, form_gen;
+    Stream stream;
+    Stream cp_in, cp_out;                               // host-pointer entries: H2D and D2H copy streams
+    PinnedBuf h_tot;                                    // pinned host scratch of the non-McICA host entry: tauctot of HOST_SETS column batches
     // pinned host staging of the host-pointer entries, HOST_SETS sets like the device staging: `in` = the rows of the caller's PAGEABLE input
     // arrays that travel (packed by the host threads, then one DMA per run of rows), `out` = the pageable output arrays' rows (DMA, then
     // unpacked by the host threads), `fill` = the table of k_fill_rows (rows that do not travel); the *_r4 entries: `widen` / `narrow` =
     // the tables of k_widen_rows (float32 input rows that have landed) and k_narrow_rows (the active output rows)
-    struct HostSet {
-        char *in = nullptr; size_t in_cap = 0; char *out = nullptr; size_t out_cap = 0; char *fill = nullptr; size_t fill_cap = 0;
-        char *widen = nullptr; size_t widen_cap = 0; char *narrow = nullptr; size_t narrow_cap = 0;
-    } hset[HOST_SETS];
-    hipEvent_t ev_h2d[HOST_SETS] = {}, ev_cmp[HOST_SETS] = {}, ev_d2h[HOST_SETS] = {};
+    struct HostSet { PinnedBuf in, out, fill, widen, narrow; } hset[HOST_SETS];
+    Event ev_h2d[HOST_SETS], ev_cmp[HOST_SETS], ev_d2h[HOST_SETS];
     KissTable kiss;             // the kissvec generator's jump table of the last (draws per sub-column, permuteseed) pair, on this device
     std::string err;
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg)
     bool profile = false;
     // small device-resident calls replayed as ONE graph (run_pipelined): what a call's launches depend on -> the instantiated graph
-    struct GraphEnt { std::vector<unsigned char> key; hipGraphExec_t exec = nullptr; int seen = 0; bool failed = false; unsigned long long used = 0; };
+    struct GraphEnt { std::vector<unsigned char> key; GraphExec exec; int seen = 0; bool failed = false; unsigned long long used = 0; };
     std::vector<GraphEnt> graphs;
     unsigned long long graph_clock = 0;
-    hipStream_t cap = nullptr;         // the stream the launches of such a call are captured on (the caller's may be the null stream)
+    Stream cap;                        // the stream the launches of such a call are captured on (the caller's may be the null stream)
     long long graph_replays = 0, graph_captures = 0;
     unsigned long long init_gen = 0;   // which initialisation (init_state) the state's tables come from: part of every graph's key
-    struct ProfRec { const char *name; hipEvent_t a, b; };
+    struct ProfRec { const char *name; Event a, b; };
     std::vector<ProfRec> prof;
-    std::vector<hipEvent_t> evpool;
+    std::vector<Event> evpool;          // events of finished profile records, handed out again by get_event()
 };
 // One State per device the library drives (rrtmg_lw_hip_init: one; rrtmg_lw_hip_init_devices: several GPUs from one process, SURVEY.md 8b
 // `ndev`).  Every function below works on the calling thread's CURRENT state `G`: state 0 for every entry, and inside the host-pointer
 // entries each worker thread of the fan-out (nomcica_host) takes the state of the device it feeds.  The same physical device may appear
 // in several states ("virtual devices": separate workspaces, streams and table copies - how the fan-out is tested on a one-GPU box).
+// The states, the queue (Q) and the generator's caches (g_mt) live in owned::NoDestroy storage: a process that ends without
+// rrtmg_lw_hip_finalize - Python tests and host models do - must not call into the HIP runtime from static destructors, after the runtime
+// may have been torn down.  finalize_state is the only path that releases them.
 constexpr int MAXDEV = 16;
-State g_states[MAXDEV];
+owned::NoDestroy<std::array<State, MAXDEV>> g_states_store;
+std::array<State, MAXDEV> &g_states = g_states_store.get();
 int g_ndev = 1;
 thread_local State *g_cur = &g_states[0];
 #define G (*g_cur)
@@ -245,9 +269,10 @@ struct ChunkQueue {
     int nlay = 0, icld = 0, idrv = 0, inflg = 0, iceflg = 0, liqflg = 0;
     long long ncol = 0;
     std::vector<QueuedChunk> chunks;
-    double *pinned = nullptr;
-    size_t pinned_doubles = 0;
-} Q;
+    PinnedBuf pinned;
+};
+owned::NoDestroy<ChunkQueue> g_queue_store;       // (never destroyed: see g_states)
+ChunkQueue &Q = g_queue_store.get();
 
 // The HIP current device is per host thread: an entry called from another thread (an OpenMP host model, a Python worker) must
 // select the device the workspace lives on, and leaves the caller's device selection as it found it.
@@ -322,6 +347,21 @@ int fail(int code, const char *fmt, ...)
         if (e_ != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// an owner's growth or release on a path that reports: the traits' code (a hipError_t) becomes the call's error
+template <class Buf>
+int grow(Buf &b, size_t need, size_t want, const char *what)
+{
+    if (const int e = b.reserve(need, want)) return fail(RRTMG_LW_HIP_EHIP, "%s: releasing the old buffer or allocating %zu bytes failed: %s", what, want, hipGetErrorString((hipError_t)e));
+    return 0;
+}
+template <class Own>
+int drop(Own &o, const char *what)
+{
+    if (const int e = o.reset()) return fail(RRTMG_LW_HIP_EHIP, "%s: release failed: %s", what, hipGetErrorString((hipError_t)e));
+    return 0;
+}
+int make_event(Event &e) { HIP_TRY(hipEventCreateWithFlags(e.slot(), hipEventDisableTiming)); return 0; }
+
 const char *physics_message(int code)
 {
     switch (code) {   // texts of the reference's `stop` statements, src/rrtmg_lw_cldprop.f90:212,217,228,244,272
@@ -372,11 +412,11 @@ int balanced_batch(int ncol, int cap)
     return std::min(nb, cap);
 }
 
-hipEvent_t get_event()
+Event get_event()
 {
-    if (!G.evpool.empty()) { hipEvent_t e = G.evpool.back(); G.evpool.pop_back(); return e; }
-    hipEvent_t e;
-    (void)hipEventCreate(&e);
+    Event e;
+    if (!G.evpool.empty()) { e = std::move(G.evpool.back()); G.evpool.pop_back(); }
+    else (void)hipEventCreate(e.slot());
     return e;
 }
 
@@ -385,10 +425,10 @@ hipEvent_t get_event()
     do {                                                                                         \
         if (G.profile) {                                                                         \
             State::ProfRec r_{NAME, get_event(), get_event()};                                   \
-            (void)hipEventRecord(r_.a, STREAM);                                                  \
+            (void)hipEventRecord(r_.a.get(), STREAM);                                            \
             hipLaunchKernelGGL(KERNEL, GRID, BLOCKDIM, 0, STREAM, __VA_ARGS__);                  \
-            (void)hipEventRecord(r_.b, STREAM);                                                  \
-            G.prof.push_back(r_);                                                                \
+            (void)hipEventRecord(r_.b.get(), STREAM);                                            \
+            G.prof.push_back(std::move(r_));                                                     \
         } else {                                                                                 \
             hipLaunchKernelGGL(KERNEL, GRID, BLOCKDIM, 0, STREAM, __VA_ARGS__);                  \
         }                                                                                        \
@@ -399,10 +439,10 @@ hipEvent_t get_event()
     do {                                                                                         \
         if (G.profile) {                                                                         \
             State::ProfRec r_{NAME, get_event(), get_event()};                                   \
-            (void)hipEventRecord(r_.a, STREAM);                                                  \
+            (void)hipEventRecord(r_.a.get(), STREAM);                                            \
             hipLaunchKernelGGL(KERNEL, GRID, BLOCKDIM, LDS, STREAM, __VA_ARGS__);                \
-            (void)hipEventRecord(r_.b, STREAM);                                                  \
-            G.prof.push_back(r_);                                                                \
+            (void)hipEventRecord(r_.b.get(), STREAM);                                            \
+            G.prof.push_back(std::move(r_));                                                     \
         } else {                                                                                 \
             hipLaunchKernelGGL(KERNEL, GRID, BLOCKDIM, LDS, STREAM, __VA_ARGS__);                \
         }                                                                                        \
@@ -559,15 +599,16 @@ int ensure_workspace(int nlay, int ncolb, bool cloud, bool mc = false, int idrv 
     const bool gdp = idrv == 1, efcl = cloud && (mode < 0 || mode == 1 || mode == 3), ovl = cloud && (mode < 0 || mode == 2);
     // (a batch small enough for the split sweeps - one band per workgroup, a slab per band - needs room for sixteen slabs of its own width)
     const size_t split_cols = ncolb <= g_split_max ? (size_t)NBND * align_up((size_t)ncolb, 64) : 0;
-    if (G.ws_base && G.ws_nlay == nlay && G.ws_ncolb >= ncolb && (G.ws_cloud || !cloud) && (G.ws_mc || !mc) && (G.ws_two_scr || !G.split_sweep) &&
-        G.ws_groups >= groups && G.ws_slabcols >= split_cols && (G.ws_gdp || !gdp) && (G.ws_efcl || !efcl) && (G.ws_ovl || !ovl)) return 0;
-    if (G.ws_base) { HIP_TRY(hipDeviceSynchronize()); graphs_clear(); HIP_TRY(hipFree(G.ws_base)); G.ws_base = nullptr; }
-    const bool same = G.ws_nlay == nlay;
-    ncolb = std::max(ncolb, same ? G.ws_ncolb : 0);
-    cloud = cloud || G.ws_cloud || mc;
-    mc = mc || G.ws_mc;
-    const int ng = std::max(groups, G.ws_groups);
-    const bool want_gdp = gdp || G.ws_gdp, want_efcl = efcl || G.ws_efcl, want_ovl = ovl || G.ws_ovl;
+    const State::WsShape &have = G.ws;         // (stays until the new workspace stands: what earlier call shapes needed is merged into it)
+    if (G.ws_buf && have.nlay == nlay && have.ncolb >= ncolb && (have.cloud || !cloud) && (have.mc || !mc) && (have.two_scr || !G.split_sweep) &&
+        have.groups >= groups && have.slabcols >= split_cols && (have.gdp || !gdp) && (have.efcl || !efcl) && (have.ovl || !ovl)) return 0;
+    if (G.ws_buf) { HIP_TRY(hipDeviceSynchronize()); graphs_clear(); if (int rc = drop(G.ws_buf, "workspace")) return rc; }
+    const bool same = have.nlay == nlay;
+    ncolb = std::max(ncolb, same ? have.ncolb : 0);
+    cloud = cloud || have.cloud || mc;
+    mc = mc || have.mc;
+    const int ng = std::max(groups, have.groups);
+    const bool want_gdp = gdp || have.gdp, want_efcl = efcl || have.efcl, want_ovl = ovl || have.ovl;
     const size_t n = (size_t)ncolb, L = (size_t)nlay;
     const size_t slabcols = std::max((size_t)ng * n, (size_t)NBND * align_up(std::min(n, (size_t)std::max(g_split_max, 0)), 64));
     struct Item { void **p; size_t bytes; };
@@ -625,14 +666,14 @@ int ensure_workspace(int nlay, int ncolb, bool cloud, bool mc = false, int idrv 
     }
     size_t total = 0;
     for (auto &it : items) total += align_up(it.bytes, 256);
-    HIP_TRY(hipMalloc(&G.ws_base, total));
+    if (int rc = grow(G.ws_buf, total, total, "workspace")) return rc;
     size_t off = 0;
-    for (auto &it : items) { *it.p = (char *)G.ws_base + off; off += align_up(it.bytes, 256); }
+    for (auto &it : items) { *it.p = G.ws_buf.as<char>() + off; off += align_up(it.bytes, 256); }
     for (auto &ps : G.prep) HIP_TRY(hipMemset(ps.wide, 0, 8));         // the count of k_layer's wide-window list (kernels.hip: k_layer)
     W.ncolb = ncolb;
     W.pcb = ncolb;
     W.nlay = nlay;
-    W.err = G.d_err;
+    W.err = G.d_err.as<int>();
     for (int a = 0; a < NSCR; a++) W.scr[a] = G.scrset[0].scr[a];
     W.fw = G.scrset[0].fw;
     {   // G.W itself carries prep set 0 and scratch set 0
@@ -641,25 +682,14 @@ int ensure_workspace(int nlay, int ncolb, bool cloud, bool mc = false, int idrv 
         W.odcld = ps.odcld; W.efcl = ps.efcl; W.ovl = ps.ovl;
         W.btop = ps.btop; W.order = ps.order; W.hgrp = ps.hgrp; W.hblk = ps.hblk; W.bbot = ps.bbot; W.hbot = ps.hbot;
     }
-    G.ws_bytes = total;
-    G.ws_nlay = nlay;
-    G.ws_ncolb = ncolb;
-    G.ws_cloud = cloud;
-    G.ws_mc = mc;
-    G.ws_two_scr = two_scr;
-    G.ws_groups = ng; G.ws_slabcols = slabcols; G.ws_gdp = want_gdp; G.ws_efcl = want_efcl; G.ws_ovl = want_ovl;
+    G.ws = State::WsShape{nlay, ncolb, cloud, mc, want_gdp, want_efcl, want_ovl, two_scr, ng, slabcols};
     return 0;
 }
 
 int ensure_mask(int nlay, size_t ncol)
 {
     const size_t bytes = (size_t)KJ_NWORD * nlay * ncol * sizeof(unsigned);
-    if (G.mask_bytes < bytes) {
-        if (G.mask) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(G.mask)); G.mask = nullptr; G.mask_bytes = 0; }
-        HIP_TRY(hipMalloc((void **)&G.mask, bytes));
-        G.mask_bytes = bytes;
-    }
-    return 0;
+    return grow(G.mask, bytes, bytes, "sub-column masks");
 }
 
 // Columns of a cloudy non-McICA batch are taken in the order k_colsort gives them (by cloud top within windows of 256: the sweeps decide
@@ -691,7 +721,7 @@ Workspace ws_for(int k, bool sorted)
     w.percol = ps.percol; w.laytrop = ps.laytrop; w.ncbands = ps.ncbands; w.cflag = ps.cflag;
     w.odcld = ps.odcld; w.efcl = ps.efcl; w.ovl = ps.ovl;
     w.btop = ps.btop; w.order = ps.order; w.hgrp = ps.hgrp; w.hblk = ps.hblk; w.bbot = ps.bbot; w.hbot = ps.hbot;
-    const State::ScrSet &ss = G.scrset[G.ws_two_scr ? k : 0];
+    const State::ScrSet &ss = G.scrset[G.ws.two_scr ? k : 0];
     for (int a = 0; a < NSCR; a++) w.scr[a] = ss.scr[a];
     w.fw = ss.fw;
     return w;
@@ -700,35 +730,28 @@ Workspace ws_for(int k, bool sorted)
 // A stream confined to the CUs [lo, hi) of the device's CU-mask order (hipExtStreamCreateWithCUMask; on a multi-XCD device consecutive
 // mask bits go round the XCDs, so a run of bits that is a multiple of 8 long takes the same number of CUs from every XCD), or - lo = hi -
 // an ordinary non-blocking stream.
-int make_stream(hipStream_t *st, int lo, int hi)
+int make_stream(Stream &st, int lo, int hi)
 {
-    if (hi <= lo) { HIP_TRY(hipStreamCreateWithFlags(st, hipStreamNonBlocking)); return 0; }
+    if (hi <= lo) { HIP_TRY(hipStreamCreateWithFlags(st.slot(), hipStreamNonBlocking)); return 0; }
     uint32_t mask[32] = {};
     const int nw = (G.cu_total + 31) / 32;
     for (int b = lo; b < hi && b < 1024; b++) mask[b >> 5] |= 1u << (b & 31);
-    HIP_TRY(hipExtStreamCreateWithCUMask(st, (uint32_t)nw, mask));
+    HIP_TRY(hipExtStreamCreateWithCUMask(st.slot(), (uint32_t)nw, mask));
     return 0;
 }
 int ensure_sweep_set(int k)
 {
-    State::SweepSet &SS = G.swset[k];
-    if (SS.q[0]) return 0;
+    if (G.swset[k].q[0]) return 0;
     const int lo = k == 1 ? G.cu_layer : 0, hi = k == 1 ? G.cu_total : 0;
-    if (!SS.main) { if (int rc = make_stream(&SS.main, lo, hi)) return rc; }
+    State::SweepSet SS;         // (built here and moved in whole: a failure part-way leaves the state's set as it was)
+    if (int rc = make_stream(SS.main, lo, hi)) return rc;
     for (int j = 0; j < 3; j++) {
-        if (int rc = make_stream(&SS.q[j], lo, hi)) return rc;
-        HIP_TRY(hipEventCreateWithFlags(&SS.done[j], hipEventDisableTiming));
+        if (int rc = make_stream(SS.q[j], lo, hi)) return rc;
+        if (int rc = make_event(SS.done[j])) return rc;
     }
-    HIP_TRY(hipEventCreateWithFlags(&SS.go, hipEventDisableTiming));
+    if (int rc = make_event(SS.go)) return rc;
+    G.swset[k] = std::move(SS);
     return 0;
-}
-void drop_sweep_set(int k)
-{
-    State::SweepSet &SS = G.swset[k];
-    if (SS.main) (void)hipStreamDestroy(SS.main);
-    for (int j = 0; j < 3; j++) { if (SS.q[j]) (void)hipStreamDestroy(SS.q[j]); if (SS.done[j]) (void)hipEventDestroy(SS.done[j]); }
-    if (SS.go) (void)hipEventDestroy(SS.go);
-    SS = State::SweepSet{};
 }
 
 // A cloudy batch too small to fill the chip is a latency chain of six kernels; three of them are the sweeps (down above the clouds, the
@@ -764,14 +787,14 @@ int run_prep(hipStream_t s, const Workspace &Wk, const Batch &b, const GcmIn &g,
     // side stream, a call that is a single batch, they run side by side: -30 us of its 0.5 ms)
     const bool scan = b.mode == 1 || b.mode == 2, fork = scan && side && side != s;
     if (fork) {
-        HIP_TRY(hipEventRecord(G.ev_fork, s));
-        HIP_TRY(hipStreamWaitEvent(side, G.ev_fork, 0));
+        HIP_TRY(hipEventRecord(G.ev_fork.get(), s));
+        HIP_TRY(hipStreamWaitEvent(side, G.ev_fork.get(), 0));
     }
     LAUNCH("k_colprep", (k_colprep<GCM>), cgrid1, cblock1, fork ? side : s, G.D, Wk, g, c, b.nb, b.col0, b.nct, b.idrv, b.istart, scan ? 0 : 1);
-    if (fork) HIP_TRY(hipEventRecord(G.ev_join, side));
+    if (fork) HIP_TRY(hipEventRecord(G.ev_join.get(), side));
     if (scan) {
         LAUNCH("k_cloudscan", (k_cloudscan<GCM>), cgrid1, cblock1, s, Wk, g, c, b.nb, b.col0, b.nct, b.inflag, b.iceflag, b.liqflag, b.mode);
-        if (fork) HIP_TRY(hipStreamWaitEvent(s, G.ev_join, 0));
+        if (fork) HIP_TRY(hipStreamWaitEvent(s, G.ev_join.get(), 0));
         const dim3 lgrid((b.nb + BLOCK - 1) / BLOCK, Wk.nlay), lblock(BLOCK);
         LAUNCH("k_cloudlay", (k_cloudlay<GCM>), lgrid, lblock, s, G.D, Wk, g, c, b.nb, b.col0, b.nct, b.mode, b.inflag, b.iceflag, b.liqflag);
         LAUNCH("k_blocksort", k_blocksort, dim3(1), dim3(256), s, Wk, (b.nb + 63) / 64, one_sweep(b.nb, b.mode) ? 1 : 0);      // the blocks by cloud top, hand-off levels
@@ -860,7 +883,7 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, const Batch &b, const GcmIn &
     // a batch that does not fill the chip: one band per workgroup, a slab per band (g_split_max, SweepArgs::split) - where the slab arrays hold
     // sixteen slabs of the batch's width
     const size_t pcb_split = align_up((size_t)nb, 64);
-    const bool split = nb <= g_split_max && (size_t)NBND * pcb_split <= G.ws_slabcols && pcb_split <= (size_t)Wk.ncolb;
+    const bool split = nb <= g_split_max && (size_t)NBND * pcb_split <= G.ws.slabcols && pcb_split <= (size_t)Wk.ncolb;
     Wk.pcb = split ? (int)pcb_split : Wk.ncolb;
     if (int rc = ensure_sweep_attrs()) return rc;
     // The four sweep launches of a batch (bands of 4, 3, 2, 1 quads) are independent.  Each workgroup owns a CU, so a launch ends with
@@ -872,8 +895,8 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, const Batch &b, const GcmIn &
     State::SweepSet &SS = G.swset[sset];
     if (fan) {
         if (int rc = ensure_sweep_set(sset)) return rc;
-        HIP_TRY(hipEventRecord(SS.go, s));
-        for (int k = 0; k < 3; k++) HIP_TRY(hipStreamWaitEvent(SS.q[k], SS.go, 0));
+        HIP_TRY(hipEventRecord(SS.go.get(), s));
+        for (int k = 0; k < 3; k++) HIP_TRY(hipStreamWaitEvent(SS.q[k].get(), SS.go.get(), 0));
     }
     SweepArgs sa = sweep_args<GCM>(b, g, c, out);
     const bool spec = sa.uflxs != nullptr;
@@ -899,7 +922,7 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, const Batch &b, const GcmIn &
     // (each decides by its group's hand-off level; the grids stay those of the batch).
     SweepGroups fg;
     if (!make_groups(b.mode, b.idrv, b.istart, b.iend, fg)) return fail(RRTMG_LW_HIP_EARG, "internal: more than %d sweep groups", NGROUP_MAX);
-    if ((!split && fg.n > G.ws_groups) || (b.idrv == 1 && !G.ws_gdp)) return fail(RRTMG_LW_HIP_EARG, "internal: workspace holds %d band groups, the call needs %d", G.ws_groups, fg.n);
+    if ((!split && fg.n > G.ws.groups) || (b.idrv == 1 && !G.ws.gdp)) return fail(RRTMG_LW_HIP_EARG, "internal: workspace holds %d band groups, the call needs %d", G.ws.groups, fg.n);
     // first slab of every group, slabs per group (k_flux)
     int slab0[NGROUP_MAX];
     unsigned long long gsz = 0ull;
@@ -933,7 +956,7 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, const Batch &b, const GcmIn &
             sa.bands = fg.bands[gi];
             sa.nbands = fg.nb[gi];
             sa.group = slab0[gi];
-            gs = (fan && nq < 4) ? SS.q[3 - nq] : s;
+            gs = (fan && nq < 4) ? SS.q[3 - nq].get() : s;
             int rc = 0;
             if (phase == 1) rc = sweepz(nq);                        // the cloud zone
             else if (b.mode == 0) rc = TUNING ? fail(RRTMG_LW_HIP_EARG, "tuning build: cloudy calls only") : sweepc(nq, 0);
@@ -944,8 +967,8 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, const Batch &b, const GcmIn &
     }
     if (fan) {
         for (int k = 0; k < 3; k++) {
-            HIP_TRY(hipEventRecord(SS.done[k], SS.q[k]));
-            HIP_TRY(hipStreamWaitEvent(s, SS.done[k], 0));
+            HIP_TRY(hipEventRecord(SS.done[k].get(), SS.q[k].get()));
+            HIP_TRY(hipStreamWaitEvent(s, SS.done[k].get(), 0));
         }
     }
     {
@@ -973,18 +996,17 @@ int run_batch(hipStream_t s, const Batch &b, const GcmIn &g, const ColIn &c, con
 // no cell codes, partial slabs or cloud arrays - only the per-column terms and k_optics' wide-window list, in an allocation of its own.
 int ensure_optics_ws(int nlay, int ncolb)
 {
-    if (G.opt_base && G.opt_nlay == nlay && G.opt_ncolb >= ncolb) return 0;
-    if (G.opt_base) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(G.opt_base)); G.opt_base = nullptr; G.opt_bytes = 0; }
+    if (G.opt_buf && G.opt_nlay == nlay && G.opt_ncolb >= ncolb) return 0;
+    if (int rc = drop(G.opt_buf, "gas-optics workspace")) return rc;
     ncolb = std::max(ncolb, G.opt_nlay == nlay ? G.opt_ncolb : 0);
     const size_t n = (size_t)ncolb, L = (size_t)nlay;
     const size_t b_pc = align_up((size_t)NPERCOL * n * 8, 256), b_lt = align_up(n * 4, 256);
     const size_t b_wide = align_up((2 + ((n + LAYER_BLOCK - 1) / LAYER_BLOCK) * L) * 4, 256);
-    HIP_TRY(hipMalloc(&G.opt_base, b_pc + b_lt + b_wide));
-    G.opt_percol = (double *)G.opt_base;
-    G.opt_laytrop = (int *)((char *)G.opt_base + b_pc);
-    G.opt_wide = (int *)((char *)G.opt_base + b_pc + b_lt);
+    if (int rc = grow(G.opt_buf, b_pc + b_lt + b_wide, b_pc + b_lt + b_wide, "gas-optics workspace")) return rc;
+    G.opt_percol = G.opt_buf.as<double>();
+    G.opt_laytrop = (int *)(G.opt_buf.as<char>() + b_pc);
+    G.opt_wide = (int *)(G.opt_buf.as<char>() + b_pc + b_lt);
     HIP_TRY(hipMemset(G.opt_wide, 0, 8));
-    G.opt_bytes = b_pc + b_lt + b_wide;
     G.opt_nlay = nlay;
     G.opt_ncolb = ncolb;
     return 0;
@@ -996,7 +1018,7 @@ template <bool GCM>
 int run_optics(hipStream_t s, const Batch &b, const GcmIn &g, const ColIn &c, const OptOut &o)
 {
     Workspace W{};
-    W.ncolb = G.opt_ncolb; W.pcb = G.opt_ncolb; W.nlay = b.nlay; W.err = G.d_err;
+    W.ncolb = G.opt_ncolb; W.pcb = G.opt_ncolb; W.nlay = b.nlay; W.err = G.d_err.as<int>();
     W.percol = G.opt_percol; W.laytrop = G.opt_laytrop;
     W.wide = GCM && HAVE_WIDE && g_wide_window ? G.opt_wide : nullptr;
     LAUNCH("k_colprep", (k_colprep<GCM>), dim3((b.nb + 63) / 64), dim3(64), s, G.D, W, g, c, b.nb, b.col0, b.nct, b.idrv, 1, 0);
@@ -1020,17 +1042,12 @@ int check_optics(int idrv, const OptOut &o)
 int ensure_pipeline()
 {
     if (G.aux) return 0;
-    HIP_TRY(hipStreamCreateWithFlags(&G.aux, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&G.ev_in, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&G.ev_last, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&G.ev_fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&G.ev_join, hipEventDisableTiming));
-    for (int k = 0; k < 2; k++) {
-        HIP_TRY(hipEventCreateWithFlags(&G.ev_ready[k], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&G.ev_layer[k], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&G.ev_done[k], hipEventDisableTiming));
-    }
-    return 0;
+    Event *const ev[] = {&G.ev_in, &G.ev_last, &G.ev_fork, &G.ev_join, &G.ev_ready[0], &G.ev_layer[0], &G.ev_done[0], &G.ev_ready[1], &G.ev_layer[1], &G.ev_done[1]};
+    int rc = 0;
+    for (Event *e : ev) if (rc == 0) rc = make_event(*e);
+    if (rc == 0) rc = make_stream(G.aux, 0, 0);          // (the marker of "made" last; a failure leaves none of them)
+    if (rc != 0) for (Event *e : ev) (void)e->reset();
+    return rc;
 }
 
 // all batches of a device-resident call on the caller's stream `s`, the per-column kernels of batch i+1 overlapping the
@@ -1052,7 +1069,6 @@ int g_graph_max = []() { const char *e = getenv("RRTMG_LW_GRAPH_MAX"); return e 
 constexpr size_t GRAPH_CACHE = 8;
 void graphs_clear()
 {
-    for (auto &e : G.graphs) if (e.exec) (void)hipGraphExecDestroy(e.exec);
     G.graphs.clear();
 }
 template <class T> void key_put(std::vector<unsigned char> &k, const T &v)
@@ -1072,16 +1088,16 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
     // a call that is ONE batch has nothing for its per-column kernels to run beside: they go on the caller's stream, one cross-stream
     // event hop (~20 us of a 0.6 ms call) less
     const bool single = ncol <= nbmax && !(G.split_sweep && G.cu_layer > 0);
-    const hipStream_t aux = single ? s : G.aux;
+    const hipStream_t aux = single ? s : G.aux.get();
     ColIn c{};
     // sub-column arrays mode keeps per-g-point cloud arrays (odg/cfef) in one set only: no layer/sweep overlap there
-    const bool split = G.split_sweep && G.ws_two_scr && !(mode == 3 && mc);
+    const bool split = G.split_sweep && G.ws.two_scr && !(mode == 3 && mc);
     const bool part = split && G.cu_layer > 0;
     if (part && !G.lay_m) {
-        if (int rc = make_stream(&G.lay_u, 0, 0)) return rc;
-        if (int rc = make_stream(&G.lay_m, 0, G.cu_layer)) return rc;
+        if (int rc = make_stream(G.lay_u, 0, 0)) return rc;
+        if (int rc = make_stream(G.lay_m, 0, G.cu_layer)) return rc;
     }
-    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last, 0));      // an earlier call, possibly on another stream, still owns the workspace
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));      // an earlier call, possibly on another stream, still owns the workspace
     // a small one-batch call as a graph (above): replay, capture (second call with this key), or the plain launches
     State::GraphEnt *gent = nullptr;
     bool capture = false;
@@ -1096,14 +1112,13 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
         // (what else decides which kernels run with which arguments: the workspace, the tuning switches)
         // (what the kernel nodes carry BY VALUE: the tables of this initialisation - DevTables with heatfac and the table pointers - on its device)
         key_put(key, G.init_gen); key_put(key, G.device);
-        key_put(key, G.ws_base); key_put(key, G.ws_bytes); key_put(key, g_colsort); key_put(key, g_colsort_min); key_put(key, g_colsort_clear); key_put(key, g_clear_groups); key_put(key, g_one_sweep_max);
+        key_put(key, G.ws_buf.get()); key_put(key, G.ws_buf.bytes()); key_put(key, g_colsort); key_put(key, g_colsort_min); key_put(key, g_colsort_clear); key_put(key, g_clear_groups); key_put(key, g_one_sweep_max);
         key_put(key, g_wide_window); key_put(key, g_layer_split); key_put(key, g_prep_fork); key_put(key, G.sweep_fanout); key_put(key, eff_batch(nlay)); key_put(key, g_split_max);
         for (auto &e : G.graphs) if (e.key == key) { gent = &e; break; }
         if (!gent) {
             if (G.graphs.size() >= GRAPH_CACHE) {           // the entry used longest ago makes room
                 size_t old = 0;
                 for (size_t j = 1; j < G.graphs.size(); j++) if (G.graphs[j].used < G.graphs[old].used) old = j;
-                if (G.graphs[old].exec) (void)hipGraphExecDestroy(G.graphs[old].exec);
                 G.graphs.erase(G.graphs.begin() + (long)old);
             }
             G.graphs.emplace_back();
@@ -1112,9 +1127,9 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
         }
         gent->used = ++G.graph_clock;
         if (gent->exec) {
-            HIP_TRY(hipGraphLaunch(gent->exec, s));
+            HIP_TRY(hipGraphLaunch(gent->exec.get(), s));
             G.graph_replays++;
-            HIP_TRY(hipEventRecord(G.ev_last, s));
+            HIP_TRY(hipEventRecord(G.ev_last.get(), s));
             G.ev_last_valid = true;
             return 0;
         }
@@ -1122,17 +1137,17 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
         // second is captured
         capture = gent->seen >= 1 && !gent->failed;
         gent->seen++;
-        if (capture && !G.cap) HIP_TRY(hipStreamCreateWithFlags(&G.cap, hipStreamNonBlocking));
+        if (capture && !G.cap) { if (int rc = make_stream(G.cap, 0, 0)) return rc; }
     }
     const hipStream_t s_call = s;
     if (capture) {
-        if (hipStreamBeginCapture(G.cap, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); capture = false; gent->failed = true; }
-        else s = G.cap;
+        if (hipStreamBeginCapture(G.cap.get(), hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); capture = false; gent->failed = true; }
+        else s = G.cap.get();
     }
     const hipStream_t aux_ = capture ? s : aux;
     if (!single) {
-        HIP_TRY(hipEventRecord(G.ev_in, s));             // inputs are ready when the caller's stream gets here
-        HIP_TRY(hipStreamWaitEvent(aux, G.ev_in, 0));
+        HIP_TRY(hipEventRecord(G.ev_in.get(), s));             // inputs are ready when the caller's stream gets here
+        HIP_TRY(hipStreamWaitEvent(aux, G.ev_in.get(), 0));
     }
     int i = 0, rc_cap = 0;
     Batch b = call;
@@ -1140,26 +1155,26 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
         const int nb = std::min(nbmax, ncol - col0), k = i & 1;
         b.nb = nb; b.col0 = col0;
         const Workspace Wk = ws_for(k, use_colsort(true, mode, nb) && !mc);
-        if (i >= 2) HIP_TRY(hipStreamWaitEvent(aux, G.ev_done[k], 0));       // prep set k is free again (sweep of batch i-2 done)
+        if (i >= 2) HIP_TRY(hipStreamWaitEvent(aux, G.ev_done[k].get(), 0));       // prep set k is free again (sweep of batch i-2 done)
         // (The per-column kernels of batch i thus run beside k_layer of batch i-1.  Their few long-lived waves cost whatever runs beside
         // them about what the overlap saves - measured per 1e6 columns: k_layer 32.7 ms beside them, 28.3 alone, step 93.9 vs 96.0 on one
         // stream; held back until k_layer is done they slow the sweep instead, 94.4, and the McICA generator then costs 7 ms more.)
         if (capture) {
             // (one batch, one stream: the batch's launches, the fork to the sweep streams and their join become the graph; an error ends
             // the capture before it is reported)
-            rc_cap = run_prep<true>(s, Wk, b, g, c, g_prep_fork ? G.aux : nullptr);
+            rc_cap = run_prep<true>(s, Wk, b, g, c, g_prep_fork ? G.aux.get() : nullptr);
             if (rc_cap == 0) rc_cap = run_layer<true>(s, Wk, b, g, c);
             if (rc_cap == 0) rc_cap = run_sweep<true>(s, Wk, b, g, c, out);
             continue;
         }
-        if (int rc = run_prep<true>(aux, Wk, b, g, c, single && g_prep_fork ? G.aux : nullptr)) return rc;
+        if (int rc = run_prep<true>(aux, Wk, b, g, c, single && g_prep_fork ? G.aux.get() : nullptr)) return rc;
         if (gen.on) {
             if (int rc = launch_kiss(aux, Wk, ncol, col0, nb, nlay, gen.icld, gen.permuteseed, SubcolIn{g.play, g.cldfr, gen.alpha})) return rc;
         }
-        if (!single) HIP_TRY(hipEventRecord(G.ev_ready[k], aux));
+        if (!single) HIP_TRY(hipEventRecord(G.ev_ready[k].get(), aux));
         // (with a CU partition nothing is enqueued on the caller's stream inside the loop: streams with a CU mask are blocking streams, and
         // where the caller's stream is the null stream every operation on it would be a barrier between them)
-        if (!part && !single) HIP_TRY(hipStreamWaitEvent(s, G.ev_ready[k], 0));
+        if (!part && !single) HIP_TRY(hipStreamWaitEvent(s, G.ev_ready[k].get(), 0));
         if (split) {
             // k_layer of this batch on the caller's stream, its sweep on the sweep set's main stream: the HBM-bound sweep of batch i
             // overlaps the issue-bound k_layer of batch i+1 (scratch set k is free once the sweep of batch i-2 is done).
@@ -1169,50 +1184,50 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
             const bool last = col0 + nbmax >= ncol;
             hipStream_t sl = s;
             int sset = 0;
-            if (part) { sl = i == 0 ? G.lay_u : G.lay_m; sset = last ? 0 : 1; }
+            if (part) { sl = i == 0 ? G.lay_u.get() : G.lay_m.get(); sset = last ? 0 : 1; }
             if (int rc = ensure_sweep_set(sset)) return rc;
-            const hipStream_t ssm = G.swset[sset].main;
+            const hipStream_t ssm = G.swset[sset].main.get();
             if (part) {
-                if (i == 0) HIP_TRY(hipStreamWaitEvent(sl, G.ev_in, 0));
-                HIP_TRY(hipStreamWaitEvent(sl, G.ev_ready[k], 0));
-                if (i >= 1) HIP_TRY(hipStreamWaitEvent(sl, G.ev_layer[(i - 1) & 1], 0));     // (k_layer launches stay in batch order across the two streams)
+                if (i == 0) HIP_TRY(hipStreamWaitEvent(sl, G.ev_in.get(), 0));
+                HIP_TRY(hipStreamWaitEvent(sl, G.ev_ready[k].get(), 0));
+                if (i >= 1) HIP_TRY(hipStreamWaitEvent(sl, G.ev_layer[(i - 1) & 1].get(), 0));     // (k_layer launches stay in batch order across the two streams)
             }
-            if (i >= 2) HIP_TRY(hipStreamWaitEvent(sl, G.ev_done[k], 0));
+            if (i >= 2) HIP_TRY(hipStreamWaitEvent(sl, G.ev_done[k].get(), 0));
             if (int rc = run_layer<true>(sl, Wk, b, g, c)) return rc;
-            HIP_TRY(hipEventRecord(G.ev_layer[k], sl));
-            HIP_TRY(hipStreamWaitEvent(ssm, G.ev_layer[k], 0));
-            if (part && i >= 1) HIP_TRY(hipStreamWaitEvent(ssm, G.ev_done[(i - 1) & 1], 0));   // (the partial slabs and the hand-off array exist once: sweeps stay in batch order across the two sets)
+            HIP_TRY(hipEventRecord(G.ev_layer[k].get(), sl));
+            HIP_TRY(hipStreamWaitEvent(ssm, G.ev_layer[k].get(), 0));
+            if (part && i >= 1) HIP_TRY(hipStreamWaitEvent(ssm, G.ev_done[(i - 1) & 1].get(), 0));   // (the partial slabs and the hand-off array exist once: sweeps stay in batch order across the two sets)
             if (int rc = run_sweep<true>(ssm, Wk, b, g, c, out, sset)) return rc;
-            HIP_TRY(hipEventRecord(G.ev_done[k], ssm));
+            HIP_TRY(hipEventRecord(G.ev_done[k].get(), ssm));
         } else {
             if (int rc = run_layer<true>(s, Wk, b, g, c)) return rc;
             if (int rc = run_sweep<true>(s, Wk, b, g, c, out)) return rc;
-            HIP_TRY(hipEventRecord(G.ev_done[k], s));
+            HIP_TRY(hipEventRecord(G.ev_done[k].get(), s));
         }
     }
     if (capture) {
         (void)aux_;
-        hipGraph_t graph = nullptr;
-        const hipError_t ce = hipStreamEndCapture(G.cap, &graph);
+        Graph graph;             // (the capture's own graph: gone once it is instantiated, or not)
+        const hipError_t ce = hipStreamEndCapture(G.cap.get(), graph.slot());
         s = s_call;
-        if (rc_cap != 0) { if (graph) (void)hipGraphDestroy(graph); gent->failed = true; return rc_cap; }
+        if (rc_cap != 0) { gent->failed = true; return rc_cap; }
         hipGraphExec_t exec = nullptr;
-        if (ce != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+        if (ce != hipSuccess || !graph || hipGraphInstantiate(&exec, graph.get(), nullptr, nullptr, 0) != hipSuccess) {
             // no graph on this runtime for this call shape: the plain launches, now and from here on
             (void)hipGetLastError();
-            if (graph) (void)hipGraphDestroy(graph);
+            graph.reset();
             gent->failed = true;
             return run_pipelined(s, call, g, out, gen);
         }
-        (void)hipGraphDestroy(graph);
-        gent->exec = exec;
+        graph.reset();
+        *gent->exec.slot() = exec;
         G.graph_captures++;
-        HIP_TRY(hipGraphLaunch(exec, s));
+        HIP_TRY(hipGraphLaunch(gent->exec.get(), s));
     }
     if (split) {                                  // the caller's stream sees the results of every batch
-        for (int k = 0; k < std::min(i, 2); k++) HIP_TRY(hipStreamWaitEvent(s, G.ev_done[k], 0));
+        for (int k = 0; k < std::min(i, 2); k++) HIP_TRY(hipStreamWaitEvent(s, G.ev_done[k].get(), 0));
     }
-    HIP_TRY(hipEventRecord(G.ev_last, s));
+    HIP_TRY(hipEventRecord(G.ev_last.get(), s));
     G.ev_last_valid = true;
     return 0;
 }
@@ -1220,11 +1235,11 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
 int read_physics_error(hipStream_t s)
 {
     int code = 0;
-    HIP_TRY(hipMemcpyAsync(&code, G.d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&code, G.d_err.as<int>(), sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (code != 0) {
         int zero = 0;
-        HIP_TRY(hipMemcpy(G.d_err, &zero, sizeof(int), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(G.d_err.as<int>(), &zero, sizeof(int), hipMemcpyHostToDevice));
         return fail(RRTMG_LW_HIP_EPHYSICS, "%s", physics_message(code));
     }
     return 0;
@@ -1232,11 +1247,7 @@ int read_physics_error(hipStream_t s)
 
 int ensure_stage(size_t bytes)
 {
-    if (G.stage_bytes >= bytes) return 0;
-    if (G.stage_base) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(G.stage_base)); G.stage_base = nullptr; G.stage_bytes = 0; }
-    HIP_TRY(hipMalloc(&G.stage_base, bytes));
-    G.stage_bytes = bytes;
-    return 0;
+    return grow(G.stage_buf, bytes, bytes, "host-entry staging");
 }
 
 // the McICA entries exist in both builds: ngptlw sub-columns (src/rrtmg_lw_rad.f90:140, :267-288), masks of MASK_WORDS words
@@ -1355,7 +1366,7 @@ int stage_alloc(std::vector<HostIn> &ins, std::vector<HostOut> &outs, size_t nb)
     for (auto &a : ins) tot += a.h ? a.inner * a.rows * nb : 0;
     for (auto &a : outs) tot += a.rows * nb;
     if (int rc = ensure_stage(tot * 8 + 4096)) return rc;
-    double *p = (double *)G.stage_base;
+    double *p = G.stage_buf.as<double>();
     for (auto &a : ins) { a.d = a.h ? p : nullptr; p += a.h ? a.inner * a.rows * nb : 0; }
     for (auto &a : outs) { a.d = p; p += a.rows * nb; }
     return 0;
@@ -1558,15 +1569,7 @@ unsigned long long static_gen_of(const void *p, size_t bytes)
     return 0;
 }
 
-int ensure_hostbuf(char **p, size_t *cap, size_t bytes)
-{
-    if (*cap >= bytes) return 0;
-    if (*p) { HIP_TRY(hipHostFree(*p)); *p = nullptr; *cap = 0; }
-    const size_t want = bytes + bytes / 4 + 4096;
-    HIP_TRY(hipHostMalloc((void **)p, want, hipHostMallocDefault));
-    *cap = want;
-    return 0;
-}
+int ensure_hostbuf(PinnedBuf &b, size_t bytes) { return grow(b, bytes, bytes + bytes / 4 + 4096, "pinned host staging"); }
 
 // Blocking copies between the caller's (possibly pageable) memory and the device through this library's own pinned buffer: the runtime is
 // never handed a pageable user pointer.  It would pin the range in place, page-granular, and unpin it afterwards - and the unpinning takes a
@@ -1576,27 +1579,27 @@ constexpr size_t BOUNCE_BYTES = (size_t)32 << 20;
 int bounce_h2d(void *dst, const void *src, size_t bytes)
 {
     auto &hs = G.hset[0];
-    if (int rc = ensure_hostbuf(&hs.in, &hs.in_cap, std::min(bytes, BOUNCE_BYTES))) return rc;
+    if (int rc = ensure_hostbuf(hs.in, std::min(bytes, BOUNCE_BYTES))) return rc;
     for (size_t o = 0; o < bytes; o += BOUNCE_BYTES) {
         const size_t n = std::min(BOUNCE_BYTES, bytes - o);
         host_parallel(2 * n, [&](int t, int nt) {
             const size_t a = n * (size_t)t / (size_t)nt, b = n * (size_t)(t + 1) / (size_t)nt;
-            memcpy(hs.in + a, (const char *)src + o + a, b - a);
+            memcpy(hs.in.as<char>() + a, (const char *)src + o + a, b - a);
         });
-        HIP_TRY(hipMemcpy((char *)dst + o, hs.in, n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((char *)dst + o, hs.in.get(), n, hipMemcpyHostToDevice));
     }
     return 0;
 }
 int bounce_d2h(void *dst, const void *src, size_t bytes)
 {
     auto &hs = G.hset[0];
-    if (int rc = ensure_hostbuf(&hs.out, &hs.out_cap, std::min(bytes, BOUNCE_BYTES))) return rc;
+    if (int rc = ensure_hostbuf(hs.out, std::min(bytes, BOUNCE_BYTES))) return rc;
     for (size_t o = 0; o < bytes; o += BOUNCE_BYTES) {
         const size_t n = std::min(BOUNCE_BYTES, bytes - o);
-        HIP_TRY(hipMemcpy(hs.out, (const char *)src + o, n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hs.out.get(), (const char *)src + o, n, hipMemcpyDeviceToHost));
         host_parallel(2 * n, [&](int t, int nt) {
             const size_t a = n * (size_t)t / (size_t)nt, b = n * (size_t)(t + 1) / (size_t)nt;
-            memcpy((char *)dst + o + a, hs.out + a, b - a);
+            memcpy((char *)dst + o + a, hs.out.as<char>() + a, b - a);
         });
     }
     return 0;
@@ -1609,14 +1612,14 @@ int bounce_h2d_rows(void *dst, const void *src, size_t row_bytes, size_t stride_
     if (row_bytes == stride_bytes) return bounce_h2d(dst, src, row_bytes * rows);
     auto &hs = G.hset[0];
     const size_t per = std::max<size_t>(1, BOUNCE_BYTES / row_bytes);
-    if (int rc = ensure_hostbuf(&hs.in, &hs.in_cap, std::min(rows, per) * row_bytes)) return rc;
+    if (int rc = ensure_hostbuf(hs.in, std::min(rows, per) * row_bytes)) return rc;
     for (size_t r0 = 0; r0 < rows; r0 += per) {
         const size_t nr = std::min(per, rows - r0);
         host_parallel(2 * nr * row_bytes, [&](int t, int nt) {
             for (size_t r = nr * (size_t)t / (size_t)nt; r < nr * (size_t)(t + 1) / (size_t)nt; r++)
-                memcpy(hs.in + r * row_bytes, (const char *)src + (r0 + r) * stride_bytes, row_bytes);
+                memcpy(hs.in.as<char>() + r * row_bytes, (const char *)src + (r0 + r) * stride_bytes, row_bytes);
         });
-        HIP_TRY(hipMemcpy((char *)dst + r0 * row_bytes, hs.in, nr * row_bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((char *)dst + r0 * row_bytes, hs.in.get(), nr * row_bytes, hipMemcpyHostToDevice));
     }
     return 0;
 }
@@ -1624,14 +1627,15 @@ int bounce_h2d_rows(void *dst, const void *src, size_t row_bytes, size_t stride_
 int ensure_copy_streams()
 {
     if (G.cp_in) return 0;
-    HIP_TRY(hipStreamCreateWithFlags(&G.cp_in, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&G.cp_out, hipStreamNonBlocking));
-    for (int k = 0; k < HOST_SETS; k++) {
-        HIP_TRY(hipEventCreateWithFlags(&G.ev_h2d[k], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&G.ev_cmp[k], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&G.ev_d2h[k], hipEventDisableTiming));
+    int rc = 0;
+    for (int k = 0; k < HOST_SETS && rc == 0; k++)
+        if ((rc = make_event(G.ev_h2d[k])) == 0 && (rc = make_event(G.ev_cmp[k])) == 0) rc = make_event(G.ev_d2h[k]);
+    if (rc == 0 && (rc = make_stream(G.cp_out, 0, 0)) == 0) rc = make_stream(G.cp_in, 0, 0);      // (the marker of "made" last)
+    if (rc != 0) {
+        G.cp_out.reset();
+        for (int k = 0; k < HOST_SETS; k++) { G.ev_h2d[k].reset(); G.ev_cmp[k].reset(); G.ev_d2h[k].reset(); }
     }
-    return 0;
+    return rc;
 }
 
 // One column batch of the input arrays -> device staging (stream s), moving only what has to move:
@@ -1702,17 +1706,17 @@ int stage_rows(std::vector<HostIn> &ins, size_t nb, int k, hipStream_t s)
         else { q.off = need; need += a.inner * nb * 8; }
     }
     auto &hs = G.hset[k];
-    if (int rc = ensure_hostbuf(&hs.in, &hs.in_cap, need)) return rc;
+    if (int rc = ensure_hostbuf(hs.in, need)) return rc;
     if (need)
         host_parallel(2 * need, [&](int t, int nt) {
             for (size_t j = (size_t)t; j < rows.size(); j += (size_t)nt) {
                 const StagedRow &q = rows[j];
-                if (!q.uniform && !ins[q.arr].src_pinned) memcpy(hs.in + q.off, row_src(q), ins[q.arr].inner * nb * ins[q.arr].src_esz);
+                if (!q.uniform && !ins[q.arr].src_pinned) memcpy(hs.in.as<char>() + q.off, row_src(q), ins[q.arr].inner * nb * ins[q.arr].src_esz);
             }
         });
-    RowFill *tab = reinterpret_cast<RowFill *>(hs.fill);
-    if (int rc = ensure_hostbuf(&hs.widen, &hs.widen_cap, nwiden * sizeof(RowCvt))) return rc;          // (the pipeline has sized it for every row)
-    RowCvt *wtab = reinterpret_cast<RowCvt *>(hs.widen);
+    RowFill *tab = hs.fill.as<RowFill>();
+    if (int rc = ensure_hostbuf(hs.widen, nwiden * sizeof(RowCvt))) return rc;          // (the pipeline has sized it for every row)
+    RowCvt *wtab = hs.widen.as<RowCvt>();
     size_t nf = 0, nw = 0, wmax = 0;
     for (size_t j = 0; j < rows.size();) {
         const StagedRow &q = rows[j];
@@ -1731,13 +1735,13 @@ int stage_rows(std::vector<HostIn> &ins, size_t nb, int k, hipStream_t s)
             const size_t st = land_stride(w);
             float *land = a.land + st / 4 * q.row;
             if (a.src_pinned) HIP_TRY(hipMemcpy2DAsync(land, st, row_src(q), a.inner * a.src_ncol * 4, w * 4, nr, hipMemcpyHostToDevice, s));
-            else HIP_TRY(hipMemcpyAsync(land, hs.in + q.off, nr * st, hipMemcpyHostToDevice, s));
+            else HIP_TRY(hipMemcpyAsync(land, hs.in.as<char>() + q.off, nr * st, hipMemcpyHostToDevice, s));
             for (size_t r = 0; r < nr; r++) wtab[nw++] = RowCvt{dst + w * r, land + st / 4 * r, w};
             wmax = std::max(wmax, w);
         } else if (a.src_pinned) {
             HIP_TRY(hipMemcpy2DAsync(dst, w * 8, row_src(q), a.inner * a.src_ncol * 8, w * 8, nr, hipMemcpyHostToDevice, s));
         } else {
-            HIP_TRY(hipMemcpyAsync(dst, hs.in + q.off, nr * w * 8, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(dst, hs.in.as<char>() + q.off, nr * w * 8, hipMemcpyHostToDevice, s));
         }
         j = j1;
     }
@@ -1763,24 +1767,23 @@ struct StageClock {
 };
 struct NoPrep { int operator()(int, int, int, hipStream_t) const { return 0; } };
 template <class Body, class Prep>
-int host_pipeline_run(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &ins, std::vector<HostOut> &outs, Body body, Prep prep, std::vector<hipEvent_t> &tev);
+int host_pipeline_run(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &ins, std::vector<HostOut> &outs, Body body, Prep prep, std::vector<Event> &tev);
 template <class Body, class Prep = NoPrep>
 int host_pipeline(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &ins, std::vector<HostOut> &outs, Body body, Prep prep = Prep())
 {
-    std::vector<hipEvent_t> tev;             // (timing) per batch: H2D begin / end, kernels begin / end
+    std::vector<Event> tev;                  // (timing) per batch: H2D begin / end, kernels begin / end
     const int rc = host_pipeline_run(ncol, c0, c1, nbmax, ins, outs, body, prep, tev);
     if (rc != 0) {
         // An error part-way leaves up to HOST_SETS batches of DMAs and kernels in flight, some of them to and from the caller's registered
         // arrays: nothing of this call may still be running when the caller gets its error (and frees or unregisters them).
-        if (G.cp_in) (void)hipStreamSynchronize(G.cp_in);
-        if (G.stream) (void)hipStreamSynchronize(G.stream);
-        if (G.cp_out) (void)hipStreamSynchronize(G.cp_out);
+        if (G.cp_in) (void)hipStreamSynchronize(G.cp_in.get());
+        if (G.stream) (void)hipStreamSynchronize(G.stream.get());
+        if (G.cp_out) (void)hipStreamSynchronize(G.cp_out.get());
     }
-    for (auto e : tev) (void)hipEventDestroy(e);
     return rc;
 }
 template <class Body, class Prep>
-int host_pipeline_run(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &ins, std::vector<HostOut> &outs, Body body, Prep prep, std::vector<hipEvent_t> &tev)
+int host_pipeline_run(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &ins, std::vector<HostOut> &outs, Body body, Prep prep, std::vector<Event> &tev)
 {   // columns [c0, c1) of arrays that are ncol columns wide
     if (int rc = ensure_copy_streams()) return rc;
     // (4-byte arrays, the *_r4 entries: behind a set's float64 arrays its float32 landing area - the input rows that travel arrive there and
@@ -1803,17 +1806,17 @@ int host_pipeline_run(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &
     set = set64 + align_up(land, 256);
     if (int rc = ensure_stage(HOST_SETS * set + 4096)) return rc;
     for (auto &hs : G.hset) {
-        if (int rc = ensure_hostbuf(&hs.fill, &hs.fill_cap, nrows * sizeof(RowFill))) return rc;
-        if (int rc = ensure_hostbuf(&hs.out, &hs.out_cap, out_pageable)) return rc;
-        if (int rc = ensure_hostbuf(&hs.widen, &hs.widen_cap, widen_rows * sizeof(RowCvt))) return rc;
-        if (int rc = ensure_hostbuf(&hs.narrow, &hs.narrow_cap, narrow_rows * sizeof(RowCvt))) return rc;
+        if (int rc = ensure_hostbuf(hs.fill, nrows * sizeof(RowFill))) return rc;
+        if (int rc = ensure_hostbuf(hs.out, out_pageable)) return rc;
+        if (int rc = ensure_hostbuf(hs.widen, widen_rows * sizeof(RowCvt))) return rc;
+        if (int rc = ensure_hostbuf(hs.narrow, narrow_rows * sizeof(RowCvt))) return rc;
     }
     auto bind = [&](int k) {                 // point the descriptors at staging set k
-        double *p = (double *)((char *)G.stage_base + (size_t)k * set);
+        double *p = (double *)(G.stage_buf.as<char>() + (size_t)k * set);
         for (auto &a : ins) { a.d = a.h ? p : nullptr; p += a.h ? a.inner * a.rows * (size_t)nbmax : 0; }
         for (auto &a : outs) { a.d = p; p += a.rows * (size_t)nbmax; }
         if (land == 0) return;
-        char *q = (char *)G.stage_base + (size_t)k * set + set64;
+        char *q = G.stage_buf.as<char>() + (size_t)k * set + set64;
         for (auto &a : ins) { const bool on = a.h && a.esz == 4; a.land = on ? (float *)q : nullptr; q += on ? a.rows * land_stride(a.inner * (size_t)nbmax) : 0; }
         for (auto &a : outs) { const bool on = a.active && a.h && a.esz == 4; a.land = on ? (float *)q : nullptr; q += on ? a.rows * land_stride((size_t)nbmax) : 0; }
     };
@@ -1821,38 +1824,38 @@ int host_pipeline_run(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &
     struct Pending { bool on = false; int col0 = 0, nb = 0; } pend[HOST_SETS];
     auto copy_out = [&](int k, int col0, int nb) -> int {
         bind(k);
-        HIP_TRY(hipStreamWaitEvent(G.cp_out, G.ev_cmp[k], 0));
-        char *p = G.hset[k].out;
+        HIP_TRY(hipStreamWaitEvent(G.cp_out.get(), G.ev_cmp[k].get(), 0));
+        char *p = G.hset[k].out.as<char>();
         bool any = false;
         if (narrow_rows) {
             // the active float32 outputs: their staged float64 rows rounded into the landing area by one launch behind the batch's kernels
             // (the table is this set's own: the launch that read it last has ended once the D2H behind it has)
-            if (narrowed[k]) HIP_TRY(hipEventSynchronize(G.ev_d2h[k]));
-            RowCvt *ntab = reinterpret_cast<RowCvt *>(G.hset[k].narrow);
+            if (narrowed[k]) HIP_TRY(hipEventSynchronize(G.ev_d2h[k].get()));
+            RowCvt *ntab = G.hset[k].narrow.as<RowCvt>();
             size_t nn = 0;
             for (auto &a : outs)
                 for (size_t r = 0; a.land && r < a.rows; r++) ntab[nn++] = RowCvt{a.d + (size_t)nb * r, a.land + land_stride((size_t)nb) / 4 * r, (unsigned long long)nb};
             for (size_t f0 = 0; f0 < nn; f0 += 65535)
-                LAUNCH("k_narrow_rows", k_narrow_rows, dim3(cvt_blocks((size_t)nb), (unsigned)std::min<size_t>(65535, nn - f0)), dim3(256), G.cp_out, (const RowCvt *)(ntab + f0));
+                LAUNCH("k_narrow_rows", k_narrow_rows, dim3(cvt_blocks((size_t)nb), (unsigned)std::min<size_t>(65535, nn - f0)), dim3(256), G.cp_out.get(), (const RowCvt *)(ntab + f0));
             narrowed[k] = true;
         }
         for (auto &a : outs) {
             if (!a.active || !a.h) continue;
             if (a.esz == 4) {                // 4-byte rows out of the landing area
                 const size_t st = land_stride((size_t)nb);
-                if (a.pinned) { HIP_TRY(hipMemcpy2DAsync((char *)a.h + (size_t)col0 * 4, (size_t)ncol * 4, a.land, st, (size_t)nb * 4, a.rows, hipMemcpyDeviceToHost, G.cp_out)); continue; }
-                HIP_TRY(hipMemcpyAsync(p, a.land, a.rows * st, hipMemcpyDeviceToHost, G.cp_out));
+                if (a.pinned) { HIP_TRY(hipMemcpy2DAsync((char *)a.h + (size_t)col0 * 4, (size_t)ncol * 4, a.land, st, (size_t)nb * 4, a.rows, hipMemcpyDeviceToHost, G.cp_out.get())); continue; }
+                HIP_TRY(hipMemcpyAsync(p, a.land, a.rows * st, hipMemcpyDeviceToHost, G.cp_out.get()));
                 p += a.rows * st;
                 any = true;
                 continue;
             }
             const size_t w = (size_t)nb * 8, sp = (size_t)ncol * 8;
-            if (a.pinned) { HIP_TRY(hipMemcpy2DAsync(a.h + col0, sp, a.d, w, w, a.rows, hipMemcpyDeviceToHost, G.cp_out)); continue; }
-            HIP_TRY(hipMemcpyAsync(p, a.d, a.rows * w, hipMemcpyDeviceToHost, G.cp_out));
+            if (a.pinned) { HIP_TRY(hipMemcpy2DAsync(a.h + col0, sp, a.d, w, w, a.rows, hipMemcpyDeviceToHost, G.cp_out.get())); continue; }
+            HIP_TRY(hipMemcpyAsync(p, a.d, a.rows * w, hipMemcpyDeviceToHost, G.cp_out.get()));
             p += a.rows * w;
             any = true;
         }
-        HIP_TRY(hipEventRecord(G.ev_d2h[k], G.cp_out));
+        HIP_TRY(hipEventRecord(G.ev_d2h[k].get(), G.cp_out.get()));
         pend[k] = Pending{any, col0, nb};
         return 0;
     };
@@ -1860,17 +1863,17 @@ int host_pipeline_run(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &
     auto unpack = [&](int k, bool must) -> int {
         if (!pend[k].on) return 0;
         if (!must) {
-            const hipError_t q = hipEventQuery(G.ev_d2h[k]);
+            const hipError_t q = hipEventQuery(G.ev_d2h[k].get());
             if (q == hipErrorNotReady) return 0;
             if (q != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "hipEventQuery failed: %s", hipGetErrorString(q));
         }
         pend[k].on = false;
-        HIP_TRY(hipEventSynchronize(G.ev_d2h[k]));
+        HIP_TRY(hipEventSynchronize(G.ev_d2h[k].get()));
         const size_t nb = (size_t)pend[k].nb, col0 = (size_t)pend[k].col0;
         struct Seg { char *dst; const char *src; size_t rows, dpitch, spitch, w; };          // (bytes: rows of 8- or of 4-byte values)
         std::vector<Seg> segs;
         size_t tot = 0, bytes = 0;
-        const char *p = G.hset[k].out;
+        const char *p = G.hset[k].out.as<char>();
         for (auto &a : outs) {
             if (!a.active || !a.h || a.pinned) continue;
             const size_t sp = a.esz == 4 ? land_stride(nb) : nb * 8;
@@ -1891,7 +1894,7 @@ int host_pipeline_run(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &
         return 0;
     };
     StageClock clk;
-    auto tmark = [&](hipStream_t st) { if (!g_stage_timing) return; hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, st); tev.push_back(e); };
+    auto tmark = [&](hipStream_t st) { if (!g_stage_timing) return; Event e; (void)hipEventCreate(e.slot()); (void)hipEventRecord(e.get(), st); tev.push_back(std::move(e)); };
     const auto t_call = std::chrono::steady_clock::now();
     int i = 0, prev_col0 = 0, prev_nb = 0;
     for (int col0 = c0; col0 < c1; col0 += nbmax, i++) {
@@ -1899,27 +1902,27 @@ int host_pipeline_run(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &
         bind(k);
         clk.start();
         if (i >= HOST_SETS) {
-            HIP_TRY(hipStreamWaitEvent(G.cp_in, G.ev_cmp[k], 0));          // kernels of batch i - HOST_SETS have read staging set k
-            HIP_TRY(hipEventSynchronize(G.ev_h2d[k]));                     // its DMAs have left the pinned set k (this thread runs ahead of the device)
+            HIP_TRY(hipStreamWaitEvent(G.cp_in.get(), G.ev_cmp[k].get(), 0));          // kernels of batch i - HOST_SETS have read staging set k
+            HIP_TRY(hipEventSynchronize(G.ev_h2d[k].get()));                     // its DMAs have left the pinned set k (this thread runs ahead of the device)
             clk.lap(0);
             if (int rc = unpack(k, true)) return rc;
             clk.lap(1);
         }
         for (auto &a : ins) { a.src = a.h; a.src_ncol = (size_t)ncol; a.src_col0 = (size_t)col0; a.src_pinned = a.pinned; a.src_esz = a.esz; a.skip = nullptr; a.known = nullptr; a.known_bits = nullptr; }
         // the entry's own host work for this batch (reductions into its pinned scratch set k, which it then names as an array's source)
-        if (int rc = prep(k, col0, nb, G.cp_in)) return rc;
+        if (int rc = prep(k, col0, nb, G.cp_in.get())) return rc;
         clk.lap(2);
-        tmark(G.cp_in);
-        if (int rc = stage_rows(ins, (size_t)nb, k, G.cp_in)) return rc;
-        tmark(G.cp_in);
-        HIP_TRY(hipEventRecord(G.ev_h2d[k], G.cp_in));
+        tmark(G.cp_in.get());
+        if (int rc = stage_rows(ins, (size_t)nb, k, G.cp_in.get())) return rc;
+        tmark(G.cp_in.get());
+        HIP_TRY(hipEventRecord(G.ev_h2d[k].get(), G.cp_in.get()));
         clk.lap(3);
-        HIP_TRY(hipStreamWaitEvent(G.stream, G.ev_h2d[k], 0));
-        if (i >= HOST_SETS) HIP_TRY(hipStreamWaitEvent(G.stream, G.ev_d2h[k], 0));         // outputs of batch i - HOST_SETS have left staging set k
-        tmark(G.stream);
-        if (int rc = body(G.stream, nb, col0, ins, outs)) return rc;
-        tmark(G.stream);
-        HIP_TRY(hipEventRecord(G.ev_cmp[k], G.stream));
+        HIP_TRY(hipStreamWaitEvent(G.stream.get(), G.ev_h2d[k].get(), 0));
+        if (i >= HOST_SETS) HIP_TRY(hipStreamWaitEvent(G.stream.get(), G.ev_d2h[k].get(), 0));         // outputs of batch i - HOST_SETS have left staging set k
+        tmark(G.stream.get());
+        if (int rc = body(G.stream.get(), nb, col0, ins, outs)) return rc;
+        tmark(G.stream.get());
+        HIP_TRY(hipEventRecord(G.ev_cmp[k].get(), G.stream.get()));
         clk.lap(4);
         if (i >= 1)
             if (int rc = copy_out(kprev, prev_col0, prev_nb)) return rc;
@@ -1934,15 +1937,15 @@ int host_pipeline_run(int ncol, int c0, int c1, int nbmax, std::vector<HostIn> &
     if (int rc = copy_out((i + HOST_SETS - 1) % HOST_SETS, prev_col0, prev_nb)) return rc;
     for (int j = 0; j < HOST_SETS; j++)                  // (oldest first)
         if (int rc = unpack((i + j) % HOST_SETS, true)) return rc;
-    HIP_TRY(hipStreamSynchronize(G.cp_out));
-    HIP_TRY(hipStreamSynchronize(G.stream));
+    HIP_TRY(hipStreamSynchronize(G.cp_out.get()));
+    HIP_TRY(hipStreamSynchronize(G.stream.get()));
     clk.lap(6);
     if (g_stage_timing) {
         double h2d = 0.0, ker = 0.0;
         for (size_t e = 0; e + 3 < tev.size(); e += 4) {
             float a = 0.f, b = 0.f;
-            (void)hipEventElapsedTime(&a, tev[e], tev[e + 1]);
-            (void)hipEventElapsedTime(&b, tev[e + 2], tev[e + 3]);
+            (void)hipEventElapsedTime(&a, tev[e].get(), tev[e + 1].get());
+            (void)hipEventElapsedTime(&b, tev[e + 2].get(), tev[e + 3].get());
             h2d += a; ker += b;
         }
         const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
@@ -1993,13 +1996,13 @@ struct MtStates {
     long long seed = -1;
     unsigned long long per = 0, C = 0;
     int M = 0;
-    unsigned *dev = nullptr;            // [NGPT * M][624]
-    size_t cap = 0;                     // states allocated
-    unsigned long long *polys = nullptr;   // [32][MT_PW]
+    DevBuf dev;                         // unsigned [NGPT * M][624]
+    DevBuf polys;                       // unsigned long long [32][MT_PW]
     unsigned long long used = 0;        // last use (the older set makes room)
-    size_t bytes() const { return (dev ? cap * (size_t)MT_NW * sizeof(unsigned) : 0) + (polys ? (size_t)32 * MT_PW * sizeof(unsigned long long) : 0); }
+    size_t bytes() const { return dev.bytes() + polys.bytes(); }
 };
-MtStates g_mt[2];
+owned::NoDestroy<std::array<MtStates, 2>> g_mt_store;      // (never destroyed: see g_states)
+std::array<MtStates, 2> &g_mt = g_mt_store.get();
 mtj::Poly g_mt_phi{};
 bool g_mt_have_phi = false;
 unsigned long long g_mt_clock = 0;
@@ -2010,7 +2013,7 @@ int mt_states(hipStream_t s, uint32_t seed, unsigned long long per, int *M_out, 
     const unsigned long long C = (per + (unsigned long long)M - 1ull) / (unsigned long long)M;
     *M_out = M; *C_out = C;
     for (MtStates &S : g_mt)
-        if (S.dev && S.seed == (long long)seed && S.per == per && S.M == M) { S.used = ++g_mt_clock; *dev_out = S.dev; return 0; }
+        if (S.dev && S.seed == (long long)seed && S.per == per && S.M == M) { S.used = ++g_mt_clock; *dev_out = S.dev.as<unsigned>(); return 0; }
     MtStates &T = g_mt[0].used <= g_mt[1].used ? g_mt[0] : g_mt[1];
     T.used = ++g_mt_clock;
     HIP_TRY(hipDeviceSynchronize());                                // an earlier call may still be reading the states
@@ -2020,15 +2023,12 @@ int mt_states(hipStream_t s, uint32_t seed, unsigned long long per, int *M_out, 
         g_mt_have_phi = true;
     }
     const mtj::Poly &phi = g_mt_phi;
-    const size_t need = (size_t)NGPT * M;
-    if (T.cap < need) {
-        if (T.dev) HIP_TRY(hipFree(T.dev));
-        T.dev = nullptr; T.cap = 0;
-        HIP_TRY(hipMalloc((void **)&T.dev, need * MT_NW * sizeof(unsigned)));
-        T.cap = need;
-    }
-    if (!T.polys) HIP_TRY(hipMalloc((void **)&T.polys, (size_t)32 * MT_PW * sizeof(unsigned long long)));
+    const size_t need = (size_t)NGPT * M * MT_NW * sizeof(unsigned), npoly = (size_t)32 * MT_PW * sizeof(unsigned long long);
+    if (int rc = grow(T.dev, need, need, "MT19937 chunk states")) return rc;
+    if (int rc = grow(T.polys, npoly, npoly, "MT19937 jump polynomials")) return rc;
     T.seed = -1;
+    unsigned *const st = T.dev.as<unsigned>();
+    unsigned long long *const polys = T.polys.as<unsigned long long>();
     // polynomials: slab level k = 0 .. K1-1 (2^K1 >= NGPT), chunk level k = 0 .. K2-1 (2^K2 >= M)
     int K1 = 0, K2 = 0;
     while ((1 << K1) < NGPT) K1++;
@@ -2042,25 +2042,25 @@ int mt_states(hipStream_t s, uint32_t seed, unsigned long long per, int *M_out, 
             for (int k = 0; k < K2; k++) { std::memcpy(&host[(size_t)(K1 + k) * MT_PW], p.data(), sizeof(p)); p = mtj::sqr_mod(p, phi); }
         }
     }
-    HIP_TRY(hipMemcpy(T.polys, host.data(), host.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(polys, host.data(), host.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
     {
         MT19937 mt(seed);                                           // init_genrand (src/mcica_random_numbers.f90:157-169)
-        HIP_TRY(hipMemcpy(T.dev, mt.st, sizeof(mt.st), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(st, mt.st, sizeof(mt.st), hipMemcpyHostToDevice));
     }
     for (int k = 0; k < K1; k++) {
         const int have = 1 << k, n = std::min(have, NGPT - have);
         if (n <= 0) break;
-        hipLaunchKernelGGL(k_mt_jump, dim3(n, 1), dim3(MT_BLOCK), 0, s, T.dev, (const unsigned long long *)(T.polys + (size_t)k * MT_PW), 0, M, 0, have * M);
+        hipLaunchKernelGGL(k_mt_jump, dim3(n, 1), dim3(MT_BLOCK), 0, s, st, (const unsigned long long *)(polys + (size_t)k * MT_PW), 0, M, 0, have * M);
     }
     for (int k = 0; k < K2; k++) {
         const int have = 1 << k, n = std::min(have, M - have);
         if (n <= 0) break;
-        hipLaunchKernelGGL(k_mt_jump, dim3(n, NGPT), dim3(MT_BLOCK), 0, s, T.dev, (const unsigned long long *)(T.polys + (size_t)(K1 + k) * MT_PW), 0, 1, M, have);
+        hipLaunchKernelGGL(k_mt_jump, dim3(n, NGPT), dim3(MT_BLOCK), 0, s, st, (const unsigned long long *)(polys + (size_t)(K1 + k) * MT_PW), 0, 1, M, have);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "k_mt_jump launch failed: %s", hipGetErrorString(e));
     T.seed = (long long)seed; T.per = per; T.C = C; T.M = M;
-    *dev_out = T.dev;
+    *dev_out = st;
     return 0;
 }
 
@@ -2073,17 +2073,17 @@ int kiss_table(hipStream_t s, int stride, int permuteseed, const KissJump **dev,
 {
     KissTable &T = G.kiss;
     const long long seed = std::max(permuteseed, 0);
-    if (!T.dev) HIP_TRY(hipMalloc((void **)&T.dev, sizeof(T.host)));
+    if (int rc = grow(T.dev, sizeof(T.host), sizeof(T.host), "kissvec jump table")) return rc;
     if (T.stride != (unsigned long long)stride || T.seed != seed) {
         // an earlier launch on another stream may still be reading the table
         HIP_TRY(hipDeviceSynchronize());
         for (int g = 0; g < KJ_NGROUP; g++) T.host[g] = kiss_jump_entry((unsigned long long)seed + 8ull * g * (unsigned long long)stride);
         T.host[KJ_NGROUP] = kiss_jump_entry((unsigned long long)stride);
         T.stride = (unsigned long long)stride; T.seed = seed;
-        HIP_TRY(hipMemcpy(T.dev, T.host, sizeof(T.host), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(T.dev.get(), T.host, sizeof(T.host), hipMemcpyHostToDevice));
     }
     (void)s;
-    *dev = T.dev;
+    *dev = T.dev.as<KissJump>();
     *jsub = T.host[KJ_NGROUP];
     return 0;
 }
@@ -2104,15 +2104,15 @@ int launch_kiss(hipStream_t s, const Workspace &Wk, int ncol, int col0, int nb, 
     const KissJump *jt = nullptr;
     KissJump jsub;
     if (int rc = kiss_table(s, stride, permuteseed, &jt, &jsub)) return rc;
-    State::ProfRec r{"k_subcol_kiss", nullptr, nullptr};
-    if (G.profile) { r.a = get_event(); r.b = get_event(); (void)hipEventRecord(r.a, s); }
+    State::ProfRec r{"k_subcol_kiss", {}, {}};
+    if (G.profile) { r.a = get_event(); r.b = get_event(); (void)hipEventRecord(r.a.get(), s); }
     switch (icld) {
     case 1: launch_kiss_rule<1>(s, Wk, in, jt, jsub, ncol, col0, nb, nlay); break;
     case 2: launch_kiss_rule<2>(s, Wk, in, jt, jsub, ncol, col0, nb, nlay); break;
     case 3: launch_kiss_rule<3>(s, Wk, in, jt, jsub, ncol, col0, nb, nlay); break;
     default: launch_kiss_rule<4>(s, Wk, in, jt, jsub, ncol, col0, nb, nlay); break;
     }
-    if (G.profile) { (void)hipEventRecord(r.b, s); G.prof.push_back(r); }
+    if (G.profile) { (void)hipEventRecord(r.b.get(), s); G.prof.push_back(std::move(r)); }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "k_subcol_kiss launch failed: %s", hipGetErrorString(e));
     return 0;
@@ -2124,10 +2124,10 @@ int prepare_mask(int ncol, int nlay, int icld, int irng, const double *alpha)
     if (nlay < 4 && irng == 0) return fail(RRTMG_LW_HIP_EARG, "the kissvec generator needs at least four layers");
     if ((icld == 4 || icld == 5) && !alpha) return fail(RRTMG_LW_HIP_EARG, "icld = 4/5 needs alpha");
     if (int rc = ensure_mask(nlay, (size_t)ncol)) return rc;
-    G.W.mask = G.mask;
+    G.W.mask = G.mask.as<unsigned>();
     G.W.mask_stride = (size_t)ncol;
     G.W.mask_col0 = 0;
-    G.W.err = G.d_err;
+    G.W.err = G.d_err.as<int>();
     if (irng == 0) {
         const size_t lds = (size_t)nlay * KJ_COLS * sizeof(int4);
         // (+ 64: the kernel's few bytes of static LDS count against the same limits)
@@ -2148,13 +2148,13 @@ int generate_mask(hipStream_t s, int ncol, int nlay, int icld, int permuteseed, 
 {
     if (int rc = prepare_mask(ncol, nlay, icld, irng, alpha)) return rc;
     // the mask buffer is shared with an earlier device-entry call that may still be running on another stream
-    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last, 0));
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));
     SubcolIn in{play, cldfrac, alpha};
     if (irng == 0) {
         if (int rc = launch_kiss(s, G.W, ncol, 0, ncol, nlay, icld, permuteseed, in)) return rc;
     } else {
         // one stream over (sub-column, column, layer): drawn chunk-parallel on the device (mt_states), applied per sub-column slab
-        HIP_TRY(hipMemsetAsync(G.mask, 0, (size_t)KJ_NWORD * nlay * ncol * sizeof(unsigned), s));
+        HIP_TRY(hipMemsetAsync(G.mask.get(), 0, (size_t)KJ_NWORD * nlay * ncol * sizeof(unsigned), s));
         const int nd = (icld == 4 || icld == 5) ? 2 : 1;
         const unsigned long long per = icld == 3 ? (unsigned long long)ncol : (unsigned long long)ncol * nlay * nd;
         int M = 0;
@@ -2165,16 +2165,12 @@ int generate_mask(hipStream_t s, int ncol, int nlay, int icld, int permuteseed, 
         // one's launches hold enough chunks (one wavefront each) to fill the device
         const int ns = (int)std::max<unsigned long long>(1ull, std::min<unsigned long long>((unsigned long long)NGPT, (512ull << 20) / (per * 8ull)));     // slabs per pass: at most 512 MB of deviates
         const size_t need = (size_t)ns * per * 8;
-        if (G.rnd_bytes < need) {
-            if (G.d_rnd) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(G.d_rnd)); G.d_rnd = nullptr; G.rnd_bytes = 0; }
-            HIP_TRY(hipMalloc((void **)&G.d_rnd, need));
-            G.rnd_bytes = need;
-        }
+        if (int rc = grow(G.d_rnd, need, need, "MT19937 deviates")) return rc;
         const dim3 block(BLOCK);
         for (int isub = 0; isub < NGPT; isub += ns) {
             const int n = std::min(ns, NGPT - isub);
-            hipLaunchKernelGGL(k_mt_fill, dim3(M, n), dim3(MT_BLOCK), 0, s, (const unsigned *)states, G.d_rnd, isub * M, M, C, per);
-            hipLaunchKernelGGL(k_subcol_slab, dim3((ncol + BLOCK - 1) / BLOCK, (n + SLAB_GROUP - 1) / SLAB_GROUP), block, 0, s, G.W, in, (const double *)G.d_rnd, ncol, nlay, icld, isub, n, per);
+            hipLaunchKernelGGL(k_mt_fill, dim3(M, n), dim3(MT_BLOCK), 0, s, (const unsigned *)states, G.d_rnd.as<double>(), isub * M, M, C, per);
+            hipLaunchKernelGGL(k_subcol_slab, dim3((ncol + BLOCK - 1) / BLOCK, (n + SLAB_GROUP - 1) / SLAB_GROUP), block, 0, s, G.W, in, G.d_rnd.as<const double>(), ncol, nlay, icld, isub, n, per);
         }
     }
     hipError_t e = hipGetLastError();
@@ -2217,30 +2213,28 @@ static int init_state(const char *static_tables_path, const char *kdata_path, do
         (void)hipDeviceSynchronize();
         graphs_clear();
         // (the *_as entries' staging is rebuilt by the next such call, on the device of this initialisation)
-        if (G.form_base) { (void)hipFree(G.form_base); G.form_base = nullptr; G.form_bytes = 0; }
-        if (G.form_gen) { (void)hipFree(G.form_gen); G.form_gen = nullptr; G.form_gen_bytes = 0; }
-        if (G.device != device && G.cap) { (void)hipStreamDestroy(G.cap); G.cap = nullptr; }       // (the capture stream belongs to the device it was made on)
+        G.form_buf.reset();
+        G.form_gen.reset();
+        if (G.device != device) G.cap.reset();       // (the capture stream belongs to the device it was made on)
     }
     static unsigned long long init_count = 0;
     G.init_gen = ++init_count;
     HIP_TRY(hipSetDevice(device));
     G.device = device;                  // (from here on the state owns resources on this device: finalize_state releases them there)
     G.sweep_attrs = false;
-    if (G.d_ktab) { (void)hipFree(G.d_ktab); G.d_ktab = nullptr; }
-    if (G.d_stat) { (void)hipFree(G.d_stat); G.d_stat = nullptr; }
-    HIP_TRY(hipMalloc((void **)&G.d_ktab, G.H.ktab.size() * 8));
-    HIP_TRY(hipMalloc((void **)&G.d_stat, G.H.stat.size() * 8));
-    if (int rc = bounce_h2d(G.d_ktab, G.H.ktab.data(), G.H.ktab.size() * 8)) return rc;          // (never a pageable pointer to the runtime: bounce_h2d)
-    if (int rc = bounce_h2d(G.d_stat, G.H.stat.data(), G.H.stat.size() * 8)) return rc;
-    if (!G.d_err) {
-        HIP_TRY(hipMalloc((void **)&G.d_err, sizeof(int)));
-    }
-    HIP_TRY(hipMemset(G.d_err, 0, sizeof(int)));
-    if (!G.stream) HIP_TRY(hipStreamCreateWithFlags(&G.stream, hipStreamNonBlocking));
+    G.d_ktab.reset();                   // (the tables of an earlier initialisation are never reused, whatever their size)
+    G.d_stat.reset();
+    if (int rc = grow(G.d_ktab, G.H.ktab.size() * 8, G.H.ktab.size() * 8, "k tables")) return rc;
+    if (int rc = grow(G.d_stat, G.H.stat.size() * 8, G.H.stat.size() * 8, "static tables")) return rc;
+    if (int rc = bounce_h2d(G.d_ktab.get(), G.H.ktab.data(), G.H.ktab.size() * 8)) return rc;          // (never a pageable pointer to the runtime: bounce_h2d)
+    if (int rc = bounce_h2d(G.d_stat.get(), G.H.stat.data(), G.H.stat.size() * 8)) return rc;
+    if (int rc = grow(G.d_err, sizeof(int), sizeof(int), "error word")) return rc;
+    HIP_TRY(hipMemset(G.d_err.get(), 0, sizeof(int)));
+    if (!G.stream) { if (int rc = make_stream(G.stream, 0, 0)) return rc; }
     HIP_TRY(hipDeviceGetAttribute(&G.cu_total, hipDeviceAttributeMultiprocessorCount, device));
     DevTables &D = G.D;
-    D.ktab = G.d_ktab;
-    D.stat = G.d_stat;
+    D.ktab = G.d_ktab.as<double>();
+    D.stat = G.d_stat.as<double>();
     for (int b = 0; b < NBND; b++) {
         D.band[b] = G.H.band[b];
         D.delwave[b] = G.H.delwave[b];
@@ -2250,7 +2244,7 @@ static int init_state(const char *static_tables_path, const char *kdata_path, do
     D.absice0[0] = G.H.absice0[0]; D.absice0[1] = G.H.absice0[1];
     D.abscld1 = G.H.abscld1; D.absliq0 = G.H.absliq0;
     D.heatfac = G.H.heatfac; D.fluxfac = G.H.fluxfac; D.oneminus = G.H.oneminus; D.bpade = G.H.bpade;
-    if (G.ws_base) { (void)hipDeviceSynchronize(); (void)hipFree(G.ws_base); G.ws_base = nullptr; G.ws_nlay = 0; G.ws_ncolb = 0; G.ws_cloud = false; G.ws_mc = false; G.ws_groups = 0; G.ws_slabcols = 0; G.ws_gdp = G.ws_efcl = G.ws_ovl = false; }
+    if (G.ws_buf) { G.ws_buf.reset(); G.ws = {}; }
     G.device = device;
     G.n1 = false;
     G.init = true;
@@ -2320,54 +2314,12 @@ static void finalize_state()
     (void)hipSetDevice(G.device);
     (void)hipDeviceSynchronize();
     graphs_clear();
-    if (G.cap) { (void)hipStreamDestroy(G.cap); G.cap = nullptr; }
-    if (G.ws_base) (void)hipFree(G.ws_base);
-    if (G.opt_base) (void)hipFree(G.opt_base);
-    if (G.stage_base) (void)hipFree(G.stage_base);
-    if (G.form_base) (void)hipFree(G.form_base);
-    if (G.form_gen) (void)hipFree(G.form_gen);
     if (first) {            // the queue and the generator's caches live on the first device
-        if (Q.pinned) { forget_pinned(Q.pinned); (void)hipHostFree(Q.pinned); Q.pinned = nullptr; Q.pinned_doubles = 0; }
-        Q.chunks.clear(); Q.ncol = 0; Q.open = false;
+        if (Q.pinned) forget_pinned(Q.pinned.get());
+        Q = ChunkQueue{};
         { std::lock_guard<std::mutex> lk(g_scan_mu); g_scan.clear(); }
         g_static.clear();
-        for (MtStates &S : g_mt) {
-            if (S.dev) (void)hipFree(S.dev);
-            if (S.polys) (void)hipFree(S.polys);
-            S = MtStates{};
-        }
-    }
-    if (G.mask) (void)hipFree(G.mask);
-    if (G.kiss.dev) (void)hipFree(G.kiss.dev);
-    if (G.d_rnd) { (void)hipFree(G.d_rnd); G.d_rnd = nullptr; G.rnd_bytes = 0; }
-    if (G.d_ktab) (void)hipFree(G.d_ktab);
-    if (G.d_stat) (void)hipFree(G.d_stat);
-    if (G.d_err) (void)hipFree(G.d_err);
-    if (G.stream) (void)hipStreamDestroy(G.stream);
-    if (G.cp_in) {
-        (void)hipStreamDestroy(G.cp_in);
-        (void)hipStreamDestroy(G.cp_out);
-        for (int k = 0; k < HOST_SETS; k++) { (void)hipEventDestroy(G.ev_h2d[k]); (void)hipEventDestroy(G.ev_cmp[k]); (void)hipEventDestroy(G.ev_d2h[k]); }
-    }
-    if (G.aux) {
-        (void)hipStreamDestroy(G.aux);
-        (void)hipEventDestroy(G.ev_in);
-        (void)hipEventDestroy(G.ev_last);
-        (void)hipEventDestroy(G.ev_fork);
-        (void)hipEventDestroy(G.ev_join);
-        for (int k = 0; k < 2; k++) { (void)hipEventDestroy(G.ev_ready[k]); (void)hipEventDestroy(G.ev_layer[k]); (void)hipEventDestroy(G.ev_done[k]); }
-    }
-    drop_sweep_set(0);
-    drop_sweep_set(1);
-    if (G.lay_u) (void)hipStreamDestroy(G.lay_u);
-    if (G.lay_m) (void)hipStreamDestroy(G.lay_m);
-    if (G.h_tot) (void)hipHostFree(G.h_tot);
-    for (auto &hs : G.hset) {
-        if (hs.in) (void)hipHostFree(hs.in);
-        if (hs.out) (void)hipHostFree(hs.out);
-        if (hs.fill) (void)hipHostFree(hs.fill);
-        if (hs.widen) (void)hipHostFree(hs.widen);
-        if (hs.narrow) (void)hipHostFree(hs.narrow);
+        for (MtStates &S : g_mt) S = MtStates{};
     }
     G = State();
 }
@@ -2405,9 +2357,9 @@ int rrtmg_lw_hip_debug_scratch(int which, void *dst, size_t bytes, int *info)
 {
     ENTRY_LOCK;
     HIP_TRY(hipDeviceSynchronize());
-    info[0] = G.ws_ncolb; info[1] = G.ws_nlay;
+    info[0] = G.ws.ncolb; info[1] = G.ws.nlay;
     const void *src = which == 2 ? (const void *)G.scrset[0].fw : (const void *)G.scrset[0].scr[which == 1 ? S_CODET : S_CODE];
-    const size_t have = which == 2 ? (size_t)NFW * G.ws_nlay * G.ws_ncolb * 4 : (size_t)NQUAD * G.ws_nlay * G.ws_ncolb * CODE_BYTES;
+    const size_t have = which == 2 ? (size_t)NFW * G.ws.nlay * G.ws.ncolb * 4 : (size_t)NQUAD * G.ws.nlay * G.ws.ncolb * CODE_BYTES;
     HIP_TRY(hipMemcpy(dst, src, std::min(bytes, have), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -2551,14 +2503,14 @@ int rrtmg_lw_hip_set_cu_partition(int layer_cus)
         (void)hipDeviceSynchronize();
         int n = layer_cus <= 0 ? 0 : std::max(8, std::min(G.cu_total - 8, (layer_cus + 4) / 8 * 8));
         if (G.cu_total < 16) n = 0;
-        drop_sweep_set(1);
-        if (G.lay_u) { (void)hipStreamDestroy(G.lay_u); G.lay_u = nullptr; }
-        if (G.lay_m) { (void)hipStreamDestroy(G.lay_m); G.lay_m = nullptr; }
+        G.swset[1] = {};
+        G.lay_u.reset();
+        G.lay_m.reset();
         G.cu_layer = n;
         if (n > 0) {
             G.split_sweep = true;
             // (created here so that a refusal of CU masks by the runtime is reported by this call)
-            if ((rc = make_stream(&G.lay_u, 0, 0)) == 0 && (rc = make_stream(&G.lay_m, 0, n)) == 0) rc = ensure_sweep_set(1);
+            if ((rc = make_stream(G.lay_u, 0, 0)) == 0 && (rc = make_stream(G.lay_m, 0, n)) == 0) rc = ensure_sweep_set(1);
             if (rc != 0 && d > 0) g_states[0].err = G.err;
         }
     }
@@ -2586,7 +2538,7 @@ long long rrtmg_lw_hip_workspace_bytes(void)
     size_t tot = 0;
     for (int d = 0; d < g_ndev; d++) {
         const State &S = g_states[d];
-        tot += S.ws_bytes + S.opt_bytes + S.stage_bytes + S.form_bytes + S.form_gen_bytes + S.mask_bytes + S.rnd_bytes + (S.kiss.dev ? sizeof(KissJump) * (KJ_NGROUP + 1) : 0);
+        tot += S.ws_buf.bytes() + S.opt_buf.bytes() + S.stage_buf.bytes() + S.form_buf.bytes() + S.form_gen.bytes() + S.mask.bytes() + S.d_rnd.bytes() + S.kiss.dev.bytes();
     }
     for (const MtStates &M : g_mt) tot += M.bytes();
     return (long long)tot;
@@ -2597,7 +2549,7 @@ int rrtmg_lw_hip_gpoints(void) { return NGPT; }
 void rrtmg_lw_hip_profile_begin(void)
 {
     ENTRY_LOCK;
-    for (auto &r : G.prof) { G.evpool.push_back(r.a); G.evpool.push_back(r.b); }
+    for (auto &r : G.prof) { G.evpool.push_back(std::move(r.a)); G.evpool.push_back(std::move(r.b)); }
     G.prof.clear();
     G.profile = true;
 }
@@ -2614,14 +2566,14 @@ int rrtmg_lw_hip_profile_end(char *buf, int len)
     std::vector<int> count;
     for (auto &r : G.prof) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) ms = 0.f;
+        if (hipEventElapsedTime(&ms, r.a.get(), r.b.get()) != hipSuccess) ms = 0.f;
         size_t k = 0;
         for (; k < names.size(); k++) if (names[k] == r.name) break;
         if (k == names.size()) { names.push_back(r.name); total.push_back(0.0); count.push_back(0); }
         total[k] += ms;
         count[k] += 1;
-        G.evpool.push_back(r.a);
-        G.evpool.push_back(r.b);
+        G.evpool.push_back(std::move(r.a));
+        G.evpool.push_back(std::move(r.b));
     }
     G.prof.clear();
     std::string out;
@@ -2740,10 +2692,10 @@ int nomcica_host_range(const CallDesc &d, int icld, int c0, int c1, const GcmIn 
     const bool use_tot = cloud && d.inflg != 0;
     std::vector<HostIn> ins;
     if (int rc = host_ins(ins, g, nullptr, L, cloud, use_tot ? 1 : NBND, NA_GCM, "", d.esz)) return rc;
-    if (use_tot && G.h_tot_doubles < HOST_SETS * L * (size_t)nbmax) {
-        if (G.h_tot) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipHostFree(G.h_tot)); G.h_tot = nullptr; G.h_tot_doubles = 0; }
-        HIP_TRY(hipHostMalloc((void **)&G.h_tot, HOST_SETS * L * (size_t)nbmax * sizeof(double), hipHostMallocDefault));
-        G.h_tot_doubles = HOST_SETS * L * (size_t)nbmax;
+    if (use_tot) {
+        const size_t need = HOST_SETS * L * (size_t)nbmax * sizeof(double);
+        if (G.h_tot && G.h_tot.bytes() < need) HIP_TRY(hipDeviceSynchronize());        // (an earlier call's copies may still read it)
+        if (int rc = grow(G.h_tot, need, need, "pinned tauctot")) return rc;
     }
     std::vector<unsigned char> cloudfree(L, 0), cf_uni(L, 0);
     std::vector<uint64_t> cf_bits(L, 0);
@@ -2753,7 +2705,7 @@ int nomcica_host_range(const CallDesc &d, int icld, int c0, int c1, const GcmIn 
         else rows_below(g.cldfr, 1, L, (size_t)ncol, (size_t)col0, (size_t)nb, 1.e-20, cloudfree.data(), cf_uni.data(), cf_bits.data());
         skip_cloudfree(ins, cloudfree.data(), cf_uni.data(), cf_bits.data());
         if (!use_tot) return 0;
-        double *tot = G.h_tot + (size_t)k * L * (size_t)nbmax;        // (the pipeline has waited for the copies that read scratch set k last)
+        double *tot = G.h_tot.as<double>() + (size_t)k * L * (size_t)nbmax;        // (the pipeline has waited for the copies that read scratch set k last)
         size_t cloudy_layers = 0;
         for (size_t l = 0; l < L; l++) cloudy_layers += cloudfree[l] ? 0 : 1;
         host_parallel((size_t)NBND * cloudy_layers * (size_t)nb * d.esz, [&](int t, int nt) {
@@ -2792,7 +2744,7 @@ int nomcica_host_range(const CallDesc &d, int icld, int c0, int c1, const GcmIn 
         return run_batch<true>(s, staged_batch(d, mode, nb), gd, ColIn{}, staged_flux(out_));
     };
     if (int rc = host_pipeline(ncol, c0, c1, nbmax, ins, outs, body, prep)) return rc;
-    hipStream_t s = G.stream;
+    hipStream_t s = G.stream.get();
     return read_physics_error(s);
 }
 
@@ -2896,8 +2848,8 @@ int rrtmg_lw_hip_run_columns(
     for (auto &i : ins) tot += i.cnt;
     const size_t out_d = 10 * n * (L + 1);
     if (int rc = ensure_stage((tot + out_d) * 8 + 4096)) return rc;
-    double *p = (double *)G.stage_base;
-    hipStream_t s = G.stream;
+    double *p = G.stage_buf.as<double>();
+    hipStream_t s = G.stream.get();
     for (auto &i : ins) {
         i.d = p; p += i.cnt;
         if (int rc = bounce_h2d(i.d, i.h, i.cnt * 8)) return rc;
@@ -2942,14 +2894,14 @@ int rrtmg_lw_hip_gas_optics_device(OPTICS_GCM_PARAMS, void *stream)
     const int nbmax = balanced_batch(ncol, eff_batch(nlay));
     if (int rc = ensure_optics_ws(nlay, nbmax)) return rc;
     const hipStream_t s = (hipStream_t)stream;
-    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last, 0));      // an earlier call, possibly on another stream, still owns the workspace
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));      // an earlier call, possibly on another stream, still owns the workspace
     Batch b;
     b.nlay = nlay; b.nct = ncol; b.idrv = idrv;
     for (b.col0 = 0; b.col0 < ncol; b.col0 += nbmax) {
         b.nb = std::min(nbmax, ncol - b.col0);
         if (int rc = run_optics<true>(s, b, g, ColIn{}, o)) return rc;
     }
-    HIP_TRY(hipEventRecord(G.ev_last, s));
+    HIP_TRY(hipEventRecord(G.ev_last.get(), s));
     G.ev_last_valid = true;
     return 0;
 }
@@ -3018,7 +2970,7 @@ int rrtmg_lw_hip_gas_optics_columns(
     }
     for (auto &r : outs) tot += r.h ? r.cnt : 0;
     if (int rc = ensure_stage(tot * 8 + 4096)) return rc;
-    double *p = (double *)G.stage_base;
+    double *p = G.stage_buf.as<double>();
     for (auto &i : ins) {
         i.d = p; p += i.cnt;
         if (int rc = bounce_h2d(i.d, i.h, i.cnt * 8)) return rc;
@@ -3026,7 +2978,7 @@ int rrtmg_lw_hip_gas_optics_columns(
     for (auto &r : outs) if (r.h) { r.d = p; p += r.cnt; }
     const ColIn c{ins[0].d, ins[1].d, ins[2].d, ins[3].d, ins[4].d, ins[5].d, ins[6].d, ins[7].d, ins[8].d, ins[9].d, ins[10].d};
     const OptOut o{outs[0].d, outs[1].d, outs[2].d, outs[3].d, outs[4].d, outs[5].d};
-    const hipStream_t s = G.stream;
+    const hipStream_t s = G.stream.get();
     Batch b;
     b.nlay = nlayers; b.nct = b.nb = ncol; b.idrv = idrv;
     if (int rc = run_optics<false>(s, b, GcmIn{}, c, o)) return rc;
@@ -3064,8 +3016,8 @@ int rrtmg_lw_hip_run_columns_mcica(
     for (auto &i : ins) { if (!i.h) return fail(RRTMG_LW_HIP_EARG, "null input array"); tot += i.cnt; }
     const size_t out_d = 10 * n * (L + 1);
     if (int rc = ensure_stage((tot + out_d) * 8 + 4096)) return rc;
-    double *p = (double *)G.stage_base;
-    hipStream_t s = G.stream;
+    double *p = G.stage_buf.as<double>();
+    hipStream_t s = G.stream.get();
     for (auto &i : ins) {
         i.d = p; p += i.cnt;
         if (int rc = bounce_h2d(i.d, i.h, i.cnt * 8)) return rc;
@@ -3156,16 +3108,14 @@ int rrtmg_lw_hip_calibrate_stream(long long bytes)
     if (!G.init) return fail(RRTMG_LW_HIP_ENOTINIT, "rrtmg_lw_hip_init has not been called");
     if (bytes < 16) return fail(RRTMG_LW_HIP_EARG, "bytes must be >= 16");
     const size_t n = (size_t)bytes / 16;
-    void *a = nullptr, *b = nullptr;
-    HIP_TRY(hipMalloc(&a, n * 16));
-    if (hipMalloc(&b, n * 16) != hipSuccess) { (void)hipFree(a); return fail(RRTMG_LW_HIP_EHIP, "hipMalloc failed"); }
-    (void)hipMemset(a, 0, n * 16);
+    DevBuf a, b;
+    if (int rc = grow(a, n * 16, n * 16, "calibration source")) return rc;
+    if (int rc = grow(b, n * 16, n * 16, "calibration target")) return rc;
+    (void)hipMemset(a.get(), 0, n * 16);
     (void)hipDeviceSynchronize();
     // (through the launch wrapper: under rrtmg_lw_hip_profile_begin / _end the copy's own time is the yardstick of tools/adjust_tsfc_timing.py)
-    LAUNCH("k_calibrate", k_calibrate, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), G.stream, (const double2 *)a, (double2 *)b, n);
-    hipError_t e = hipStreamSynchronize(G.stream);
-    (void)hipFree(a);
-    (void)hipFree(b);
+    LAUNCH("k_calibrate", k_calibrate, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), G.stream.get(), a.as<const double2>(), b.as<double2>(), n);
+    hipError_t e = hipStreamSynchronize(G.stream.get());
     if (e != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "calibration kernel failed: %s", hipGetErrorString(e));
     return 0;
 }
@@ -3233,14 +3183,13 @@ static int solve_chunks(const std::vector<QueuedChunk> &chunks, long long N, Cal
     size_t tot = has_alpha ? doubles(A_ALPHA) : 0;
     for (int a = 0; a < NA_GCM; a++) tot += doubles(a);
     for (int a = A_UFLX; a < A_UFLXS; a++) tot += doubles(a);
-    if (Q.pinned_doubles < tot) {
-        if (Q.pinned) { forget_pinned(Q.pinned); (void)hipHostFree(Q.pinned); Q.pinned = nullptr; Q.pinned_doubles = 0; }
-        HIP_TRY(hipHostMalloc((void **)&Q.pinned, tot * sizeof(double), hipHostMallocDefault));
-        Q.pinned_doubles = tot;
-        g_pinned.emplace_back((const char *)Q.pinned, tot * sizeof(double));
+    if (Q.pinned.bytes() < tot * sizeof(double)) {
+        if (Q.pinned) forget_pinned(Q.pinned.get());
+        if (int rc = grow(Q.pinned, tot * sizeof(double), tot * sizeof(double), "queue staging")) return rc;
+        g_pinned.emplace_back(Q.pinned.as<const char>(), tot * sizeof(double));
     }
     double *in_p[NA_IN] = {}, *out_p[NA_CALL] = {};
-    double *p = Q.pinned;
+    double *p = Q.pinned.as<double>();
     for (int a = 0; a < NA_GCM; a++) { in_p[a] = p; p += doubles(a); }
     for (int a = A_UFLX; a < A_UFLXS; a++) { out_p[a] = p; p += doubles(a); }
     if (has_alpha) in_p[A_ALPHA] = p;
@@ -3497,7 +3446,7 @@ static int mcica_host(const CallDesc &d, const GcmIn &g, const McIn &m, const Fl
         return 0;
     };
     if (int rc = host_pipeline(ncol, c0, c1, nbmax, ins, outs, body, prep)) return rc;
-    hipStream_t s = G.stream;
+    hipStream_t s = G.stream.get();
     return read_physics_error(s);
     });
 }
@@ -3529,7 +3478,7 @@ int rrtmg_lw_hip_get_alpha(int ncol, int nlay, int icld, int idcor, double decor
     for (auto &a : ins) if (!a.h) return fail(RRTMG_LW_HIP_EARG, "null input array");
     std::vector<HostOut> outs = {{alpha, L, 0, true}};
     if (int rc = stage_alloc(ins, outs, n)) return rc;
-    hipStream_t s = G.stream;
+    hipStream_t s = G.stream.get();
     if (int rc = stage_in(ins, n, 0, n, s)) return rc;
     const dim3 grid((ncol + BLOCK - 1) / BLOCK, nlay), block(BLOCK);
     hipLaunchKernelGGL(k_alpha, grid, block, 0, s, ncol, nlay, icld, idcor, decorr_con, (const double *)ins[0].d, (const double *)ins[1].d,
@@ -3569,7 +3518,7 @@ static int subcol_host_range(
     std::vector<HostIn> ins = {{play, 1, L, 0}, {cldfrac, 1, L, 0}, {two ? alpha : nullptr, 1, L, 0}};
     std::vector<HostOut> outs;                                   // outputs are written by the host threads below
     if (int rc = stage_alloc(ins, outs, nl)) return rc;
-    hipStream_t s = G.stream;
+    hipStream_t s = G.stream.get();
     if (int rc = stage_in(ins, n, (size_t)c0, nl, s)) return rc;
     if (int rc = generate_mask(s, (int)nl, nlay, icld, permuteseed, irng, ins[0].d, ins[1].d, ins[2].d)) return rc;
     // The sub-column arrays are implied by the mask (MASK_WORDS x 4 B per (column, layer)) and the grid-mean inputs, which the host holds:
@@ -3578,7 +3527,7 @@ static int subcol_host_range(
     // depth, elsewhere zero).  (Expanding on the device and copying 322 KB per 72-layer column back ran at 0.03 M columns/s.)
     std::vector<unsigned> hmask((size_t)MASK_WORDS * L * nl);
     HIP_TRY(hipStreamSynchronize(s));
-    if (int rc = bounce_d2h(hmask.data(), G.mask, hmask.size() * sizeof(unsigned))) return rc;
+    if (int rc = bounce_d2h(hmask.data(), G.mask.get(), hmask.size() * sizeof(unsigned))) return rc;
     int gband[NGPT];
     for (int ig = 0; ig < NGPT; ig++) { int b = 1; for (int B = 2; B <= NBND; B++) b += (ig >= band_g0(B)) ? 1 : 0; gband[ig] = b - 1; }
     host_parallel((size_t)NGPT * nl * L * 8 * 4, [&](int t, int nt) {
@@ -3679,38 +3628,36 @@ static int mcica_subcol_host_range(const CallDesc &d, int icld_gen, int irng, in
     const int nbmax = balanced_batch(nloc, std::min(eff_batch(nlay), HOST_BATCH));
     if (int rc = ensure_workspace(nlay, nbmax, cloud, false, idrv, mode)) return rc;
     const size_t L = (size_t)nlay, n = (size_t)ncol, nl = (size_t)nloc;
-    hipStream_t s = G.stream;
+    hipStream_t s = G.stream.get();
     // 1. masks of the block's columns: needs play, cldfr, alpha of every one of them
-    double *d_gen = nullptr;
     if (cloud) {
         if (!g.play || !g.cldfr || (two && !alpha)) return fail(RRTMG_LW_HIP_EARG, "null generator input");
         const bool r4 = d.esz == 4;
-        HIP_TRY(hipMalloc((void **)&d_gen, nl * L * (r4 ? 12 : 8) * 3));
+        DevBuf gen_buf;             // (released when this block is left, on every path)
+        if (int rc = grow(gen_buf, nl * L * (r4 ? 12 : 8) * 3, nl * L * (r4 ? 12 : 8) * 3, "generator inputs")) return rc;
+        double *const d_gen = gen_buf.as<double>();
         // (through the library's own pinned buffer: see bounce_h2d)
-        int rc = 0;
         if (r4) {
             // float arrays: the three travel as float32 behind the float64 ones and are widened there (k_widen_rows, an entry each)
             float *f_gen = reinterpret_cast<float *>(d_gen + 3 * nl * L);
             const double *src[3] = {g.play, g.cldfr, two ? alpha : nullptr};
             auto &hs = G.hset[0];
-            rc = ensure_hostbuf(&hs.widen, &hs.widen_cap, 3 * sizeof(RowCvt));
-            RowCvt *wtab = reinterpret_cast<RowCvt *>(hs.widen);
+            if (int rc = ensure_hostbuf(hs.widen, 3 * sizeof(RowCvt))) return rc;
+            RowCvt *wtab = hs.widen.as<RowCvt>();
             unsigned nw = 0;
-            for (size_t a = 0; a < 3 && rc == 0; a++) {
+            for (size_t a = 0; a < 3; a++) {
                 if (!src[a]) continue;
-                rc = bounce_h2d_rows(f_gen + a * nl * L, (const float *)src[a] + c0, nl * 4, n * 4, L);
+                if (int rc = bounce_h2d_rows(f_gen + a * nl * L, (const float *)src[a] + c0, nl * 4, n * 4, L)) return rc;
                 wtab[nw++] = RowCvt{d_gen + a * nl * L, f_gen + a * nl * L, nl * L};
             }
-            if (rc == 0) LAUNCH("k_widen_rows", k_widen_rows, dim3(cvt_blocks(nl * L), nw), dim3(256), s, (const RowCvt *)wtab);
+            LAUNCH("k_widen_rows", k_widen_rows, dim3(cvt_blocks(nl * L), nw), dim3(256), s, (const RowCvt *)wtab);
         } else {
-            rc = bounce_h2d_rows(d_gen, g.play + c0, nl * 8, n * 8, L);
-            if (rc == 0) rc = bounce_h2d_rows(d_gen + nl * L, g.cldfr + c0, nl * 8, n * 8, L);
-            if (rc == 0 && two) rc = bounce_h2d_rows(d_gen + 2 * nl * L, alpha + c0, nl * 8, n * 8, L);
+            if (int rc = bounce_h2d_rows(d_gen, g.play + c0, nl * 8, n * 8, L)) return rc;
+            if (int rc = bounce_h2d_rows(d_gen + nl * L, g.cldfr + c0, nl * 8, n * 8, L)) return rc;
+            if (two) { if (int rc = bounce_h2d_rows(d_gen + 2 * nl * L, alpha + c0, nl * 8, n * 8, L)) return rc; }
         }
-        if (rc == 0) rc = generate_mask(s, nloc, nlay, icld_gen, d.permuteseed, irng, d_gen, d_gen + nl * L, two ? d_gen + 2 * nl * L : nullptr);
-        if (rc == 0 && hipStreamSynchronize(s) != hipSuccess) rc = fail(RRTMG_LW_HIP_EHIP, "generator failed");
-        (void)hipFree(d_gen);
-        if (rc) return rc;
+        if (int rc = generate_mask(s, nloc, nlay, icld_gen, d.permuteseed, irng, d_gen, d_gen + nl * L, two ? d_gen + 2 * nl * L : nullptr)) return rc;
+        if (hipStreamSynchronize(s) != hipSuccess) return fail(RRTMG_LW_HIP_EHIP, "generator failed");      // (the generator has read d_gen before it goes)
     }
     // 2. column batches
     std::vector<HostIn> ins;
@@ -3857,14 +3804,7 @@ int form_launch(hipStream_t s, bool in, const rrtmg_lw_hip_array_form &f, const 
     return launches_ok();
 }
 // the staging of a batch / of the generator's call-wide arrays: grows like the workspace, freed by finalize and by a re-initialisation
-int ensure_form(void **base, size_t *have, size_t bytes)
-{
-    if (*have >= bytes) return 0;
-    if (*base) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(*base)); *base = nullptr; *have = 0; }
-    HIP_TRY(hipMalloc(base, bytes));
-    *have = bytes;
-    return 0;
-}
+int ensure_form(DevBuf &b, size_t bytes) { return grow(b, bytes, bytes, "array-form staging"); }
 
 // what the three entries check first; 1 = the plain form (the entry forwards)
 int form_check(const rrtmg_lw_hip_array_form *f, bool *plain)
@@ -3901,14 +3841,14 @@ int form_solve(const rrtmg_lw_hip_array_form &f, const CallDesc &d, int mode, co
     const size_t nbmax = (size_t)balanced_batch(d.ncol, eff_batch(d.nlay));
     std::vector<double *> si, so;
     const size_t n_in = form_place(ins, nbmax, nullptr, si), n_out = form_place(outs, nbmax, nullptr, so);
-    if (int rc = ensure_form(&G.form_base, &G.form_bytes, (n_in + n_out) * 8)) return rc;
+    if (int rc = ensure_form(G.form_buf, (n_in + n_out) * 8)) return rc;
     if (int rc = ensure_pipeline()) return rc;
-    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last, 0));      // an earlier call, possibly on another stream, still owns the workspace and the staging
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));      // an earlier call, possibly on another stream, still owns the workspace and the staging
     int rc = 0;
     for (size_t col0 = 0; col0 < ncol && rc == 0; col0 += nbmax) {
         const size_t nb = std::min(nbmax, ncol - col0);
-        const size_t used = form_place(ins, nb, (double *)G.form_base, si);
-        form_place(outs, nb, (double *)G.form_base + used, so);
+        const size_t used = form_place(ins, nb, G.form_buf.as<double>(), si);
+        form_place(outs, nb, G.form_buf.as<double>() + used, so);
         const double *sp[NA_IN] = {};
         for (size_t k = 0; k < ins.size(); k++) sp[ins[k].pos] = si[k];
         GcmIn g = gcm_from(sp);
@@ -3921,7 +3861,7 @@ int form_solve(const rrtmg_lw_hip_array_form &f, const CallDesc &d, int mode, co
         if (rc == 0) rc = form_launch(s, false, f, outs, so, ncol, col0, nb);
     }
     G.W.mask_col0 = 0;
-    HIP_TRY(hipEventRecord(G.ev_last, s));
+    HIP_TRY(hipEventRecord(G.ev_last.get(), s));
     G.ev_last_valid = true;
     return rc;
 }
@@ -3959,10 +3899,10 @@ int mcica_subcol_device_as(const rrtmg_lw_hip_array_form &f, const CallDesc &d, 
         if (two) gen.push_back(form_item(alpha, A_ALPHA, L));
         std::vector<double *> sg;
         const size_t need = form_place(gen, n, nullptr, sg);
-        if (int rc = ensure_form(&G.form_gen, &G.form_gen_bytes, need * 8)) return rc;
-        form_place(gen, n, (double *)G.form_gen, sg);
+        if (int rc = ensure_form(G.form_gen, need * 8)) return rc;
+        form_place(gen, n, G.form_gen.as<double>(), sg);
         if (int rc = ensure_pipeline()) return rc;
-        if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last, 0));
+        if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));
         if (int rc = form_launch(s, true, f, gen, sg, n, 0, n)) return rc;
         if (int rc = generate_mask(s, d.ncol, d.nlay, icld_gen, d.permuteseed, *d.irng, sg[0], sg[1], two ? sg[2] : nullptr)) return rc;
     }
@@ -3991,16 +3931,16 @@ int gas_optics_device_as(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, i
     const size_t per_col = (form_place(ins, 1, nullptr, si) + form_place(outs, 1, nullptr, so)) * 8;
     const size_t cap = std::max<size_t>(64, std::min<size_t>((size_t)eff_batch(nlay), ((size_t)256 << 20) / per_col / 64 * 64));
     const size_t nbmax = (size_t)balanced_batch(ncol, (int)std::min<size_t>(cap, (size_t)eff_batch(nlay)));
-    if (int rc = ensure_form(&G.form_base, &G.form_bytes, per_col * nbmax)) return rc;
+    if (int rc = ensure_form(G.form_buf, per_col * nbmax)) return rc;
     if (int rc = ensure_pipeline()) return rc;
     if (int rc = ensure_optics_ws(nlay, (int)nbmax)) return rc;
     const hipStream_t s = (hipStream_t)stream;
-    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last, 0));
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));
     int rc = 0;
     for (size_t col0 = 0; col0 < (size_t)ncol && rc == 0; col0 += nbmax) {
         const size_t nb = std::min(nbmax, (size_t)ncol - col0);
-        const size_t used = form_place(ins, nb, (double *)G.form_base, si);
-        form_place(outs, nb, (double *)G.form_base + used, so);
+        const size_t used = form_place(ins, nb, G.form_buf.as<double>(), si);
+        form_place(outs, nb, G.form_buf.as<double>() + used, so);
         const double *sp[NA_IN] = {};
         for (size_t k = 0; k < ins.size(); k++) sp[ins[k].pos] = si[k];
         double *op[6] = {};
@@ -4011,7 +3951,7 @@ int gas_optics_device_as(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, i
         if (rc == 0) rc = run_optics<true>(s, b, gcm_from(sp), ColIn{}, OptOut{op[0], op[1], op[2], op[3], op[4], op[5]});
         if (rc == 0) rc = form_launch(s, false, f, outs, so, (size_t)ncol, col0, nb);
     }
-    HIP_TRY(hipEventRecord(G.ev_last, s));
+    HIP_TRY(hipEventRecord(G.ev_last.get(), s));
     G.ev_last_valid = true;
     return rc;
 }

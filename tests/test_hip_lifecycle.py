@@ -8,12 +8,16 @@ tests compute one call in a freshly prepared library and compare it with the ora
    tuning switches, failing calls) after each of which a fixed set of probe calls must give the bits it gave in a fresh library;
  * a batch whose workspace rows lie more than 2^31 bytes behind the start of their array: the sweeps read rows through a buffer descriptor
    of 0x7ffffff0 bytes with the row as a scalar byte offset (kernels.hip: sweep_rsrc, bload_*'s soff);
- * the batch size in force (rrtmg_lw_hip_effective_batch): its defaults, and that it keeps those rows inside the descriptor.
+ * the batch size in force (rrtmg_lw_hip_effective_batch): its defaults, and that it keeps those rows inside the descriptor;
+ * three cycles of rrtmg_lw_ini .. finalize in one process with a call per family of GPU resources the driver owns (driver.hip, "who
+   owns what"), and a process that ends without finalize: nothing of the library runs at exit.
 
 Every test leaves the library as the session fixture made it: 140 g-points, stand-in k-data, cpdair 1004.0, device 0, set_batch(0), every
 switch at its previous value."""
+import ctypes
 import os
 import re
+import subprocess
 import sys
 
 import numpy as np
@@ -547,3 +551,161 @@ def test_effective_batch(hip):
         hip.set_batch(0)
     for nlay, b in defaults.items():
         assert hip.effective_batch(nlay) == b, nlay
+
+
+# -------------------------------------------------------------------------------------------- 3. init .. finalize, over and over
+ENOTINIT = 4
+
+
+def _raw(v):
+    """the bytes of an output, whatever holds it"""
+    return (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)).tobytes()
+
+
+class _Families:
+    """One call per family of GPU resources (driver.hip: device buffers, pinned buffers, streams, events, graphs) at 130 columns x 20 layers
+    - a ragged window, a partial 64-column block - cloudy, idrv = 1.  The arrays are made once; a cycle only calls."""
+    NCOL, NLAY = 130, 20
+
+    def __init__(self, hip):
+        import torch
+        from rrtmg_lw_amd import arrays
+        self.hip, self.torch, self.arrays = hip, torch, arrays
+        n, L = self.NCOL, self.NLAY
+        self.dev = _DeviceCall(hip, n, L, "cloudy", idrv=1, col0=0)
+        self.tall = _DeviceCall(hip, n, 72, "cloudy", idrv=1, col0=0)
+        self.host = dict(make_gcm_inputs(n, L, "cloudy"), inflglw=2)
+        self.chunks = [make_gcm_inputs(70, L, "cloudy", col0=0), make_gcm_inputs(60, L, "cloudy", col0=70)]
+        self.form = arrays.ArrayForm(4, 1, 1)
+        x = arrays.from_reference(self.host, self.form)
+        self.formed = {k: (torch.from_numpy(v).to("cuda:0") if isinstance(v, np.ndarray) else v) for k, v in x.items()}
+
+    def cycle(self):
+        """-> (outputs by name, [(workspace_bytes, effective_batch(20)) after every call], [graph_stats deltas])"""
+        hip, torch = self.hip, self.torch
+        res, marks, graphs = {}, [], []
+        s = torch.cuda.current_stream().cuda_stream
+
+        def mark():
+            marks.append((hip.workspace_bytes(), hip.effective_batch(self.NLAY)))
+
+        def keep(tag, out, names):
+            res.update({tag + "." + k: _raw(out[k]) for k in names})
+        flux = OUT6 + ("duflx_dt", "duflxc_dt")
+        hip.rrtmg_lw_ini(1004.0, kdata=hip.STANDIN_KDATA, device=0)
+        mark()
+        c0, r0 = hip.graph_stats()
+        res["device"] = _raw(self.dev.run(3))                            # plain launches, capture, replay
+        c1, r1 = hip.graph_stats()
+        graphs.append((c1 - c0, r1 - r0))
+        mark()
+        keep("host", hip.rrtmg_lw_from_dict(self.host, icld=2, idrv=1), flux)           # copy streams, host sets, h_tot
+        mark()
+        for irng in (0, 1):                                              # mask, kiss table / MT states, d_rnd
+            keep(f"fused{irng}", hip.rrtmg_lw_mcica_subcol_from_dict(self.host, 11, irng, icld=2, idrv=1), flux)
+            mark()
+        keep("optics", hip.gas_optics(self.host, idrv=1), ("taug", "fracs", "planklay", "planklev", "plankbnd", "dplankbnd_dt"))
+        mark()
+        out = self.arrays.empty_like_form(flux, self.NCOL, self.NLAY, self.form, device="cuda:0", fill=float("nan"))
+        hip.rrtmg_lw_device(self.formed, out, icld=2, idrv=1, stream=s, form=self.form)      # form staging
+        hip.check(s)
+        keep("as", out, flux)
+        mark()
+        q = hip.ChunkQueue(self.NLAY, 2, 1, 2, self.host["iceflglw"], self.host["liqflglw"])        # Q.pinned
+        outs = [q.add(c) for c in self.chunks]
+        q.flush()
+        for i, o in enumerate(outs):
+            keep(f"queue{i}", o, flux)
+        mark()
+        buf = ctypes.create_string_buffer(1 << 16)
+        hip.lib().rrtmg_lw_hip_profile_begin()                           # the event pool
+        try:
+            res["profiled"] = _raw(self.dev.run(1))
+        finally:
+            hip.lib().rrtmg_lw_hip_profile_end(buf, len(buf))
+        res["profiled.kernels"] = " ".join(sorted(ln.split()[0] + "x" + ln.split()[1] for ln in buf.value.decode().splitlines() if ln.strip()))
+        mark()
+        c0, r0 = hip.graph_stats()
+        res["tall"] = _raw(self.tall.run(1))                             # 72 layers: the workspace dropped and rebuilt, the graphs cleared
+        res["device.again"] = _raw(self.dev.run(2))                      # (back at 20 layers: plain, then captured anew)
+        c1, r1 = hip.graph_stats()
+        graphs.append((c1 - c0, r1 - r0))
+        mark()
+        hip.finalize()
+        assert hip.num_devices() == 0
+        with pytest.raises(hip.RrtmgLwError, match=f"error {ENOTINIT}: rrtmg_lw_hip_init has not been called"):
+            hip.rrtmg_lw_device(self.dev.d, self.dev.out, icld=2, idrv=1, stream=s)
+        return res, marks, graphs
+
+
+@gpu
+def test_three_cycles_of_init_and_finalize(hip):
+    """rrtmg_lw_ini, one call per resource family, finalize - three times in one process.  Every cycle gives the outputs of the first bit
+    for bit, holds the same device memory (workspace_bytes) and batch size after every call, and captures and replays the same number of
+    graphs; after every finalize the library is uninitialised (num_devices() == 0, a call is refused with RRTMG_LW_HIP_ENOTINIT)."""
+    fam = _Families(hip)
+    try:
+        hip.finalize()
+        first = fam.cycle()
+        res, marks, graphs = first
+        print(f"cycle 1: {len(res)} outputs, workspace_bytes after each call {[m[0] for m in marks]}, graph captures / replays {graphs}")
+        assert res["device"] == res["profiled"] == res["device.again"]          # (graph replay, profiled launches, plain launches: one result)
+        assert all(np.isfinite(np.frombuffer(v, dtype=np.float32 if k.startswith("as.") else np.float64)).all()
+                   for k, v in res.items() if k != "profiled.kernels")
+        assert "k_layer" in res["profiled.kernels"] and graphs[0][0] == 1 and graphs[0][1] >= 1 and graphs[1] == (1, 0)
+        assert marks[-1][0] > marks[1][0] > marks[0][0] >= 0
+        for n in (2, 3):
+            res, marks, graphs = fam.cycle()
+            bad = [k for k in first[0] if res[k] != first[0][k]]
+            assert not bad, f"cycle {n}: {bad} differ from cycle 1"
+            assert marks == first[1], f"cycle {n}: workspace_bytes / effective_batch {marks} against {first[1]}"
+            assert graphs == first[2], f"cycle {n}: graph captures / replays {graphs} against {first[2]}"
+    finally:
+        _as_session(hip)
+
+
+_CHILD = """
+import ctypes, sys
+import numpy as np
+import torch
+from rrtmg_lw_amd import api
+from rrtmg_lw_amd.shard import output_rows, output_views
+from rrtmg_lw_amd.synth import make_gcm_inputs
+api.rrtmg_lw_ini(1004.0, kdata=api.STANDIN_KDATA, device=0)
+dev = torch.device("cuda", 0)
+d = make_gcm_inputs(64, 20, "cloudy", backend="torch", device=dev)
+buf = torch.full((output_rows(20, 0), 64), float("nan"), dtype=torch.float64, device=dev)
+out = output_views(buf, 20, 0)
+s = torch.cuda.current_stream().cuda_stream
+api.rrtmg_lw_device(d, out, icld=2, idrv=0, stream=s)
+api.check(s)
+assert torch.isfinite(buf).all()
+h = api.rrtmg_lw_from_dict(make_gcm_inputs(64, 20, "cloudy"))
+assert np.isfinite(h["uflx"]).all()
+names = ctypes.create_string_buffer(1 << 16)
+api.lib().rrtmg_lw_hip_profile_begin()
+api.rrtmg_lw_device(d, out, icld=2, idrv=0, stream=s)
+api.check(s)
+api.lib().rrtmg_lw_hip_profile_end(names, len(names))
+assert b"k_layer" in names.value
+for _ in range(int(sys.argv[1])):
+    api.finalize()
+print("child: ok", flush=True)
+"""
+
+
+@gpu
+@pytest.mark.parametrize("finalizes", [0, 2], ids=["exit without finalize", "finalize twice"])
+def test_a_process_may_end_without_finalize(finalizes):
+    """A fresh process initialises, makes a device call, a host call and a profiled call of 64 x 20 columns and ends - without
+    rrtmg_lw_hip_finalize (as Python tests and host models do: the library's globals hold streams, events and buffers then, and nothing
+    of it may call into the HIP runtime from a static destructor), or after finalizing twice (the second is a no-op).  Return code 0 and
+    nothing on stderr either way."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""), PYTHONWARNINGS="ignore")
+    p = subprocess.run([sys.executable, "-c", _CHILD, str(finalizes)], timeout=120, capture_output=True, text=True, cwd=root, env=env)
+    print(f"return code {p.returncode}; stdout {p.stdout!r}; stderr {p.stderr!r}")
+    assert p.returncode == 0 and "child: ok" in p.stdout
+    # (libdrm's complaint about its missing table of marketing names, where the file is not installed, is no word of the runtime's)
+    said = [ln for ln in p.stderr.splitlines() if ln.strip() and not ln.rstrip().endswith("amdgpu.ids: No such file or directory")]
+    assert not said, said

@@ -545,8 +545,7 @@ int ensure_sweep_attrs()
     const auto raise = [](auto K) { HIP_TRY(hipFuncSetAttribute((const void *)K.kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, SWEEPC_LDS_MAX)); return 0; };
     if (int rc = sweepc_dispatch(EVERY, EVERY, EVERY, EVERY, raise)) return rc;
     if (int rc = sweepz_dispatch(EVERY, EVERY, EVERY, EVERY, raise)) return rc;
-    HIP_TRY(hipFuncSetAttribute((const void *)k_flux<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FLUX_LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_flux<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FLUX_LDS_BYTES));
+    // (k_flux: its exchange tile, flux_lds_bytes, is static and far below 64 KB)
 #ifndef RRLW_TUNE
     HIP_TRY(hipFuncSetAttribute((const void *)k_n1<false>, hipFuncAttributeMaxDynamicSharedMemorySize, N1_LDS_MAX));      // (the prototype run_sweep launches when G.n1 is set)
 #endif
@@ -972,10 +971,11 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, const Batch &b, const GcmIn &
         }
     }
     {
-        const dim3 wgrid((nb + COLSORT_WIN - 1) / COLSORT_WIN, (b.nlay + 1 + FLUX_LV - 1) / FLUX_LV), wblock(COLSORT_WIN, FLUX_TY);
+        // a window of positions x a chunk of levels per workgroup
+        const dim3 wgrid((nb + COLSORT_WIN - 1) / COLSORT_WIN, (b.nlay + 1 + FLUX_CH - 1) / FLUX_CH), wblock(COLSORT_WIN);
         const double *pz = GCM ? g.plev : c.pz;
-        if (b.idrv == 1) LAUNCH_LDS("k_flux", (k_flux<true>), wgrid, wblock, FLUX_LDS_BYTES, s, G.D, Wk, out, pz, nb, b.col0, b.nct, b.mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0);
-        else LAUNCH_LDS("k_flux", (k_flux<false>), wgrid, wblock, FLUX_LDS_BYTES, s, G.D, Wk, out, pz, nb, b.col0, b.nct, b.mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0);
+        if (b.idrv == 1) LAUNCH("k_flux", (k_flux<true>), wgrid, wblock, s, G.D, Wk, out, pz, nb, b.col0, b.nct, b.mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0);
+        else LAUNCH("k_flux", (k_flux<false>), wgrid, wblock, s, G.D, Wk, out, pz, nb, b.col0, b.nct, b.mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0);
     }
     return launches_ok();
 }
@@ -1151,14 +1151,33 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
     }
     int i = 0, rc_cap = 0;
     Batch b = call;
+    // The per-column kernels of batch j on the auxiliary stream, once prep set j & 1 is free again (sweep of batch j-2 done).
+    // (They thus run beside k_layer of batch j-1.  Their few long-lived waves cost whatever runs beside
+    // them about what the overlap saves - measured per 1e6 columns: k_layer 32.7 ms beside them, 28.3 alone, step 93.9 vs 96.0 on one
+    // stream; held back until k_layer is done they slow the sweep instead, 94.4, and the McICA generator then costs 7 ms more.)
+    const auto prep = [&](int j) -> int {
+        Batch bj = call;
+        bj.col0 = j * nbmax; bj.nb = std::min(nbmax, ncol - bj.col0);
+        const int kj = j & 1;
+        const Workspace Wj = ws_for(kj, use_colsort(true, mode, bj.nb) && !mc);
+        if (j >= 2) HIP_TRY(hipStreamWaitEvent(aux, G.ev_done[kj].get(), 0));
+        if (int rc = run_prep<true>(aux, Wj, bj, g, c, single && g_prep_fork ? G.aux.get() : nullptr)) return rc;
+        if (gen.on) {
+            if (int rc = launch_kiss(aux, Wj, ncol, bj.col0, bj.nb, nlay, gen.icld, gen.permuteseed, SubcolIn{g.play, g.cldfr, gen.alpha})) return rc;
+        }
+        if (!single) HIP_TRY(hipEventRecord(G.ev_ready[kj].get(), aux));
+        return 0;
+    };
+    // The default pipeline enqueues them BEFORE the sweeps of batch j-1.  A process has fewer hardware queues than this pipeline has
+    // streams (the caller's, the auxiliary one, three for the sweeps; four queues by default), so the auxiliary stream shares a queue with
+    // a sweep stream, and a queue takes its packets in the order they were enqueued: behind the sweeps of batch j-1, which wait for that
+    // batch's k_layer, the per-column kernels ran only when those sweeps were done - beside k_flux, which then took 1.42 ms instead of
+    // 0.54 (profiles/flux_walk.md).  (The McICA generator keeps its place: measured where it is.)
+    const bool ahead = !single && !split && !capture && !gen.on;
     for (int col0 = 0; col0 < ncol; col0 += nbmax, i++) {
         const int nb = std::min(nbmax, ncol - col0), k = i & 1;
         b.nb = nb; b.col0 = col0;
         const Workspace Wk = ws_for(k, use_colsort(true, mode, nb) && !mc);
-        if (i >= 2) HIP_TRY(hipStreamWaitEvent(aux, G.ev_done[k].get(), 0));       // prep set k is free again (sweep of batch i-2 done)
-        // (The per-column kernels of batch i thus run beside k_layer of batch i-1.  Their few long-lived waves cost whatever runs beside
-        // them about what the overlap saves - measured per 1e6 columns: k_layer 32.7 ms beside them, 28.3 alone, step 93.9 vs 96.0 on one
-        // stream; held back until k_layer is done they slow the sweep instead, 94.4, and the McICA generator then costs 7 ms more.)
         if (capture) {
             // (one batch, one stream: the batch's launches, the fork to the sweep streams and their join become the graph; an error ends
             // the capture before it is reported)
@@ -1167,11 +1186,7 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
             if (rc_cap == 0) rc_cap = run_sweep<true>(s, Wk, b, g, c, out);
             continue;
         }
-        if (int rc = run_prep<true>(aux, Wk, b, g, c, single && g_prep_fork ? G.aux.get() : nullptr)) return rc;
-        if (gen.on) {
-            if (int rc = launch_kiss(aux, Wk, ncol, col0, nb, nlay, gen.icld, gen.permuteseed, SubcolIn{g.play, g.cldfr, gen.alpha})) return rc;
-        }
-        if (!single) HIP_TRY(hipEventRecord(G.ev_ready[k].get(), aux));
+        if (!ahead || i == 0) { if (int rc = prep(i)) return rc; }
         // (with a CU partition nothing is enqueued on the caller's stream inside the loop: streams with a CU mask are blocking streams, and
         // where the caller's stream is the null stream every operation on it would be a barrier between them)
         if (!part && !single) HIP_TRY(hipStreamWaitEvent(s, G.ev_ready[k].get(), 0));
@@ -1201,6 +1216,7 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
             HIP_TRY(hipEventRecord(G.ev_done[k].get(), ssm));
         } else {
             if (int rc = run_layer<true>(s, Wk, b, g, c)) return rc;
+            if (ahead && col0 + nbmax < ncol) { if (int rc = prep(i + 1)) return rc; }
             if (int rc = run_sweep<true>(s, Wk, b, g, c, out)) return rc;
             HIP_TRY(hipEventRecord(G.ev_done[k].get(), s));
         }

@@ -22,7 +22,7 @@
 //              (transmittance table, the bands' Planck integrals and fractions in LDS); k_sweepc above the hand-off level of the
 //              wave's block group and for cloud-free calls (1 thread / (column, band)), k_sweepz in the cloud zone (1 thread /
 //              (column, quad)); a workgroup = the bands of one group, flux partials added over the group in LDS
-//   k_flux     group partials -> fluxes, net fluxes, heating rates           1 thread / (column, level)
+//   k_flux     group partials -> fluxes, net fluxes, heating rates           1 thread / (column, chunk of levels)
 //   k_subcol_* McICA sub-column generator (bit masks), k_alpha           see the section below
 //
 // Reference lines are cited per routine.  No CPU fallback exists anywhere in this file.
@@ -4175,55 +4175,99 @@ __global__ __launch_bounds__(64 * N1_WAVES) void k_n1(DevTables T, Workspace W, 
 
 // ------------------------------------------------------------------------------------------------
 // k_flux  : sum of the group partials (rtrn :549-574), flux scaling (rtrn :580-594), net flux and heating rate (rtrn :583-604; output
-//           copies src/rrtmg_lw_rad.nomcica.f90:563-583).  A workgroup covers a WINDOW of 256 columns and FLUX_LV levels and sums the
-//           level above them once more, so that no second pass over the flux arrays is needed for the heating rate of its last layer.
-//           The partials lie by POSITION, the caller's arrays by COLUMN (k_colsort): thread (t, .) sums the groups at position w0 + t
-//           (coalesced), the values change places in LDS - position -> column; the same place where the columns are taken as they
-//           lie - and thread (t, .) writes column w0 + t of the caller's arrays (coalesced).  (Gathered at the column's position,
-//           eight bytes per lane, the slabs cost a third more - sixteen cache lines per access instead of four -, scattered to the
-//           position's column the outputs 60 %; and the 256-column rows make this kernel 7 % faster than its 64-column predecessor
-//           where no column moves at all.)
+//           copies src/rrtmg_lw_rad.nomcica.f90:563-583).  A workgroup covers a WINDOW of 256 positions and a CHUNK of FLUX_CH
+//           consecutive levels.  A thread owns one position and walks the chunk's levels upward with the net fluxes u - d, uc - dc and
+//           the pressure of the level below in registers (the form k_adjust_cf has), so the heating rate of a layer needs no second
+//           look at a level; a chunk that does not start at the surface sums the level below its first one once more - the level
+//           belongs to the chunk before, which stores it.  The usual case - four groups of one slab each - has a straight-line body:
+//           the loads of level k + 1 are issued before the sums of level k are used.  Any other group list (SweepArgs::split: a slab
+//           per band; fewer groups) takes the loop over groups and slabs.
+//           The partials lie by POSITION, the caller's arrays by COLUMN (k_colsort).  In a window that kept its order (wsort == 0, or
+//           no order at all) position = column and the thread stores what it summed, straight from registers.  In a reordered window
+//           the values of a level change places through a double-buffered LDS tile - position -> column, one barrier per level - and
+//           thread t writes column w0 + t of the caller's arrays and reads its pressure: loads and stores stay coalesced either way.
+//           (Gathered at the column's position, eight bytes per lane, the slabs cost a third more - sixteen cache lines per access
+//           instead of four -, scattered to the position's column the outputs 60 %.)  The branch is uniform over the workgroup.
 //           clear_from_total: a cloud-free call, the clear-sky stream equals the total-sky stream.  clear_groups: so it does in the
 //           cloud-free block groups of a cloudy call, whose clear-sky sums are formed here from copies of the total ones - the values
 //           k_sweepc<., 2> wrote twice before.  Only bands in [istart, iend] were
 //           swept: the groups hold exactly those.
+//           The sums keep their order - a group's slabs first, in list order, then the groups in order, then x fluxfac - and the
+//           heating rate its expression, so the results are those of the kernel's earlier forms bit for bit.
 // ------------------------------------------------------------------------------------------------
-constexpr int FLUX_LV = 8, FLUX_TY = 4;         // levels of a workgroup (+ 1: the level above, summed again), threads per column
-static_assert(COLSORT_WIN * FLUX_TY <= 1024, "k_flux: a window x FLUX_TY threads");
-constexpr int FLUX_LDS_BYTES = (FLUX_LV + 1) * 4 * COLSORT_WIN * 8;       // 72 KB: two workgroups per CU
+constexpr int FLUX_CH = 18;                     // levels of a chunk: 73 levels are 4 chunks and one of a single level; 250 000 columns 19 workgroups per CU
+constexpr int FLUX_NG = 4;                      // groups of the straight-line body, one slab each
+constexpr unsigned long long FLUX_GSZ1 = 0x1111ull;        // ... as `gsz` states them
+template <bool IDRV> struct FluxRaw { Part2 u[FLUX_NG], d[FLUX_NG], q[IDRV ? FLUX_NG : 1]; };      // a level's group partials as loaded
+struct FluxVal { double u, d, uc, dc, du, duc; };
+constexpr int flux_lds_bytes(bool idrv) { return 2 * (idrv ? 6 : 4) * COLSORT_WIN * 8; }           // the exchange tile: 16 KB, 24 KB with d/dT
 template <bool IDRV>
-__global__ __launch_bounds__(COLSORT_WIN * FLUX_TY) void k_flux(DevTables T, Workspace W, FluxOut out, const double *pz, int ncol, int col0, int nct,
-                                                                int clear_from_total, int ngroups, unsigned long long gsz, int clear_groups)
+__global__ __launch_bounds__(COLSORT_WIN) void k_flux(DevTables T, Workspace W, FluxOut out, const double *pz, int ncol, int col0, int nct,
+                                                      int clear_from_total, int ngroups, unsigned long long gsz, int clear_groups)
 {   // gsz: slabs per group, a nibble each (1, or - SweepArgs::split - the group's bands: added first, in their order, like the group's workgroup does)
-    constexpr int NV = 4, NL = (FLUX_LV + FLUX_TY) / FLUX_TY;      // values that change places at a time; levels per thread
-    extern __shared__ __align__(16) unsigned char smem_f[];
-    double (*s_v)[NV][COLSORT_WIN] = reinterpret_cast<double (*)[NV][COLSORT_WIN]>(smem_f);      // [FLUX_LV + 1]
-    double kdu[IDRV ? NL : 1], kduc[IDRV ? NL : 1];         // d(flux)/dT of this thread's levels: they change places after the fluxes, in the same buffer
-    const int t = threadIdx.x, ty = threadIdx.y, w0 = blockIdx.x * COLSORT_WIN;
-    const int slot = w0 + t, col = w0 + t;                  // the position whose partials this thread sums, the column it writes
-    const bool son = slot < ncol, con = col < ncol;
-    const int nlay = W.nlay, lev0 = blockIdx.y * FLUX_LV;
-    const size_t ncb = W.ncolb, gc = (size_t)col0 + col;
-    const int dst = son ? pcol(W, slot) - w0 : t;           // where the position's column lies in the window
+    constexpr int NV = IDRV ? 6 : 4;                        // values of a level that change places
+    __shared__ double s_v[2][NV][COLSORT_WIN];
+    static_assert(sizeof(s_v) == flux_lds_bytes(IDRV), "k_flux: the exchange tile");
+    const int t = threadIdx.x, w0 = blockIdx.x * COLSORT_WIN;
+    const int slot = w0 + t;                                // the position whose partials this thread sums, and the column it writes
+    const bool on = slot < ncol;
+    const int nlay = W.nlay;
+    const int k0 = blockIdx.y * FLUX_CH, k1 = min(nlay, k0 + FLUX_CH - 1), kf = max(k0 - 1, 0);       // the chunk's levels; the level the walk starts from
+    const size_t gc = (size_t)col0 + slot;
+    const bool moved = pmoved(W, w0);                       // (uniform over the workgroup)
+    const int dst = (moved && on) ? W.perm[slot] - w0 : t;  // where the position's column lies in the window
     // Partials arrive summed per group of bands.  Downward at and above the hand-off level of the position's 64-column block, and everywhere
     // in a cloud-free call, the clear-sky stream equals the total one and one value was written (k_sweepc); below, and upward, two.
-    const int ltop = (son && !clear_from_total) ? W.hblk[slot >> 6] : 0;       // (uniform over the wave)
+    // (uniform over the wave, and read as such: a wave's first lane is a column wherever any of its lanes is)
+    const int ltop = __builtin_amdgcn_readfirstlane((on && !clear_from_total) ? W.hblk[slot >> 6] : 0);
     // (clear_groups - SweepArgs::cfree: a block whose hand-off level is 0 was swept by k_sweepc<., 0>, one value upward as well)
-    const bool up1 = clear_from_total != 0 || (clear_groups != 0 && son && ltop == 0);
+    const bool up1 = clear_from_total != 0 || (clear_groups != 0 && ltop == 0);
+    const size_t pcb = (size_t)W.pcb, nlev = (size_t)nlay + 1;
+    // the straight-line body's loads of one level: every group's slab, 8 or 16 bytes by the block's hand-off level
+    const auto load = [&](int lev, FluxRaw<IDRV> &r) {
+        if (!on) return;
+        const size_t g0 = (size_t)lev * pcb + slot, gs = nlev * pcb;
+        if (clear_from_total || lev >= ltop) {
 #pragma unroll
-    for (int k = 0; k < NL; k++) {          // (unrolled: kdu / kduc stay in registers)
-        const int lc = ty + k * FLUX_TY, lev = lev0 + lc;
-        if constexpr (IDRV) { kdu[k] = 0.0; kduc[k] = 0.0; }
-        if (lc <= FLUX_LV && son && lev <= nlay) {
+            for (int g = 0; g < FLUX_NG; g++) { r.d[g].a = W.gdn1[g0 + g * gs]; r.d[g].b = r.d[g].a; }
+        } else {
+#pragma unroll
+            for (int g = 0; g < FLUX_NG; g++) r.d[g] = W.gdn[g0 + g * gs];
+        }
+        if (up1) {
+#pragma unroll
+            for (int g = 0; g < FLUX_NG; g++) { r.u[g].a = W.gup1[g0 + g * gs]; r.u[g].b = r.u[g].a; }
+        } else {
+#pragma unroll
+            for (int g = 0; g < FLUX_NG; g++) r.u[g] = W.gup[g0 + g * gs];
+        }
+        if constexpr (IDRV) {
+#pragma unroll
+            for (int g = 0; g < FLUX_NG; g++) r.q[g] = W.gdp[g0 + g * gs];
+        }
+    };
+    // ... and their sums, the groups in order
+    const auto sum = [&](const FluxRaw<IDRV> &r) -> FluxVal {
+        double u = 0.0, d = 0.0, uc = 0.0, dc = 0.0, du = 0.0, duc = 0.0;
+#pragma unroll
+        for (int g = 0; g < FLUX_NG; g++) {
+            u = u + r.u[g].a; uc = uc + r.u[g].b;
+            d = d + r.d[g].a; dc = dc + r.d[g].b;
+            if constexpr (IDRV) { du = du + r.q[g].a; duc = duc + r.q[g].b; }
+        }
+        return FluxVal{u, d, uc, dc, du, duc};
+    };
+    // any group list: the slabs of a group first, in list order, then the groups in order
+    const auto sum_list = [&](int lev) -> FluxVal {
+        double u = 0.0, d = 0.0, uc = 0.0, dc = 0.0, du = 0.0, duc = 0.0;
+        if (on) {
             const bool dn1 = clear_from_total || lev >= ltop;
-            double u = 0.0, d = 0.0, uc = 0.0, dc = 0.0, du = 0.0, duc = 0.0;
-            const size_t pcb = (size_t)W.pcb;
             int slab = 0;
             for (int g = 0; g < ngroups; g++) {
                 const int n = (int)((gsz >> (4 * g)) & 15ull);
                 Part2 su{0.0, 0.0}, sd{0.0, 0.0}, sq{0.0, 0.0};
                 for (int q = 0; q < n; q++, slab++) {
-                    const size_t go = ((size_t)slab * (nlay + 1) + lev) * pcb + slot;
+                    const size_t go = ((size_t)slab * nlev + lev) * pcb + slot;
                     Part2 tu, td, tq{0.0, 0.0};
                     if (dn1) { td.a = W.gdn1[go]; td.b = td.a; } else td = W.gdn[go];
                     if (up1) { tu.a = W.gup1[go]; tu.b = tu.a; } else tu = W.gup[go];
@@ -4235,44 +4279,53 @@ __global__ __launch_bounds__(COLSORT_WIN * FLUX_TY) void k_flux(DevTables T, Wor
                 d = d + sd.a; dc = dc + sd.b;
                 du = du + sq.a; duc = duc + sq.b;
             }
-            u = u * T.fluxfac; d = d * T.fluxfac;
-            if (clear_from_total) { uc = u; dc = d; duc = du; }
-            else { uc = uc * T.fluxfac; dc = dc * T.fluxfac; }
-            s_v[lc][0][dst] = u; s_v[lc][1][dst] = d; s_v[lc][2][dst] = uc; s_v[lc][3][dst] = dc;
-            if constexpr (IDRV) { kdu[k] = du; kduc[k] = duc; }
         }
-    }
-    __syncthreads();
-    for (int lc = ty; lc < FLUX_LV; lc += FLUX_TY) {
-        const int lev = lev0 + lc;
-        if (con && lev <= nlay) {
-            const double u = s_v[lc][0][t], d = s_v[lc][1][t], uc = s_v[lc][2][t], dc = s_v[lc][3][t];
-            const size_t o = gc + (size_t)nct * lev;
+        return FluxVal{u, d, uc, dc, du, duc};
+    };
+    double pb = 0.0, nb = 0.0, nbc = 0.0;                   // pressure and net fluxes of the level below
+    // one level of the walk: scaling, the exchange where the window's columns moved, the column's stores
+    const auto level = [&](int lev, FluxVal v, double p) {
+        double u = v.u * T.fluxfac, d = v.d * T.fluxfac, uc, dc, du = v.du, duc = v.duc;
+        if (clear_from_total) { uc = u; dc = d; duc = du; }
+        else { uc = v.uc * T.fluxfac; dc = v.dc * T.fluxfac; }
+        if (moved) {
+            double (*s)[COLSORT_WIN] = s_v[lev & 1];        // (two tiles: a level's is read before the barrier of the next one, written again after it)
+            s[0][dst] = u; s[1][dst] = d; s[2][dst] = uc; s[3][dst] = dc;
+            if constexpr (IDRV) { s[4][dst] = du; s[5][dst] = duc; }
+            __syncthreads();
+            u = s[0][t]; d = s[1][t]; uc = s[2][t]; dc = s[3][t];
+            if constexpr (IDRV) { du = s[4][t]; duc = s[5][t]; }
+        }
+        if (!on) return;
+        const size_t o = gc + (size_t)nct * lev;
+        const double net = u - d, netc = uc - dc;
+        if (lev >= k0) {
             out.uflx[o] = u; out.dflx[o] = d; out.uflxc[o] = uc; out.dflxc[o] = dc;
             if (out.fnet) { out.fnet[o] = u - d; out.fnetc[o] = uc - dc; }
-            if (lev < nlay) {       // net flux and heating rate of the layer above the level
-                const double net = u - d, netc = uc - dc;
-                const double above = s_v[lc + 1][0][t] - s_v[lc + 1][1][t], abovec = s_v[lc + 1][2][t] - s_v[lc + 1][3][t];
-                const double dp = pz[o] - pz[o + (size_t)nct];
-                out.hr[o] = T.heatfac * (net - above) / dp;
-                out.hrc[o] = T.heatfac * (netc - abovec) / dp;
-            }
+            if constexpr (IDRV) { out.duflx_dt[o] = du; out.duflxc_dt[o] = duc; }
         }
-    }
-    if constexpr (IDRV) {
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < NL; k++) {
-            const int lc = ty + k * FLUX_TY, lev = lev0 + lc;
-            if (lc < FLUX_LV && son && lev <= nlay) { s_v[lc][0][dst] = kdu[k]; s_v[lc][1][dst] = kduc[k]; }
+        if (lev > kf) {             // net flux and heating rate of the layer below the level
+            const double dp = pb - p;
+            out.hr[o - (size_t)nct] = T.heatfac * (nb - net) / dp;
+            out.hrc[o - (size_t)nct] = T.heatfac * (nbc - netc) / dp;
         }
-        __syncthreads();
-        for (int lc = ty; lc < FLUX_LV; lc += FLUX_TY) {
-            const int lev = lev0 + lc;
-            if (con && lev <= nlay) {
-                const size_t o = gc + (size_t)nct * lev;
-                out.duflx_dt[o] = s_v[lc][0][t]; out.duflxc_dt[o] = s_v[lc][1][t];
-            }
+        pb = p; nb = net; nbc = netc;
+    };
+    const double *const pzc = pz + gc;
+    double p = on ? pzc[(size_t)nct * kf] : 0.0;
+    if (ngroups == FLUX_NG && gsz == FLUX_GSZ1) {
+        FluxRaw<IDRV> cur{}, nxt{};
+        load(kf, cur);
+        for (int lev = kf; lev <= k1; lev++) {
+            double pn = 0.0;
+            if (lev < k1) { load(lev + 1, nxt); if (on) pn = pzc[(size_t)nct * (lev + 1)]; }
+            level(lev, sum(cur), p);
+            cur = nxt; p = pn;
+        }
+    } else {
+        for (int lev = kf; lev <= k1; lev++) {
+            level(lev, sum_list(lev), p);
+            if (lev < k1 && on) p = pzc[(size_t)nct * (lev + 1)];
         }
     }
 }

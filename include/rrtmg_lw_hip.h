@@ -580,6 +580,78 @@ int rrtmg_lw_hip_adjust_tsfc_device_as(const rrtmg_lw_hip_array_form *form, int 
     const void *uflxc, const void *dflxc, const void *duflxc_dt,
     void *uflx_adj, void *hr_adj, void *uflxc_adj, void *hrc_adj, void *stream);
 
+/* ---- Device arrays with a column stride ("_view") ------------------------------------------------------------------------------------
+ * A GPU-resident host model dimensions its fields (pcols, pver) and calls radiation for ncol <= pcols columns of them, or for a range
+ * of columns out of a wider field.  These four entries take such arrays where they lie: the array form of the *_as entries above
+ * (real_bytes, layer_fastest, top_first: the same meaning) plus
+ *   ld              the column extent of EVERY column-fastest array of the call, inputs and outputs alike, in elements: element (i, k)
+ *                   of a (ncol, nlay) array lies at i + ld*k.  emis and plankbnd are (ld, 16); taucld (16, ld, nlay): element (b, i, k) at
+ *                   b + 16*(i + ld*k); tauaer and planklay (ld, nlay, 16): element (i, k, b) at i + ld*(k + nlay*b); the spectral outputs
+ *                   and planklev (ld, nlay+1, 16); taug and fracs (ld, nlay, NG); tsfc and dtsfc (ncol).  The vertical extent stays nlay /
+ *                   nlay+1 as passed (no vertical stride).  ld = 0 means ncol.  ld < ncol is RRTMG_LW_HIP_EARG.  The largest ld is
+ *                   2^30 = 1 073 741 824; a larger one is RRTMG_LW_HIP_EARG (every product with ld is formed in 64 bits; the bound keeps
+ *                   ld plus a batch's column offset inside 32 bits).  With layer_fastest = 1 the column is the slowest index and a
+ *                   column range is a pointer offset and nothing else: ld must be 0 or ncol, anything else is RRTMG_LW_HIP_EARG.
+ * Pointers: every pointer addresses the element of the FIRST COLUMN OF THE CALL - for columns [c0, c0 + ncol) of a wider field the caller
+ * passes p + c0 (taucld: p + 16*c0; with layer_fastest = 1, p + c0 * the column's values).  The device is chosen from `play` (plev in
+ * the adjustment entry).  Each entry takes the argument list of the *_as entry it is named after behind `view`; the two solver entries
+ * take four more outputs in front of `stream`:
+ *   uflxs, dflxs, uflxcs, dflxcs    the spectral outputs of the *_spectral entries, (ld, nlay+1, 16) ((ncol, nlay+1, 16) in C order with
+ *                   layer_fastest = 1), in the view's element type, vertical order and layout.  All four NULL: the plain call.  Otherwise
+ *                   the rules of the *_spectral entries: uflxs and dflxs both set, uflxcs and dflxcs both NULL or both set.
+ * Results: what the existing entry of the same form returns on contiguous copies of the call's ncol columns (*_device, *_spectral_device,
+ * *_device_as), bit for bit.  Elements outside the call's columns - the padding of each row, the other columns of a wider field - are
+ * never written, and their contents never influence a result (they may hold NaN).
+ * The form {8, 0, 0} runs IN PLACE: the solver's kernels read and write the caller's arrays with ld as their row stride, nothing is
+ * staged, the call keeps the pipelining and the graph replay of the plain device entry (ld is part of a graph's key), and
+ * rrtmg_lw_hip_workspace_bytes() is what the plain entry of the same shape leaves.  One exception: the fused McICA entry with irng = 1
+ * and ld != ncol copies play, cldfr and alpha of the call into ncol-wide arrays of its own first (3 x ncol x nlay x 8 B), as the *_as
+ * entry does - the Mersenne-Twister stream is consumed over the ncol columns of the call, in call order.  {8, 0, 0} with ld = 0 or ncol
+ * is the plain (or spectral) device entry.  The adjustment entry reads and writes in place in every form; it moves 16 bytes per access
+ * where every row of every array starts on a 16-byte boundary and one element otherwise (an odd first column or an odd ld).
+ * A converting form (float32, top first, layer fastest) goes through the staging of the *_as entries; the spectral outputs, when asked
+ * for, are staged like the others: 4 x (nlay+1) x 16 x 8 B more per column of a batch (2 x without the clear-sky pair), allocated only
+ * then.  Errors (RRTMG_LW_HIP_EARG, refused before anything is launched): a null view, the form errors of the *_as entries, the ld
+ * rules above, a half-given spectral pair, and everything the entry named after refuses.
+ * Out of scope: the explicit-sub-column McICA entries, the queue, host pointers, a vertical stride. */
+typedef struct {
+    int real_bytes;
+    int layer_fastest;
+    int top_first;
+    int ld;
+} rrtmg_lw_hip_array_view;
+
+int rrtmg_lw_hip_run_nomcica_device_view(const rrtmg_lw_hip_array_view *view,
+    int ncol, int nlay, int *icld, int idrv,
+    const void *play, const void *plev, const void *tlay, const void *tlev, const void *tsfc,
+    const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *n2ovmr,
+    const void *o2vmr, const void *cfc11vmr, const void *cfc12vmr, const void *cfc22vmr,
+    const void *ccl4vmr, const void *emis, int inflglw, int iceflglw, int liqflglw,
+    const void *cldfr, const void *taucld, const void *cicewp, const void *cliqwp,
+    const void *reice, const void *reliq, const void *tauaer,
+    void *uflx, void *dflx, void *hr, void *uflxc, void *dflxc, void *hrc,
+    void *duflx_dt, void *duflxc_dt, void *uflxs, void *dflxs, void *uflxcs, void *dflxcs, void *stream);
+int rrtmg_lw_hip_run_mcica_subcol_device_view(const rrtmg_lw_hip_array_view *view,
+    int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng,
+    const void *play, const void *plev, const void *tlay, const void *tlev, const void *tsfc,
+    const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *n2ovmr,
+    const void *o2vmr, const void *cfc11vmr, const void *cfc12vmr, const void *cfc22vmr,
+    const void *ccl4vmr, const void *emis, int inflglw, int iceflglw, int liqflglw,
+    const void *cldfr, const void *taucld, const void *cicewp, const void *cliqwp,
+    const void *reice, const void *reliq, const void *alpha, const void *tauaer,
+    void *uflx, void *dflx, void *hr, void *uflxc, void *dflxc, void *hrc,
+    void *duflx_dt, void *duflxc_dt, void *uflxs, void *dflxs, void *uflxcs, void *dflxcs, void *stream);
+int rrtmg_lw_hip_gas_optics_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, int idrv,
+    const void *play, const void *plev, const void *tlay, const void *tlev, const void *tsfc,
+    const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *n2ovmr,
+    const void *o2vmr, const void *cfc11vmr, const void *cfc12vmr, const void *cfc22vmr,
+    const void *ccl4vmr, const void *emis,
+    void *taug, void *fracs, void *planklay, void *planklev, void *plankbnd, void *dplankbnd_dt, void *stream);
+int rrtmg_lw_hip_adjust_tsfc_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, const void *plev, const void *dtsfc,
+    const void *uflx, const void *dflx, const void *duflx_dt,
+    const void *uflxc, const void *dflxc, const void *duflxc_dt,
+    void *uflx_adj, void *hr_adj, void *uflxc_adj, void *hrc_adj, void *stream);
+
 /* ---- Host arrays of a host built with 4-byte reals ("_r4") ----------------------------------------------------------------------------
  * A host model that carries RRTMG_LW at the default real kind (no -r8) owns float arrays.  These four entries take them as they are:
  * HOST pointers, every floating-point array of the call - inputs and outputs, alpha too - `float`.  Layout, argument order, the in/out

@@ -374,19 +374,60 @@ def _form_arg(form, d, out, in_names, out_names):
     return C.byref(_ArrayFormC(*form))
 
 
-def rrtmg_lw_device(d, out, icld=None, idrv=None, stream=None, form=None):
+class _ArrayViewC(C.Structure):
+    """rrtmg_lw_hip_array_view"""
+    _fields_ = [("real_bytes", C.c_int), ("layer_fastest", C.c_int), ("top_first", C.c_int), ("ld", C.c_int)]
+
+
+def _view_arg(form, ld, d, out, in_names, out_names):
+    """The `view` argument of a *_view entry: the array form (None: the reference form) and ld, the column extent of the fields the
+    call's tensors are views of (rrtmg_lw_amd.arrays: shapes and strides of such views; 0 = ncol).  Every tensor the call hands over is
+    checked against it before the library is called - dtype (TypeError); ld < ncol, ld with layer_fastest = 1, a tensor that is not the
+    call's columns of a field ld wide (ValueError)."""
+    from . import arrays
+    form = arrays.ArrayForm(*(form if form is not None else arrays.REFERENCE))
+    if form.real_bytes not in (4, 8) or form.layer_fastest not in (0, 1) or form.top_first not in (0, 1):
+        raise ValueError(f"bad array form {tuple(form)}")
+    ncol, nlay = int(d["ncol"]), int(d["nlay"])
+    ld = arrays.check_ld(ncol, ld, form)
+    for src, names in ((d, in_names), (out, out_names)):
+        for k in names:
+            if src.get(k) is not None:
+                arrays.check_tensor(k, src[k], ncol, nlay, form, gpoints(), ld=ld)
+    return C.byref(_ArrayViewC(*form, ld))
+
+
+def _spec_view(out):
+    """the four spectral arguments of a solver *_view entry: null unless `out` holds them"""
+    return [C.c_void_p(out[k].data_ptr()) if out.get(k) is not None else C.c_void_p(0) for k in _SPEC]
+
+
+def rrtmg_lw_device(d, out, icld=None, idrv=None, stream=None, form=None, ld=None):
     """Device-resident call: `d` holds torch CUDA tensors laid out column-fastest (synth.make_gcm_inputs(backend="torch")),
     `out` a dict of preallocated output tensors (uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt).
     Enqueues on `stream` (an integer hipStream_t handle, e.g. torch.cuda.current_stream().cuda_stream) and returns
     immediately; call check(stream) to synchronise and collect physics errors.  When `out` holds uflxs (and dflxs, optionally
     uflxcs / dflxcs: (ncol, nlay+1, 16) laid out column-fastest, band last) the spectral entry fills them as well.
     form: an rrtmg_lw_amd.arrays.ArrayForm - the tensors of `d` and `out` then lie in that form (float32, (ncol, nlay) C order, top
-    first: see arrays.py) and rrtmg_lw_hip_run_nomcica_device_as takes them as they are; no spectral outputs."""
+    first: see arrays.py) and rrtmg_lw_hip_run_nomcica_device_as takes them as they are; no spectral outputs.
+    ld: an integer - the call goes to rrtmg_lw_hip_run_nomcica_device_view: every tensor of `d` and `out` is a VIEW of the call's
+    d["ncol"] columns inside a column-fastest field ld columns wide (a host's (pcols, pver) fields, a column range of a wider field;
+    arrays.py states the shapes and strides, arrays.embed / field_view make such views; ld=0 means ncol), in `form` if one is given.
+    Nothing outside the views is read or written.  The spectral outputs are available on this path in every form."""
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     icld_c = C.c_int(int(icld))
     ptr = lambda t: C.c_void_p(t.data_ptr())
     args = [C.c_int(d["ncol"]), C.c_int(d["nlay"]), C.byref(icld_c), C.c_int(int(idrv))]
+    if ld is not None:
+        view = _view_arg(form, ld, d, out, _GCM_ORDER + _CLD_ORDER, _FLUX_OUT + _SPEC)
+        args = [view] + args + [ptr(d[k]) for k in _GCM_ORDER]
+        args += [C.c_int(int(d["inflglw"])), C.c_int(int(d["iceflglw"])), C.c_int(int(d["liqflglw"]))]
+        args += [ptr(d[k]) for k in _CLD_ORDER]
+        args += [ptr(out[k]) for k in ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc")]
+        args += [ptr(out[k]) if out.get(k) is not None else C.c_void_p(0) for k in ("duflx_dt", "duflxc_dt")]
+        _check(lib().rrtmg_lw_hip_run_nomcica_device_view(*args, *_spec_view(out), C.c_void_p(stream or 0)))
+        return icld_c.value
     if form is not None:
         if "uflxs" in out:
             raise ValueError("the spectral outputs are not available with an array form")
@@ -510,16 +551,22 @@ def gas_optics(d, idrv=0, out=None):
     return out
 
 
-def gas_optics_device(d, out, stream=None, idrv=None, form=None):
+def gas_optics_device(d, out, stream=None, idrv=None, form=None, ld=None):
     """Device-resident gas optics (rrtmg_lw_hip_gas_optics_device): `d` as for rrtmg_lw_device (torch tensors, column fastest), `out` a
     dict of preallocated float64 tensors laid out column fastest, g-point / band last - taug, fracs of shape (ngpt, nlay, ncol), planklay
     (16, nlay, ncol), planklev (16, nlay+1, ncol), plankbnd, dplankbnd_dt (16, ncol); the Planck ones optional.  Enqueues on `stream`
     and returns; call check(stream) to synchronise.  idrv: d["idrv"] unless given.  form: as for rrtmg_lw_device - with layer_fastest
-    taug and fracs are (ncol, nlay, ngpt) C-contiguous, planklay (ncol, nlay, 16), planklev (ncol, nlay+1, 16), plankbnd (ncol, 16)."""
+    taug and fracs are (ncol, nlay, ngpt) C-contiguous, planklay (ncol, nlay, 16), planklev (ncol, nlay+1, 16), plankbnd (ncol, 16).
+    ld: as for rrtmg_lw_device (rrtmg_lw_hip_gas_optics_device_view) - the tensors are views of the call's columns in fields ld wide,
+    with the logical shapes of arrays.py: taug, fracs (ncol, nlay, ngpt), planklay (ncol, nlay, 16), planklev (ncol, nlay+1, 16)."""
     idrv = d["idrv"] if idrv is None else idrv
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
     args = [C.c_int(d["ncol"]), C.c_int(d["nlay"]), C.c_int(int(idrv))] + [ptr(d[k]) for k in _GCM_ORDER]
     args += [ptr(out.get(k)) for k in _OPTICS]
+    if ld is not None:
+        view = _view_arg(form, ld, d, out, _GCM_ORDER, _OPTICS)
+        _check(lib().rrtmg_lw_hip_gas_optics_device_view(view, *args, C.c_void_p(stream or 0)))
+        return
     if form is not None:
         _check(lib().rrtmg_lw_hip_gas_optics_device_as(_form_arg(form, d, out, _GCM_ORDER, _OPTICS), *args, C.c_void_p(stream or 0)))
         return
@@ -553,6 +600,7 @@ _ADJUST_ARGTYPES = {
     "rrtmg_lw_hip_adjust_tsfc_r4": [C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 12,
     "rrtmg_lw_hip_adjust_tsfc_device": [C.c_int, C.c_int] + [C.c_void_p] * 13,
     "rrtmg_lw_hip_adjust_tsfc_device_as": [C.POINTER(_ArrayFormC), C.c_int, C.c_int] + [C.c_void_p] * 13,
+    "rrtmg_lw_hip_adjust_tsfc_device_view": [C.POINTER(_ArrayViewC), C.c_int, C.c_int] + [C.c_void_p] * 13,
 }
 
 
@@ -593,14 +641,19 @@ def adjust_tsfc(ncol, nlay, plev, dtsfc, uflx, dflx, duflx_dt, uflxc=None, dflxc
     return out
 
 
-def adjust_tsfc_device(arrays, out, stream=None, form=None):
+def adjust_tsfc_device(arrays, out, stream=None, form=None, ld=None):
     """Device-resident adjustment (rrtmg_lw_hip_adjust_tsfc_device): `arrays` holds ncol, nlay and the torch CUDA tensors plev, dtsfc,
     uflx, dflx, duflx_dt and - all or none - uflxc, dflxc, duflxc_dt, laid out column fastest as for rrtmg_lw_device; `out` the
     preallocated tensors uflx_adj, hr_adj and, with the clear-sky inputs, uflxc_adj, hrc_adj.  One kernel launch on `stream`, no
     synchronisation: check(stream) before the results are read.  form: an rrtmg_lw_amd.arrays.ArrayForm - every tensor then lies in
-    that form (dtsfc in its precision) and is read and written where it lies (rrtmg_lw_hip_adjust_tsfc_device_as)."""
+    that form (dtsfc in its precision) and is read and written where it lies (rrtmg_lw_hip_adjust_tsfc_device_as).  ld: as for
+    rrtmg_lw_device (rrtmg_lw_hip_adjust_tsfc_device_view) - the tensors are views of the call's columns in fields ld wide."""
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
     args = [int(arrays["ncol"]), int(arrays["nlay"])] + [ptr(arrays.get(k)) for k in _ADJUST_IN] + [ptr(out.get(k)) for k in _ADJUST_OUT]
+    if ld is not None:
+        view = _view_arg(form, ld, arrays, out, _ADJUST_IN, _ADJUST_OUT)
+        _check(_adjust_fn("rrtmg_lw_hip_adjust_tsfc_device_view")(view, *args, C.c_void_p(stream or 0)))
+        return
     if form is not None:
         _check(_adjust_fn("rrtmg_lw_hip_adjust_tsfc_device_as")(_form_arg(form, arrays, out, _ADJUST_IN, _ADJUST_OUT), *args, C.c_void_p(stream or 0)))
         return
@@ -736,14 +789,24 @@ def rrtmg_lw_mcica_subcol_from_dict(d, permuteseed, irng, alpha=None, icld=None,
                                  d["reliq"], alpha, d["tauaer"], spectral=spectral, out=out, dtype=dtype)
 
 
-def rrtmg_lw_mcica_subcol_device(d, out, permuteseed, irng, alpha=None, icld=None, idrv=None, stream=None, form=None):
-    """Device-resident fused generator + solver (torch CUDA tensors, column-fastest); see rrtmg_lw_device (`form` as there: `alpha` lies
-    in that form as well)."""
+def rrtmg_lw_mcica_subcol_device(d, out, permuteseed, irng, alpha=None, icld=None, idrv=None, stream=None, form=None, ld=None):
+    """Device-resident fused generator + solver (torch CUDA tensors, column-fastest); see rrtmg_lw_device (`form` and `ld` as there:
+    `alpha` lies in that form, and is such a view, as well; ld goes to rrtmg_lw_hip_run_mcica_subcol_device_view)."""
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     icld_c, irng_c = C.c_int(int(icld)), C.c_int(int(irng))
     ptr = lambda t: C.c_void_p(t.data_ptr())
     args = [C.c_int(d["ncol"]), C.c_int(d["nlay"]), C.byref(icld_c), C.c_int(int(idrv)), C.c_int(int(permuteseed)), C.byref(irng_c)]
+    if ld is not None:
+        view = _view_arg(form, ld, dict(d, alpha=alpha), out, _GCM_ORDER + _CLD_ORDER + ("alpha",), _FLUX_OUT + _SPEC)
+        args = [view] + args + [ptr(d[k]) for k in _GCM_ORDER]
+        args += [C.c_int(int(d["inflglw"])), C.c_int(int(d["iceflglw"])), C.c_int(int(d["liqflglw"]))]
+        args += [ptr(d[k]) for k in ("cldfr", "taucld", "cicewp", "cliqwp", "reice", "reliq")]
+        args += [ptr(alpha) if alpha is not None else C.c_void_p(0), ptr(d["tauaer"])]
+        args += [ptr(out[k]) for k in ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc")]
+        args += [ptr(out[k]) if out.get(k) is not None else C.c_void_p(0) for k in ("duflx_dt", "duflxc_dt")]
+        _check(lib().rrtmg_lw_hip_run_mcica_subcol_device_view(*args, *_spec_view(out), C.c_void_p(stream or 0)))
+        return icld_c.value
     if form is not None:
         if "uflxs" in out:
             raise ValueError("the spectral outputs are not available with an array form")

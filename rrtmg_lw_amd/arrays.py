@@ -23,6 +23,19 @@ An ArrayForm(real_bytes, layer_fastest, top_first) describes what a device-resid
     top_first       1: the vertical index runs from the top of the atmosphere: layer k of the reference lies at nlay-1-k, level k at
                        nlay-k (both layouts; inputs and outputs).
 
+A view (include/rrtmg_lw_hip.h, rrtmg_lw_hip_array_view) adds `ld`: the call's ncol columns lie inside column-fastest arrays ld >= ncol
+columns wide - a host model's (pcols, pver) fields, or a range of columns of a wider field.  In Python such an array is a tensor VIEW of
+the field: the logical shape above (ncol columns), column stride 1 (16 for taucld), and every further index strides as in the field:
+
+    (ncol, nlay) arrays                     strides (1, ld)                 emis, plankbnd      (ncol, 16)        strides (1, ld)
+    taucld          (16, ncol, nlay)        strides (1, 16, 16 * ld)        tsfc, dtsfc         (ncol,)           stride 1
+    tauaer, planklay, planklev, taug, fracs, the spectral outputs           (ncol, n1, n2)      strides (1, ld, ld * n1)
+
+which is what `field[c0:c0 + ncol]` (taucld: `field[:, c0:c0 + ncol]`) gives for a field stored with its first index fastest; its
+data_ptr() is the element of the call's first column, as the header asks.  With layer_fastest = 1 the column is the slowest index: a
+range of columns is a contiguous slice, and ld must be 0 or ncol.  field_strides / check_tensor(..., ld=) state and check exactly this;
+embed / field_view lay an array of a form into such a field at a column offset and cut the call's columns out again.
+
 from_reference / to_reference convert a dict of call arrays (numpy arrays or torch tensors; other entries - ncol, nlay, the flags -
 pass through) between the two.  A float32 form rounds on the way out of the reference form and widens, exactly, on the way back.
 """
@@ -37,7 +50,7 @@ LAYER_ARRAYS = ("play", "tlay", "h2ovmr", "o3vmr", "co2vmr", "ch4vmr", "n2ovmr",
 LEVEL_ARRAYS = ("plev", "tlev", "uflx", "dflx", "uflxc", "dflxc", "duflx_dt", "duflxc_dt", "uflx_adj", "uflxc_adj")
 BAND_ARRAYS = ("emis", "plankbnd", "dplankbnd_dt")                      # (ncol, 16): no vertical axis
 LAYER_X_ARRAYS = ("tauaer", "planklay", "taug", "fracs")                # (ncol, nlay, 16 | NG)
-LEVEL_X_ARRAYS = ("planklev",)                                          # (ncol, nlay+1, 16)
+LEVEL_X_ARRAYS = ("planklev", "uflxs", "dflxs", "uflxcs", "dflxcs")      # (ncol, nlay+1, 16)
 COLUMN_ARRAYS = ("tsfc", "dtsfc")
 ALL_ARRAYS = LAYER_ARRAYS + LEVEL_ARRAYS + BAND_ARRAYS + LAYER_X_ARRAYS + LEVEL_X_ARRAYS + COLUMN_ARRAYS + ("taucld",)
 
@@ -71,7 +84,7 @@ def reference_shape(name, ncol, nlay, ng=140):
         return (ncol, nlay, NBND)
     if name in ("taug", "fracs"):
         return (ncol, nlay, ng)
-    if name == "planklev":
+    if name in LEVEL_X_ARRAYS:
         return (ncol, nlay + 1, NBND)
     if name in COLUMN_ARRAYS:
         return (ncol,)
@@ -175,14 +188,103 @@ def empty_like_form(names, ncol, nlay, form, ng=140, device=None, fill=None):
     return out
 
 
-def check_tensor(name, t, ncol, nlay, form, ng=140):
+def column_axis(name, form):
+    """the axis of the column index in the logical shape of `name`"""
+    return 1 if name == "taucld" and not ArrayForm(*form).layer_fastest else 0
+
+
+def check_ld(ncol, ld, form):
+    """The column extent in force for a view of `ncol` columns (ld = 0 or None: ncol).  ValueError for an ld the header refuses:
+    smaller than ncol, beyond 2^30, or - with layer_fastest = 1, where the column is the slowest index - anything but ncol."""
+    form = ArrayForm(*form)
+    ncol, ld = int(ncol), int(ld or 0)
+    if ld == 0:
+        return ncol
+    if ld < ncol:
+        raise ValueError(f"ld={ld} is smaller than ncol={ncol}")
+    if ld > 1 << 30:
+        raise ValueError(f"ld={ld} exceeds 2^30")
+    if form.layer_fastest and ld != ncol:
+        raise ValueError(f"ld={ld} with layer_fastest=1: the column is the slowest index there, ld must be 0 or ncol={ncol}")
+    return ld
+
+
+def field_strides(name, ncol, nlay, form, ld, ng=140):
+    """Element strides of the view (logical shape form_shape(name, ncol, ...)) of array `name` inside a column-fastest field `ld`
+    columns wide - the header's table: first index fastest, the column extent ld.  C order for a layer_fastest form."""
+    form = ArrayForm(*form)
+    shape = form_shape(name, ncol, nlay, form, ng)
+    if form.layer_fastest:
+        st, acc = [], 1
+        for n in reversed(shape):
+            st.append(acc)
+            acc *= n
+        return tuple(reversed(st))
+    ax = column_axis(name, form)
+    st, acc = [], 1
+    for k, n in enumerate(shape):
+        st.append(acc)
+        acc *= ld if k == ax and len(shape) > 1 else n
+    return tuple(st)
+
+
+def embed(a, name, form, ld, col0=0, fill=float("nan")):
+    """Lay array `a` - array `name` of a call in `form`, logical shape form_shape(name, ncol, nlay, form) (from_reference gives it) - into
+    a new field `ld` columns wide at column `col0`, every other element of the field set to `fill`.  Returns (field, view): the field
+    with its first index fastest (C order for a layer_fastest form, where ld must equal ncol and col0 be 0), and the view of the call's
+    columns inside it, which is what the device entries take with ld= (field_view)."""
+    form = ArrayForm(*form)
+    ax = column_axis(name, form)
+    shape = tuple(a.shape)
+    ncol = shape[ax]
+    ld = check_ld(ncol, ld, form)
+    if col0 < 0 or col0 + ncol > ld or (form.layer_fastest and col0 != 0):
+        raise ValueError(f"columns [{col0}, {col0 + ncol}) do not lie in a field {ld} wide")
+    fshape = shape[:ax] + (ld,) + shape[ax + 1:]
+    if _is_torch(a):
+        import torch
+        if form.layer_fastest or len(fshape) == 1:
+            field = torch.full(fshape, fill, dtype=a.dtype, device=a.device)
+        else:
+            field = torch.full(tuple(reversed(fshape)), fill, dtype=a.dtype, device=a.device).permute(*reversed(range(len(fshape))))
+    else:
+        field = np.full(fshape, fill, dtype=a.dtype, order="C" if form.layer_fastest else "F")
+    view = field_view(field, name, form, ncol, col0)
+    if _is_torch(a):
+        view.copy_(a)
+    else:
+        view[...] = a
+    return field, view
+
+
+def field_view(field, name, form, ncol, col0=0):
+    """columns [col0, col0 + ncol) of `field` (array `name` of `form`, any width): a view, nothing is copied"""
+    ax = column_axis(name, form)
+    idx = [slice(None)] * len(field.shape)
+    idx[ax] = slice(col0, col0 + ncol)
+    return field[tuple(idx)]
+
+
+def check_tensor(name, t, ncol, nlay, form, ng=140, ld=None):
     """TypeError / ValueError unless tensor `t` can be array `name` of a call in `form`: its dtype, its number of elements, and dense
-    storage (a form fixes where every element lies; a strided view does not have that layout)."""
+    storage (a form fixes where every element lies; a strided view does not have that layout).  With ld (a view call: an integer, 0 =
+    ncol) the tensor must be exactly the storage the header describes: the logical shape form_shape(name, ncol, ...) and the strides
+    field_strides(...) of columns inside a field ld wide (an index of extent 1 may stride as it likes)."""
     import torch
     form = ArrayForm(*form)
     want = torch.float64 if form.real_bytes == 8 else torch.float32
     if t.dtype != want:
         raise TypeError(f"'{name}' is {t.dtype}, the array form (real_bytes={form.real_bytes}) needs {want}")
+    if ld is not None:
+        ld = check_ld(ncol, ld, form)
+        shape = form_shape(name, ncol, nlay, form, ng)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"'{name}' has shape {tuple(t.shape)}, a view of {ncol} columns needs {tuple(shape)}")
+        st = field_strides(name, ncol, nlay, form, ld, ng)
+        for n, have, need in zip(shape, t.stride(), st):
+            if n > 1 and have != need:
+                raise ValueError(f"'{name}' has strides {tuple(t.stride())}: columns of a field ld={ld} wide have {st} (tensor too small for ld, or not such a view)")
+        return
     n = form_size(name, ncol, nlay, form, ng)
     if t.numel() != n:
         raise ValueError(f"'{name}' holds {t.numel()} elements, the array form needs {n} ({form_shape(name, ncol, nlay, form, ng)})")

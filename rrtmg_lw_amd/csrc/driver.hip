@@ -181,15 +181,18 @@ struct CallDesc {
     bool spectral = false;                        // a *_spectral entry: uflxs and dflxs are required (check_spec)
     size_t esz = 8;                               // bytes per element of the caller's HOST arrays: 4 in the *_r4 entries, whose float arrays travel in
                                                   // GcmIn / FluxOut as addresses only (nothing above the staging layer reads through them)
+    int ld = 0;                                   // the *_view entries: columns between two rows of the caller's column-fastest device arrays (0: ncol)
 };
 CallDesc real4(CallDesc d) { d.esz = 4; return d; }
 CallDesc spectral(CallDesc d) { d.spectral = true; return d; }
+CallDesc strided(CallDesc d, int ld) { d.ld = ld; return d; }
 
 // The scalars of a batch below the entry points, as CallDesc and the array structs are for a call: what is fixed for the call, and the
-// columns [col0, col0 + nb) of arrays nct columns wide that one batch takes.  Whoever knows the values names them once; run_prep,
+// columns [col0, col0 + nb) of arrays nct columns wide that one batch takes, out of the ncall columns of the call (the arrays of a *_view
+// call are wider than the call: nct = ld >= ncall, every pointer at the call's first column).  Whoever knows the values names them once; run_prep,
 // run_layer, run_sweep, run_batch and run_optics read them.
 struct Batch {
-    int nlay = 0, nct = 0;
+    int nlay = 0, nct = 0, ncall = 0;
     int mode = 0;                                 // 0 clear, 1 rtrn, 2 rtrnmr, 3 rtrnmc (McICA)
     int idrv = 0;
     int istart = 1, iend = 16;                    // only bands in [istart, iend] (the column entries)
@@ -197,11 +200,11 @@ struct Batch {
     const McIn *mc = nullptr;                     // mode 3: the sub-column arrays, or null when the sub-columns come from the generator's mask (Workspace::mask)
     int nb = 0, col0 = 0;                         // this batch
 };
-// a GCM call's batches: all bands, arrays as wide as the call
+// a GCM call's batches: all bands, arrays as wide as the call - or, in a *_view call, as its `ld` says
 Batch batch_of(const CallDesc &d, int mode, const McIn *mc = nullptr)
 {
     Batch b;
-    b.nlay = d.nlay; b.nct = d.ncol; b.mode = mode; b.idrv = d.idrv;
+    b.nlay = d.nlay; b.nct = d.ld > 0 ? d.ld : d.ncol; b.ncall = d.ncol; b.mode = mode; b.idrv = d.idrv;
     b.inflag = d.inflg; b.iceflag = d.iceflg; b.liqflag = d.liqflg; b.mc = mc;
     return b;
 }
@@ -209,7 +212,7 @@ Batch batch_of(const CallDesc &d, int mode, const McIn *mc = nullptr)
 Batch staged_batch(const CallDesc &d, int mode, int nb, const McIn *mc = nullptr)
 {
     Batch b = batch_of(d, mode, mc);
-    b.nct = b.nb = nb;
+    b.nct = b.ncall = b.nb = nb;
     return b;
 }
 
@@ -1058,6 +1061,9 @@ int ensure_pipeline()
 // of a CU's LDS and waits for the generator's work-groups to leave) - 77.5 vs 77.7 ms a step either way, also with the auxiliary stream
 // at the lowest priority.  The generator's 12.9 ms are added work, not hidden work.)
 int launch_kiss(hipStream_t s, const Workspace &Wk, int ncol, int col0, int nb, int nlay, int icld, int permuteseed, const SubcolIn &in);
+// play, cldfr and alpha of a call whose arrays are d.ld columns wide, once more d.ncol wide in the library's own memory (below, with the
+// array-form staging)
+int stage_generator_arrays(hipStream_t s, const CallDesc &d, int icld_gen, const double **play, const double **cldfr, const double **alpha);
 
 // A device-resident call of ONE batch that does not fill the chip is a chain of a dozen dependent launches on up to four streams: the
 // kernels themselves take two thirds of its time, launch gaps and cross-stream event hops the rest (profiles/round4_small_calls.md).  The
@@ -1082,7 +1088,8 @@ struct KissGen { bool on; int icld, permuteseed; const double *alpha; };      //
 int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOut &out, KissGen gen = KissGen{false, 0, 0, nullptr})
 {
     if (int rc = ensure_pipeline()) return rc;
-    const int ncol = call.nct, nlay = call.nlay, mode = call.mode, idrv = call.idrv;
+    // (ncol: the columns of the call; call.nct, the width of its arrays, only travels to the kernels)
+    const int ncol = call.ncall, nlay = call.nlay, mode = call.mode, idrv = call.idrv;
     const McIn *const mc = call.mc;
     const int nbmax = balanced_batch(ncol, eff_batch(nlay));
     // a call that is ONE batch has nothing for its per-column kernels to run beside: they go on the caller's stream, one cross-stream
@@ -1103,7 +1110,7 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
     bool capture = false;
     if (single && !split && !gen.on && !mc && !G.profile && !G.n1 && ncol <= g_graph_max) {
         std::vector<unsigned char> key;
-        key_put(key, ncol); key_put(key, nlay); key_put(key, mode); key_put(key, idrv); key_put(key, call.inflag); key_put(key, call.iceflag); key_put(key, call.liqflag);
+        key_put(key, ncol); key_put(key, call.nct); key_put(key, nlay); key_put(key, mode); key_put(key, idrv); key_put(key, call.inflag); key_put(key, call.iceflag); key_put(key, call.liqflag);
         const double *gp[] = {g.play, g.plev, g.tlay, g.tlev, g.tsfc, g.h2ovmr, g.o3vmr, g.co2vmr, g.ch4vmr, g.n2ovmr, g.o2vmr, g.cfc11vmr, g.cfc12vmr,
                               g.cfc22vmr, g.ccl4vmr, g.emis, g.cldfr, g.taucld, g.cicewp, g.cliqwp, g.reice, g.reliq, g.tauaer, g.tauctot,
                               out.uflx, out.dflx, out.hr, out.uflxc, out.dflxc, out.hrc, out.duflx_dt, out.duflxc_dt, out.fnet, out.fnetc,
@@ -1163,7 +1170,7 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
         if (j >= 2) HIP_TRY(hipStreamWaitEvent(aux, G.ev_done[kj].get(), 0));
         if (int rc = run_prep<true>(aux, Wj, bj, g, c, single && g_prep_fork ? G.aux.get() : nullptr)) return rc;
         if (gen.on) {
-            if (int rc = launch_kiss(aux, Wj, ncol, bj.col0, bj.nb, nlay, gen.icld, gen.permuteseed, SubcolIn{g.play, g.cldfr, gen.alpha})) return rc;
+            if (int rc = launch_kiss(aux, Wj, call.nct, bj.col0, bj.nb, nlay, gen.icld, gen.permuteseed, SubcolIn{g.play, g.cldfr, gen.alpha})) return rc;
         }
         if (!single) HIP_TRY(hipEventRecord(G.ev_ready[kj].get(), aux));
         return 0;
@@ -2112,7 +2119,8 @@ void launch_kiss_rule(hipStream_t s, const Workspace &Wk, const SubcolIn &in, co
     hipLaunchKernelGGL(k_subcol_kiss<RULE>, grid, block, lds, s, Wk, in, jt, jsub, ncol, col0, nb, nlay);
 }
 
-// kissvec masks of columns col0 .. col0+nb-1 (of ncol) on stream s; G.W.mask must be set up (prepare_mask)
+// kissvec masks of columns col0 .. col0+nb-1 on stream s, from play, cldfrac and alpha `ncol` columns wide (the mask has its own width,
+// Workspace::mask_stride: the columns of the call); G.W.mask must be set up (prepare_mask)
 int launch_kiss(hipStream_t s, const Workspace &Wk, int ncol, int col0, int nb, int nlay, int icld, int permuteseed, const SubcolIn &in)
 {
     if (icld < 1 || icld > 5) return fail(RRTMG_LW_HIP_EARG, "the sub-column generator needs icld 1..5");
@@ -2896,7 +2904,9 @@ int rrtmg_lw_hip_run_columns(
     int ncol, int nlay, int idrv, GCM_PARAMS,                                                                   \
     double *taug, double *fracs, double *planklay, double *planklev, double *plankbnd, double *dplankbnd_dt
 
-int rrtmg_lw_hip_gas_optics_device(OPTICS_GCM_PARAMS, void *stream)
+// the device entry on arrays `ld` columns wide (rrtmg_lw_hip_gas_optics_device: ld = ncol; the view entry's in-place form: every pointer
+// at the call's first column)
+static int gas_optics_device_ld(OPTICS_GCM_PARAMS, int ld, void *stream)
 {
     ENTRY_LOCK_FOR(play);
     if (int rc = check_common(ncol, nlay)) return rc;
@@ -2912,7 +2922,7 @@ int rrtmg_lw_hip_gas_optics_device(OPTICS_GCM_PARAMS, void *stream)
     const hipStream_t s = (hipStream_t)stream;
     if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));      // an earlier call, possibly on another stream, still owns the workspace
     Batch b;
-    b.nlay = nlay; b.nct = ncol; b.idrv = idrv;
+    b.nlay = nlay; b.nct = ld; b.ncall = ncol; b.idrv = idrv;
     for (b.col0 = 0; b.col0 < ncol; b.col0 += nbmax) {
         b.nb = std::min(nbmax, ncol - b.col0);
         if (int rc = run_optics<true>(s, b, g, ColIn{}, o)) return rc;
@@ -2920,6 +2930,10 @@ int rrtmg_lw_hip_gas_optics_device(OPTICS_GCM_PARAMS, void *stream)
     HIP_TRY(hipEventRecord(G.ev_last.get(), s));
     G.ev_last_valid = true;
     return 0;
+}
+int rrtmg_lw_hip_gas_optics_device(OPTICS_GCM_PARAMS, void *stream)
+{
+    return gas_optics_device_ld(ncol, nlay, idrv, GCM_NAMES, taug, fracs, planklay, planklev, plankbnd, dplankbnd_dt, ncol, stream);
 }
 
 // columns [c0, c1) of a host-pointer gas-optics call on the calling thread's current device state (the fan-out's worker); no lock taken
@@ -3617,7 +3631,13 @@ static int mcica_subcol_device(const CallDesc &d, const GcmIn &g, const double *
         if (*d.irng == 0) {          // kissvec: every column owns its stream -> generated batch by batch on the auxiliary stream
             if (int rc = prepare_mask(d.ncol, d.nlay, icld_gen, 0, alpha)) return rc;
             gen.on = true;
-        } else if (int rc = generate_mask(s, d.ncol, d.nlay, icld_gen, d.permuteseed, *d.irng, g.play, g.cldfr, alpha)) return rc;
+        } else {
+            // the Mersenne-Twister stream runs over the ncol columns of the call, in call order, and its kernels take arrays as wide as
+            // the call: a *_view call with a wider ld stages play, cldfr and alpha call-wide first, as the *_as entry does
+            const double *gp = g.play, *gc = g.cldfr, *ga = alpha;
+            if (d.ld > 0 && d.ld != d.ncol) { if (int rc = stage_generator_arrays(s, d, icld_gen, &gp, &gc, &ga)) return rc; }
+            if (int rc = generate_mask(s, d.ncol, d.nlay, icld_gen, d.permuteseed, *d.irng, gp, gc, ga)) return rc;
+        }
     }
     return run_pipelined(s, batch_of(d, mode), g, out, gen);
 }
@@ -3790,7 +3810,8 @@ size_t form_place(const std::vector<FormItem> &items, size_t nb, double *base, s
         }
     return off;
 }
-// one launch of k_form_in (in = true) or k_form_out over the items
+// one launch of k_form_in (in = true) or k_form_out over the items; ncol: the columns between two rows of the caller's column-fastest
+// arrays (the call's columns, or a *_view call's ld), col0: the batch's first column
 int form_launch(hipStream_t s, bool in, const rrtmg_lw_hip_array_form &f, const std::vector<FormItem> &items, const std::vector<double *> &staged,
                 size_t ncol, size_t col0, size_t nb)
 {
@@ -3838,7 +3859,7 @@ int form_check(const rrtmg_lw_hip_array_form *f, bool *plain)
 // u / uo: the caller's arrays.  Caller holds the entry lock, the workspace stands.
 int form_solve(const rrtmg_lw_hip_array_form &f, const CallDesc &d, int mode, const GcmIn &u, const FluxOut &uo, hipStream_t s)
 {
-    const size_t L = (size_t)d.nlay, ncol = (size_t)d.ncol;
+    const size_t L = (size_t)d.nlay, ncol = (size_t)d.ncol, ldu = d.ld > 0 ? (size_t)d.ld : ncol;
     const bool cloud = mode != 0;
     // with inflglw >= 1 cldprop reads taucld only through its band sum (nomcica_host_range): one staged value per cell instead of sixteen
     const bool use_tot = cloud && mode != 3 && d.inflg != 0;
@@ -3854,6 +3875,8 @@ int form_solve(const rrtmg_lw_hip_array_form &f, const CallDesc &d, int mode, co
     double *uop[NA_CALL];
     flux_pointers(uo, uop);
     for (int a = A_UFLX; a < A_UFLXS; a++) if (a < A_DUFLX_DT || d.idrv == 1) outs.push_back(form_item(uop[a], a, L));
+    // the spectral outputs of a *_view call ((., nlay+1, 16) like planklev): staged only when they are asked for
+    for (int a = A_UFLXS; a < NA_CALL; a++) if (uop[a]) outs.push_back(form_item(uop[a], a, L));
     const size_t nbmax = (size_t)balanced_batch(d.ncol, eff_batch(d.nlay));
     std::vector<double *> si, so;
     const size_t n_in = form_place(ins, nbmax, nullptr, si), n_out = form_place(outs, nbmax, nullptr, so);
@@ -3871,10 +3894,10 @@ int form_solve(const rrtmg_lw_hip_array_form &f, const CallDesc &d, int mode, co
         if (use_tot) { g.tauctot = g.taucld; g.taucld = nullptr; }
         double *op[NA_CALL] = {};
         for (size_t k = 0; k < outs.size(); k++) op[outs[k].pos] = so[k];
-        rc = form_launch(s, true, f, ins, si, ncol, col0, nb);
+        rc = form_launch(s, true, f, ins, si, ldu, col0, nb);
         G.W.mask_col0 = mode == 3 ? col0 : 0;             // staged arrays start at column 0, the mask holds the call's columns
         if (rc == 0) rc = run_batch<true>(s, staged_batch(d, mode, (int)nb), g, ColIn{}, flux_from(op));
-        if (rc == 0) rc = form_launch(s, false, f, outs, so, ncol, col0, nb);
+        if (rc == 0) rc = form_launch(s, false, f, outs, so, ldu, col0, nb);
     }
     G.W.mask_col0 = 0;
     HIP_TRY(hipEventRecord(G.ev_last.get(), s));
@@ -3898,6 +3921,7 @@ int mcica_subcol_device_as(const rrtmg_lw_hip_array_form &f, const CallDesc &d, 
 {
     ENTRY_LOCK_FOR(u.play, d.irng && *d.irng != 0);
     if (int rc = check_mcica_build()) return rc;
+    if (d.spectral) if (int rc = check_spec(uo)) return rc;
     if (!d.icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
     if (int rc = check_subcol_args(d.ncol, d.nlay, *d.icld, d.irng)) return rc;
     if (d.idrv == 1 && (!uo.duflx_dt || !uo.duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
@@ -3919,14 +3943,35 @@ int mcica_subcol_device_as(const rrtmg_lw_hip_array_form &f, const CallDesc &d, 
         form_place(gen, n, G.form_gen.as<double>(), sg);
         if (int rc = ensure_pipeline()) return rc;
         if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));
-        if (int rc = form_launch(s, true, f, gen, sg, n, 0, n)) return rc;
+        if (int rc = form_launch(s, true, f, gen, sg, d.ld > 0 ? (size_t)d.ld : n, 0, n)) return rc;
         if (int rc = generate_mask(s, d.ncol, d.nlay, icld_gen, d.permuteseed, *d.irng, sg[0], sg[1], two ? sg[2] : nullptr)) return rc;
     }
     return form_solve(f, d, mode, u, uo, s);
 }
 
-int gas_optics_device_as(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, int idrv, const GcmIn &u, const OptOut &uo, void *stream)
+// (declared in front of run_pipelined) the in-place *_view call with the Mersenne-Twister generator: G.form_gen as above, no conversion
+int stage_generator_arrays(hipStream_t s, const CallDesc &d, int icld_gen, const double **play, const double **cldfr, const double **alpha)
 {
+    const bool two = icld_gen == 4 || icld_gen == 5;
+    if (!*play || !*cldfr || (two && !*alpha)) return fail(RRTMG_LW_HIP_EARG, two && !*alpha ? "icld = 4/5 needs alpha" : "null generator input");
+    const size_t L = (size_t)d.nlay, n = (size_t)d.ncol;
+    std::vector<FormItem> gen = {form_item(*play, A_PLAY, L), form_item(*cldfr, A_CLDFR, L)};
+    if (two) gen.push_back(form_item(*alpha, A_ALPHA, L));
+    std::vector<double *> sg;
+    const size_t need = form_place(gen, n, nullptr, sg);
+    if (int rc = ensure_form(G.form_gen, need * 8)) return rc;
+    form_place(gen, n, G.form_gen.as<double>(), sg);
+    if (int rc = ensure_pipeline()) return rc;
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));
+    if (int rc = form_launch(s, true, rrtmg_lw_hip_array_form{8, 0, 0}, gen, sg, (size_t)d.ld, 0, n)) return rc;
+    *play = sg[0]; *cldfr = sg[1];
+    if (two) *alpha = sg[2];
+    return 0;
+}
+
+int gas_optics_device_as(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, int idrv, const GcmIn &u, const OptOut &uo, void *stream, int ld = 0)
+{
+    const size_t ldu = ld > 0 ? (size_t)ld : (size_t)ncol;
     ENTRY_LOCK_FOR(u.play);
     if (int rc = check_common(ncol, nlay)) return rc;
     if (int rc = check_optics(idrv, uo)) return rc;
@@ -3961,11 +4006,11 @@ int gas_optics_device_as(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, i
         for (size_t k = 0; k < ins.size(); k++) sp[ins[k].pos] = si[k];
         double *op[6] = {};
         for (size_t k = 0; k < outs.size(); k++) op[outs[k].pos] = so[k];
-        rc = form_launch(s, true, f, ins, si, (size_t)ncol, col0, nb);
+        rc = form_launch(s, true, f, ins, si, ldu, col0, nb);
         Batch b;
         b.nlay = nlay; b.nct = b.nb = (int)nb; b.idrv = idrv;
         if (rc == 0) rc = run_optics<true>(s, b, gcm_from(sp), ColIn{}, OptOut{op[0], op[1], op[2], op[3], op[4], op[5]});
-        if (rc == 0) rc = form_launch(s, false, f, outs, so, (size_t)ncol, col0, nb);
+        if (rc == 0) rc = form_launch(s, false, f, outs, so, ldu, col0, nb);
     }
     HIP_TRY(hipEventRecord(G.ev_last.get(), s));
     G.ev_last_valid = true;
@@ -3978,7 +4023,7 @@ struct AdjustIn { const void *plev, *dtsfc, *uflx, *dflx, *duflx_dt, *uflxc, *df
 struct AdjustOut { void *uflx_adj, *hr_adj, *uflxc_adj, *hrc_adj; };
 
 // what the three entries check before anything is enqueued; *clear: the clear-sky set is there
-int check_adjust(int ncol, int nlay, int real_bytes, const AdjustIn &in, const AdjustOut &o, bool *clear)
+int check_adjust(int ncol, int nlay, int real_bytes, const AdjustIn &in, const AdjustOut &o, bool *clear, int ld = 0)
 {
     if (int rc = check_common(ncol, nlay)) return rc;
     if (!in.plev || !in.dtsfc || !in.uflx || !in.dflx || !in.duflx_dt) return fail(RRTMG_LW_HIP_EARG, "adjust_tsfc: null input array");
@@ -3988,7 +4033,9 @@ int check_adjust(int ncol, int nlay, int real_bytes, const AdjustIn &in, const A
         return fail(RRTMG_LW_HIP_EARG, "adjust_tsfc: uflxc, dflxc, duflxc_dt, uflxc_adj and hrc_adj must be all null or all set (%d of 5 are set)", nc);
     *clear = nc == 5;
     // no output may share a byte with an input or with another output
-    const size_t n = (size_t)ncol, lev = n * ((size_t)nlay + 1) * (size_t)real_bytes, lay = n * (size_t)nlay * (size_t)real_bytes;
+    // (an array of R rows ld columns apart reaches from the call's first column to its last one in row R - 1)
+    const size_t n = (size_t)ncol, w = ld > 0 ? (size_t)ld : n;
+    const size_t lev = (w * (size_t)nlay + n) * (size_t)real_bytes, lay = (w * ((size_t)nlay - 1) + n) * (size_t)real_bytes;
     struct Range { const char *name; const void *p; size_t bytes; };
     const Range ins[] = {{"plev", in.plev, lev}, {"dtsfc", in.dtsfc, n * (size_t)real_bytes}, {"uflx", in.uflx, lev}, {"dflx", in.dflx, lev},
                          {"duflx_dt", in.duflx_dt, lev}, {"uflxc", in.uflxc, lev}, {"dflxc", in.dflxc, lev}, {"duflxc_dt", in.duflxc_dt, lev}};
@@ -4016,9 +4063,10 @@ void adjust_launch_form(hipStream_t s, bool layer_fastest, const AdjustArgs &a, 
         LAUNCH("k_adjust_lf", (k_adjust_lf<R, TOP, NS>), dim3((unsigned)((threads + 255) / 256)), dim3(256), s, a);
         return;
     }
-    // 16-byte accesses where every row of every array starts on a 16-byte boundary
+    // 16-byte accesses where every row of every array starts on a 16-byte boundary: the first one does (aligned) and the rows lie a
+    // multiple of 16 bytes apart; a call of a *_view entry at an odd column of a field, or with an odd ld, takes the narrow variant
     constexpr size_t V = 16 / sizeof(R);
-    const bool wide = aligned && n % V == 0;
+    const bool wide = aligned && n % V == 0 && (size_t)a.ld % V == 0;
     const size_t threads = wide ? n / V : n;
     // a small call is spread over the chip along the vertical: chunks of at least 8 layers until ~2^18 threads run
     AdjustArgs b = a;
@@ -4028,14 +4076,14 @@ void adjust_launch_form(hipStream_t s, bool layer_fastest, const AdjustArgs &a, 
     else LAUNCH("k_adjust_cf", (k_adjust_cf<R, 1, TOP, NS>), grid, dim3(256), s, b);
 }
 
-// one launch over ncol columns of arrays that are ncol columns wide, in the form f, on stream s
-int adjust_launch(hipStream_t s, const rrtmg_lw_hip_array_form &f, int ncol, int nlay, const AdjustIn &in, const AdjustOut &o, bool clear)
+// one launch over ncol columns of arrays that are ncol columns wide - column-fastest ones `ld` columns where ld > 0 -, in the form f, on stream s
+int adjust_launch(hipStream_t s, const rrtmg_lw_hip_array_form &f, int ncol, int nlay, const AdjustIn &in, const AdjustOut &o, bool clear, int ld = 0)
 {
     AdjustArgs a{};
     a.plev = in.plev; a.dtsfc = in.dtsfc;
     a.s[0] = AdjustSet{in.uflx, in.dflx, in.duflx_dt, o.uflx_adj, o.hr_adj};
     if (clear) a.s[1] = AdjustSet{in.uflxc, in.dflxc, in.duflxc_dt, o.uflxc_adj, o.hrc_adj};
-    a.ncol = (unsigned long long)ncol; a.nlay = nlay; a.chunk = nlay;
+    a.ncol = (unsigned long long)ncol; a.ld = (unsigned long long)(ld > 0 ? ld : ncol); a.nlay = nlay; a.chunk = nlay;
     a.heatfac = G.H.heatfac;
     // column-fastest: rows of ncol values (hr too), the wide path also asks ncol to be a multiple of the vector; layer-fastest: the
     // level arrays as one run from their first byte (dtsfc and hr are accessed value by value)
@@ -4056,12 +4104,12 @@ int adjust_launch(hipStream_t s, const rrtmg_lw_hip_array_form &f, int ncol, int
     return 0;
 }
 
-int adjust_device(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, const AdjustIn &in, const AdjustOut &o, void *stream)
+int adjust_device(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, const AdjustIn &in, const AdjustOut &o, void *stream, int ld = 0)
 {
     ENTRY_LOCK_FOR(in.plev);
     bool clear = false;
-    if (int rc = check_adjust(ncol, nlay, f.real_bytes, in, o, &clear)) return rc;
-    return adjust_launch((hipStream_t)stream, f, ncol, nlay, in, o, clear);
+    if (int rc = check_adjust(ncol, nlay, f.real_bytes, in, o, &clear, ld)) return rc;
+    return adjust_launch((hipStream_t)stream, f, ncol, nlay, in, o, clear, ld);
 }
 
 // columns [c0, c1) of a host-pointer call on the calling thread's current device state (the fan-out's worker); no lock taken
@@ -4174,6 +4222,98 @@ int rrtmg_lw_hip_gas_optics_device_as(const rrtmg_lw_hip_array_form *form, int n
                                                      (double *)planklev, (double *)plankbnd, (double *)dplankbnd_dt, stream);
     return gas_optics_device_as(*form, ncol, nlay, idrv, {GCM_NAMES_AS},
                                 OptOut{(double *)taug, (double *)fracs, (double *)planklay, (double *)planklev, (double *)plankbnd, (double *)dplankbnd_dt}, stream);
+}
+
+}  // extern "C"
+
+// ---- device arrays with a column stride (rrtmg_lw_hip_*_view) ---------------------------------------------------------------------------
+// The *_as entries' forms plus `ld`: the call's ncol columns lie inside column-fastest arrays ld columns wide, every pointer at the call's
+// first column.  Below the entries ld is Batch::nct - the kernels have always taken the batch as (col0, nb) inside arrays nct wide - and
+// the call's own column count travels beside it (Batch::ncall; CallDesc::ld above).  The form {8, 0, 0} runs on the caller's arrays in
+// place (nomcica_device / mcica_subcol_device / gas_optics_device_ld / adjust_launch with the stride); a converting form goes through
+// the *_as staging, whose two kernels take ld as the width of the caller's arrays (FormTable::ncol).
+namespace {
+
+constexpr int VIEW_LD_MAX = 1 << 30;          // (include/rrtmg_lw_hip.h: the largest ld)
+
+// what the four entries check first, before any lock is held or anything is launched; *f: the form, *ld: the width in force (ncol for
+// 0), *plain: the form {8, 0, 0}
+int view_check(const rrtmg_lw_hip_array_view *v, int ncol, rrtmg_lw_hip_array_form *f, int *ld, bool *plain)
+{
+    if (!v) { ENTRY_LOCK; return fail(RRTMG_LW_HIP_EARG, "array view is null"); }
+    *f = rrtmg_lw_hip_array_form{v->real_bytes, v->layer_fastest, v->top_first};
+    if (int rc = form_check(f, plain)) return rc;
+    *ld = v->ld == 0 ? ncol : v->ld;
+    if (ncol < 1) return 0;                     // (refused as a bad dimension by the entry's own checks)
+    const char *bad = v->ld < 0 || *ld < ncol ? "array view: ld is smaller than ncol"
+                    : *ld > VIEW_LD_MAX ? "array view: ld exceeds 2^30"
+                    : (v->layer_fastest && *ld != ncol) ? "array view: with layer_fastest = 1 the column is the slowest index - ld must be 0 or ncol" : nullptr;
+    if (bad) { ENTRY_LOCK; return fail(RRTMG_LW_HIP_EARG, "%s (ld=%d, ncol=%d)", bad, v->ld, ncol); }
+    return 0;
+}
+
+}   // namespace
+
+extern "C" {
+
+#define SPEC_PARAMS_AS void *uflxs, void *dflxs, void *uflxcs, void *dflxcs
+#define SPEC_NAMES_AS nullptr, nullptr, (double *)uflxs, (double *)dflxs, (double *)uflxcs, (double *)dflxcs
+
+int rrtmg_lw_hip_run_nomcica_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, int *icld, int idrv, GCM_PARAMS_AS,
+    int inflglw, int iceflglw, int liqflglw, CLOUD_PARAMS_AS, const void *tauaer, OUT_PARAMS_AS, SPEC_PARAMS_AS, void *stream)
+{
+    rrtmg_lw_hip_array_form f;
+    int ld = 0;
+    bool plain = false;
+    if (int rc = view_check(view, ncol, &f, &ld, &plain)) return rc;
+    CallDesc d{ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw};
+    d.spectral = uflxs || dflxs || uflxcs || dflxcs;
+    d.ld = ld;
+    const GcmIn g{GCM_NAMES_AS, CLOUD_NAMES_AS, AS_(tauaer)};
+    const FluxOut out{OUT_NAMES_AS, SPEC_NAMES_AS};
+    if (plain) return nomcica_device(d, g, out, stream);          // (ld = ncol: what the plain / spectral device entry does)
+    return nomcica_device_as(f, d, g, out, stream);
+}
+
+int rrtmg_lw_hip_run_mcica_subcol_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng,
+    GCM_PARAMS_AS, int inflglw, int iceflglw, int liqflglw, CLOUD_PARAMS_AS, const void *alpha, const void *tauaer, OUT_PARAMS_AS, SPEC_PARAMS_AS,
+    void *stream)
+{
+    rrtmg_lw_hip_array_form f;
+    int ld = 0;
+    bool plain = false;
+    if (int rc = view_check(view, ncol, &f, &ld, &plain)) return rc;
+    CallDesc d{ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng};
+    d.spectral = uflxs || dflxs || uflxcs || dflxcs;
+    d.ld = ld;
+    const GcmIn g{GCM_NAMES_AS, CLOUD_NAMES_AS, AS_(tauaer)};
+    const FluxOut out{OUT_NAMES_AS, SPEC_NAMES_AS};
+    if (plain) return mcica_subcol_device(d, g, AS_(alpha), out, stream);
+    return mcica_subcol_device_as(f, d, g, alpha, out, stream);
+}
+
+int rrtmg_lw_hip_gas_optics_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, int idrv, GCM_PARAMS_AS,
+    void *taug, void *fracs, void *planklay, void *planklev, void *plankbnd, void *dplankbnd_dt, void *stream)
+{
+    rrtmg_lw_hip_array_form f;
+    int ld = 0;
+    bool plain = false;
+    if (int rc = view_check(view, ncol, &f, &ld, &plain)) return rc;
+    if (plain) return gas_optics_device_ld(ncol, nlay, idrv, GCM_NAMES_AS, (double *)taug, (double *)fracs, (double *)planklay, (double *)planklev,
+                                           (double *)plankbnd, (double *)dplankbnd_dt, ld, stream);
+    return gas_optics_device_as(f, ncol, nlay, idrv, {GCM_NAMES_AS},
+                                OptOut{(double *)taug, (double *)fracs, (double *)planklay, (double *)planklev, (double *)plankbnd, (double *)dplankbnd_dt}, stream, ld);
+}
+
+int rrtmg_lw_hip_adjust_tsfc_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, const void *plev, const void *dtsfc,
+    const void *uflx, const void *dflx, const void *duflx_dt, const void *uflxc, const void *dflxc, const void *duflxc_dt,
+    void *uflx_adj, void *hr_adj, void *uflxc_adj, void *hrc_adj, void *stream)
+{
+    rrtmg_lw_hip_array_form f;
+    int ld = 0;
+    bool plain = false;
+    if (int rc = view_check(view, ncol, &f, &ld, &plain)) return rc;
+    return adjust_device(f, ncol, nlay, {plev, dtsfc, uflx, dflx, duflx_dt, uflxc, dflxc, duflxc_dt}, {uflx_adj, hr_adj, uflxc_adj, hrc_adj}, stream, ld);
 }
 
 }  // extern "C"

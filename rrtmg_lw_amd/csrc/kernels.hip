@@ -4349,8 +4349,8 @@ __global__ __launch_bounds__(256) void k_calibrate(const double2 *__restrict__ i
 //               in float64 on float64 or widened float32 arrays, total sky and (NS = 2) clear sky.  Nothing but traffic - 6.4 KB per
 //               72-layer column -, so the kernels read and write the caller's arrays where they lie, in the caller's form (R: element
 //               type, TOP: vertical index 0 at the top of the atmosphere), every element once, lanes along the form's fastest index.
-//   k_adjust_cf   columns fastest.  A thread owns V consecutive columns (V x sizeof(R) = 16 bytes per access where every row of every
-//               array is 16-byte aligned, V = 1 otherwise) and walks the levels of its chunk (blockIdx.y) upward with the net flux and
+//   k_adjust_cf   columns fastest, rows a.ld columns apart.  A thread owns V consecutive columns (V x sizeof(R) = 16 bytes per access where
+//               every row of every array is 16-byte aligned - the first one is and both ncol and ld are multiples of V -, V = 1 otherwise) and walks the levels of its chunk (blockIdx.y) upward with the net flux and
 //               pressure of the level below in registers.  A chunk reads the level it ends at once more; the level belongs to the next
 //               chunk, which stores its u'.  The chunks only spread a small call over the chip: a large one walks whole columns.
 //   k_adjust_lf   levels fastest: the (ncol, nlay+1) arrays are walked as ONE run of ncol x (nlay+1) values, V per thread, whatever
@@ -4362,7 +4362,8 @@ struct AdjustSet { const void *u, *d, *du; void *ua, *hr; };
 struct AdjustArgs {
     const void *plev, *dtsfc;
     AdjustSet s[2];             // total sky, clear sky
-    unsigned long long ncol;    // columns, and the row length of column-fastest arrays
+    unsigned long long ncol;    // columns of the call
+    unsigned long long ld;      // k_adjust_cf: columns between two rows of the arrays (ncol, or the wider field's of a *_view call)
     int nlay, chunk;            // chunk: layers per blockIdx.y (k_adjust_cf)
     int vec;                    // k_adjust_lf: every level array starts on a 16-byte boundary
     double heatfac;
@@ -4403,14 +4404,14 @@ template <class R, int V, bool TOP, int NS>
 __global__ __launch_bounds__(256) void k_adjust_cf(AdjustArgs a)
 {
 #pragma clang fp contract(off)
-    const size_t n = (size_t)a.ncol, c = ((size_t)blockIdx.x * 256 + threadIdx.x) * V;
+    const size_t n = (size_t)a.ncol, ld = (size_t)a.ld, c = ((size_t)blockIdx.x * 256 + threadIdx.x) * V;
     if (c >= n) return;
     const int nlay = a.nlay, k0 = (int)blockIdx.y * a.chunk, k1 = min(nlay, k0 + a.chunk);
     double dt[V], pb[V], nb[NS][V];         // dtsfc; pressure and net fluxes of the level below
     adjust_load<R, V>(a.dtsfc, c, dt);
 #pragma unroll 2
     for (int k = k0; k <= k1; k++) {
-        const size_t at = (size_t)(TOP ? nlay - k : k) * n + c;
+        const size_t at = (size_t)(TOP ? nlay - k : k) * ld + c;
         const bool mine = k < k1 || k1 == nlay;          // (the chunk's last level is the next chunk's first)
         double p[V], net[NS][V];
         adjust_load<R, V>(a.plev, at, p);
@@ -4425,7 +4426,7 @@ __global__ __launch_bounds__(256) void k_adjust_cf(AdjustArgs a)
             if (mine) adjust_store<R, V>(a.s[s].ua, at, u);
         }
         if (k > k0) {
-            const size_t ah = (size_t)(TOP ? nlay - k : k - 1) * n + c;          // layer k - 1
+            const size_t ah = (size_t)(TOP ? nlay - k : k - 1) * ld + c;         // layer k - 1
 #pragma unroll
             for (int s = 0; s < NS; s++) {
                 double h[V];

@@ -174,8 +174,8 @@ int rrtmg_lw_hip_get_alpha(int ncol, int nlay, int icld, int idcor, double decor
  * exponential-random overlap (alpha may be NULL unless icld is 4 or 5); icld 0 returns without touching the
  * outputs.  irng is in/out (any non-zero value becomes 1): 0 = kissvec, one stream per column seeded from
  * its four lowest layer pressures; 1 = one Mersenne-Twister stream seeded with permuteseed, consumed in
- * (sub-column, column, layer) order.  kissvec: 4 <= nlay <= 603 (modules/parrrtm.f90:31; the column driver's mxlay is 203); a permuteseed that differs
- * from the previous call's rebuilds a small jump-ahead table on the host (one device synchronisation). */
+ * (sub-column, column, layer) order.  kissvec: 4 <= nlay <= 603 (modules/parrrtm.f90:31; the column driver's mxlay is 203); a permuteseed the library
+ * has not seen builds a small jump-ahead table on the host; the tables of the last 128 seeds are kept. */
 int rrtmg_lw_hip_mcica_subcol(
     int ncol, int nlay, int icld, int permuteseed, int *irng, const double *play, const double *cldfrac, const double *ciwp,
     const double *clwp, const double *rei, const double *rel, const double *tauc, const double *alpha,
@@ -215,6 +215,65 @@ int rrtmg_lw_hip_run_mcica_subcol_device(
     const double *reice, const double *reliq, const double *alpha, const double *tauaer,
     double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
     double *duflx_dt, double *duflxc_dt, void *stream);
+
+/* The mean over several sub-column samples ---------------------------------------------------------- */
+/* One call of the fused entry returns the fluxes of ONE set of sub-columns; the reference's column driver averages 200 of them
+ * (src/rrtmg_lw.1col.f90:457-480, :641-660).  These two entries do that at GCM width.  Their argument lists are those of
+ * rrtmg_lw_hip_run_mcica_subcol / _device with `nsamp, seedstep` behind permuteseed.  With X_s what that entry returns in output X when
+ * called with permuteseed + s * seedstep, s = 0 .. nsamp-1:
+ *     uflx, dflx, hr, duflx_dt       (((X_0 + X_1) + X_2) + ... + X_{nsamp-1}) / nsamp: the float64 sum in sample order, then ONE IEEE
+ *                                    division (not a multiplication by a reciprocal) - bit for bit what a caller gets who runs the
+ *                                    nsamp calls and averages in that order
+ *     uflxc, dflxc, hrc, duflxc_dt   X_0 itself: the clear-sky stream does not depend on the sample and is written once
+ * seedstep: the generator skips `permuteseed` draws of every column's stream (src/mcica_subcol_gen_lw.f90:472-474) and asks callers to
+ * offset seeds by the number of sub-columns (:193-196, :262), so rrtmg_lw_hip_gpoints() - 140, 256 in the g256 build - is the documented
+ * choice.  nsamp = 1 is rrtmg_lw_hip_run_mcica_subcol[_device]; *icld = 0 draws nothing and returns that single call's outputs whatever
+ * nsamp is.  icld is in/out and reset as the fused entry does it; optional outputs keep its NULL rules (duflx_dt, duflxc_dt with idrv = 1).
+ * RRTMG_LW_HIP_EARG, with a text that names the argument and before any output is written: nsamp < 1, nsamp > RRTMG_LW_HIP_MAX_SAMPLES,
+ * seedstep < 1, permuteseed + (nsamp-1) * seedstep not an int, *irng != 0 together with nsamp > 1 (the Mersenne-Twister stream is out of
+ * scope: its chunk-state cache holds two seeds).  A physics error in any sample is reported as the single call reports it - by the
+ * device entry through rrtmg_lw_hip_check(stream).
+ * The device entry enqueues on `stream` and does not synchronise; in steady state - the same (permuteseed, seedstep, nsamp, nlay, icld)
+ * as an earlier call since initialisation - that includes the generator's jump tables, which are kept per (draws per sub-column, seed)
+ * in a set of 128 - larger than RRTMG_LW_HIP_MAX_SAMPLES - so that a single-seed call between two averaging calls rebuilds nothing either;
+ * once 128 pairs have been seen a new one replaces the pair used longest ago, after one device synchronisation
+ * (rrtmg_lw_hip_kiss_tables_built counts the tables built).  It never reads the output arrays before it has written them.  The host
+ * entry takes the entry lock like any other call, does not join the combining of concurrent small calls, and keeps the whole call's
+ * arrays on the device while it runs (the samples add up there): about 0.5 KB per column and layer beside the workspace, allocated
+ * for the call and not counted by rrtmg_lw_hip_workspace_bytes - a call too large for that is made in column blocks by the caller.
+ * What the samples share: the argument checks, the workspace, the jump tables, the clear-sky outputs (stored by sample 0 only), the
+ * averaging, which k_flux does as it stores (sample 0 stores, the others add, the last one adds and divides: no pass over the outputs
+ * of its own), and the gas optics: per batch of columns k_layer runs once, with the first sample, and leaves the cells' float64 optical
+ * depths in the workspace; the total codes of a later sample's cloudy layers are formed from them by a small kernel (k_codet) with
+ * k_layer's expressions.  The workspace holds those optical depths in the arrays the McICA entry with sub-column arrays uses (1.2 KB per
+ * column and layer, and as much again for that entry's emissivity array, which comes with it: the workspace of a call of that entry).  Every sample still runs the per-column kernels, the generator, the
+ * cloud optics and all sweeps, the clear-sky ones included.
+ * nsamp = 1 and *icld = 0 through the host entry ARE rrtmg_lw_hip_run_mcica_subcol behind the entry lock - its fan-out over several
+ * initialised devices included; with nsamp > 1 and cloud the host entry runs on the first device.
+ * Not offered: *_as, *_view, *_r4 and *_spectral variants, fan-out over several devices, per-sample or variance outputs. */
+#define RRTMG_LW_HIP_MAX_SAMPLES 64
+int rrtmg_lw_hip_run_mcica_samples(
+    int ncol, int nlay, int *icld, int idrv, int permuteseed, int nsamp, int seedstep, int *irng,
+    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
+    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
+    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
+    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
+    const double *reice, const double *reliq, const double *alpha, const double *tauaer,
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
+    double *duflx_dt, double *duflxc_dt);
+int rrtmg_lw_hip_run_mcica_samples_device(
+    int ncol, int nlay, int *icld, int idrv, int permuteseed, int nsamp, int seedstep, int *irng,
+    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
+    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
+    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
+    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
+    const double *reice, const double *reliq, const double *alpha, const double *tauaer,
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
+    double *duflx_dt, double *duflxc_dt, void *stream);
+/* jump tables of the kissvec generator built since the library was loaded (a counter, like rrtmg_lw_hip_graph_stats) */
+long long rrtmg_lw_hip_kiss_tables_built(void);
 
 /* Spectral (per-band) fluxes --------------------------------------------------------------------- */
 /* The six entries below take the argument list of the entry they are named after, followed by four more outputs (in the device entries

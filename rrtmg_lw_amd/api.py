@@ -210,6 +210,27 @@ def graph_stats():
     return int(a.value), int(b.value)
 
 
+def kiss_tables_built():
+    """jump tables of the kissvec generator built so far (rrtmg_lw_hip_kiss_tables_built): does not move in steady state"""
+    fn = lib().rrtmg_lw_hip_kiss_tables_built
+    fn.restype = C.c_longlong
+    return int(fn())
+
+
+def _samples(nsamp, seedstep, **refused):
+    """The sample count and seed step of a fused McICA call (include/rrtmg_lw_hip.h, "The mean over several sub-column samples"):
+    -> (nsamp, seedstep) as ints, seedstep=None the sub-columns of a sample.  The averaging entries exist for float64 reference-form
+    arrays only: with nsamp > 1 any of `refused` that is set raises ValueError, before the library is touched."""
+    nsamp = int(nsamp)
+    if nsamp > 1:
+        for name, value in refused.items():
+            if value is not None and value is not False:
+                raise ValueError(f"nsamp = {nsamp}: the mean over several samples is not available with {name}")
+    if nsamp == 1:
+        return 1, 0                  # (the existing entries: they take no seedstep)
+    return nsamp, (gpoints() if seedstep is None else int(seedstep))
+
+
 def set_wide_window(on):
     """k_layer's second pass with the wide staging window for workgroups whose columns lie more than one reference-pressure plane apart
     (rrtmg_lw_hip_set_wide_window); returns the previous on / off"""
@@ -755,10 +776,14 @@ def mcica_subcol_lw(ncol, nlay, icld, permuteseed, irng, play, cldfrac, ciwp, cl
 
 def rrtmg_lw_mcica_subcol(ncol, nlay, icld, idrv, permuteseed, irng, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr,
                           ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw,
-                          cldfr, taucld, cicewp, cliqwp, reice, reliq, alpha, tauaer, spectral=False, out=None, dtype=None):
+                          cldfr, taucld, cicewp, cliqwp, reice, reliq, alpha, tauaer, spectral=False, out=None, dtype=None,
+                          nsamp=1, seedstep=None):
     """mcica_subcol_lw followed by the McICA rrtmg_lw in one call; the sub-columns stay on the device as bit masks.
     spectral=True: the fluxes per band as well (see rrtmg_lw); `out`: a dict of preallocated spectral outputs to fill.
-    dtype=np.float32: float32 arrays in and out, alpha too (rrtmg_lw_hip_run_mcica_subcol_r4; _real)."""
+    dtype=np.float32: float32 arrays in and out, alpha too (rrtmg_lw_hip_run_mcica_subcol_r4; _real).
+    nsamp > 1: the mean of the total-sky outputs over nsamp samples drawn with permuteseed + s * seedstep (seedstep=None: gpoints()),
+    summed in float64 in sample order and divided once; clear-sky outputs are sample 0's (rrtmg_lw_hip_run_mcica_samples)."""
+    nsamp, seedstep = _samples(nsamp, seedstep, **{"spectral=True": spectral, "a float32 dtype": dtype is not None and np.dtype(dtype) == np.float32})
     dt = _real(dtype, spectral)
     a = _gcm_arrays(ncol, nlay, play, plev, tlay, tlev, tsfc,
                     (h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr), emis, dt)
@@ -769,8 +794,12 @@ def rrtmg_lw_mcica_subcol(ncol, nlay, icld, idrv, permuteseed, irng, play, plev,
     out = dict(out or {}, **_out_arrays(ncol, nlay, idrv, dt))
     icld_c, irng_c = C.c_int(int(icld)), C.c_int(int(irng))
     args = [C.c_int(ncol), C.c_int(nlay), C.byref(icld_c), C.c_int(int(idrv)), C.c_int(int(permuteseed)), C.byref(irng_c)]
+    if nsamp != 1:
+        args[5:5] = [C.c_int(nsamp), C.c_int(seedstep)]
     args += [_p(x) for x in a] + [C.c_int(int(inflglw)), C.c_int(int(iceflglw)), C.c_int(int(liqflglw))] + cld + _out_ptrs(out, idrv)
-    if spectral:
+    if nsamp != 1:
+        _check(lib().rrtmg_lw_hip_run_mcica_samples(*args))
+    elif spectral:
         _check(lib().rrtmg_lw_hip_run_mcica_subcol_spectral(*args, *_spec_ptrs(out, ncol, nlay)))
     elif dt == np.float32:
         _check(lib().rrtmg_lw_hip_run_mcica_subcol_r4(*args))
@@ -781,17 +810,22 @@ def rrtmg_lw_mcica_subcol(ncol, nlay, icld, idrv, permuteseed, irng, play, plev,
     return out
 
 
-def rrtmg_lw_mcica_subcol_from_dict(d, permuteseed, irng, alpha=None, icld=None, idrv=None, spectral=False, out=None, dtype=None):
+def rrtmg_lw_mcica_subcol_from_dict(d, permuteseed, irng, alpha=None, icld=None, idrv=None, spectral=False, out=None, dtype=None,
+                                    nsamp=1, seedstep=None):
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     return rrtmg_lw_mcica_subcol(d["ncol"], d["nlay"], icld, idrv, permuteseed, irng, *[d[k] for k in _GCM_ORDER], d["inflglw"],
                                  d["iceflglw"], d["liqflglw"], d["cldfr"], d["taucld"], d["cicewp"], d["cliqwp"], d["reice"],
-                                 d["reliq"], alpha, d["tauaer"], spectral=spectral, out=out, dtype=dtype)
+                                 d["reliq"], alpha, d["tauaer"], spectral=spectral, out=out, dtype=dtype, nsamp=nsamp, seedstep=seedstep)
 
 
-def rrtmg_lw_mcica_subcol_device(d, out, permuteseed, irng, alpha=None, icld=None, idrv=None, stream=None, form=None, ld=None):
+def rrtmg_lw_mcica_subcol_device(d, out, permuteseed, irng, alpha=None, icld=None, idrv=None, stream=None, form=None, ld=None,
+                                 nsamp=1, seedstep=None):
     """Device-resident fused generator + solver (torch CUDA tensors, column-fastest); see rrtmg_lw_device (`form` and `ld` as there:
-    `alpha` lies in that form, and is such a view, as well; ld goes to rrtmg_lw_hip_run_mcica_subcol_device_view)."""
+    `alpha` lies in that form, and is such a view, as well; ld goes to rrtmg_lw_hip_run_mcica_subcol_device_view).
+    nsamp, seedstep: as in rrtmg_lw_mcica_subcol (rrtmg_lw_hip_run_mcica_samples_device: float64 reference-form tensors only)."""
+    nsamp, seedstep = _samples(nsamp, seedstep, **{"form=": form, "ld=": ld, "spectral outputs": "uflxs" in out,
+                                                   "float32 tensors": str(getattr(out.get("uflx"), "dtype", "")).endswith("float32")})
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     icld_c, irng_c = C.c_int(int(icld)), C.c_int(int(irng))
@@ -821,6 +855,10 @@ def rrtmg_lw_mcica_subcol_device(d, out, permuteseed, irng, alpha=None, icld=Non
         _check(lib().rrtmg_lw_hip_run_mcica_subcol_spectral_device(*args, *_spec_dev(out), C.c_void_p(stream or 0)))
         return icld_c.value
     args.append(C.c_void_p(stream or 0))
+    if nsamp != 1:
+        args[5:5] = [C.c_int(nsamp), C.c_int(seedstep)]
+        _check(lib().rrtmg_lw_hip_run_mcica_samples_device(*args))
+        return icld_c.value
     if form is not None:
         _check(lib().rrtmg_lw_hip_run_mcica_subcol_device_as(*args))
         return icld_c.value

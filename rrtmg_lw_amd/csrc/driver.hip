@@ -65,7 +65,12 @@ using Event = owned::Owned<EventTraits>;
 using Graph = owned::Owned<GraphTraits>;
 using GraphExec = owned::Owned<GraphExecTraits>;
 
-struct KissTable { unsigned long long stride = 0; long long seed = -1; KissJump host[KJ_NGROUP + 1]; DevBuf dev; };
+// the kissvec generator's jump tables on a device: one slot per (draws per sub-column, permuteseed) pair, the slots in one allocation made
+// at the first use.  More slots than a call can have samples (RRTMG_LW_HIP_MAX_SAMPLES), so that the seeds of an averaging call and the
+// single seed of a call made between two of them all stay.
+constexpr int KISS_SLOTS = 2 * RRTMG_LW_HIP_MAX_SAMPLES;
+struct KissSlot { unsigned long long stride = 0; long long seed = -1; unsigned long long used = 0; };
+struct KissTable { std::vector<KissSlot> slot; unsigned long long clock = 0; DevBuf dev; PinnedBuf host; };      // host: the tables as built, page-locked (they are copied asynchronously)
 
 // Columns per internal batch when the caller has not chosen (rrtmg_lw_hip_set_batch(0) comes back to this): 262 144 at up to 96 layers,
 // the next lower power of two of 262 144 x 72 / nlay above (131 072 at 137 layers) - the workspace grows with the layers, the step
@@ -139,7 +144,7 @@ struct State {
     // the tables of k_widen_rows (float32 input rows that have landed) and k_narrow_rows (the active output rows)
     struct HostSet { PinnedBuf in, out, fill, widen, narrow; } hset[HOST_SETS];
     Event ev_h2d[HOST_SETS], ev_cmp[HOST_SETS], ev_d2h[HOST_SETS];
-    KissTable kiss;             // the kissvec generator's jump table of the last (draws per sub-column, permuteseed) pair, on this device
+    KissTable kiss;             // the kissvec generator's jump tables of the last KISS_SLOTS (draws per sub-column, permuteseed) pairs, on this device
     std::string err;
     // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg)
     bool profile = false;
@@ -199,6 +204,9 @@ struct Batch {
     int inflag = 0, iceflag = 0, liqflag = 0;
     const McIn *mc = nullptr;                     // mode 3: the sub-column arrays, or null when the sub-columns come from the generator's mask (Workspace::mask)
     int nb = 0, col0 = 0;                         // this batch
+    int acc = 0, nsamp = 1;                       // a sample of a call that averages nsamp of them (run_samples): 0 k_flux stores, 1 adds, 2 adds and divides
+    int share = 0;                                // ... 1: k_layer leaves the cells' float64 optical depths in W.odg (the first sample), 2: k_codet forms the
+                                                  // sample's total codes from them and k_layer does not run (a later sample of the same batch)
 };
 // a GCM call's batches: all bands, arrays as wide as the call - or, in a *_view call, as its `ld` says
 Batch batch_of(const CallDesc &d, int mode, const McIn *mc = nullptr)
@@ -844,6 +852,18 @@ int run_layer(hipStream_t s, const Workspace &Wk, const Batch &b, const GcmIn &g
     const dim3 wgrid(gx * b.nlay, la.nparts);
     // (the list's count: cleared on the stream in front of the narrow launch - a memset node when the call is captured as a graph)
     if (Wn.wide) HIP_TRY(hipMemsetAsync(Wn.wide, 0, sizeof(int), s));
+    if (b.share != 0) {         // an averaging call (run_samples): the gas optics of a batch once, a sample's total codes from them
+        if constexpr (GCM && !TUNING) {
+            if (b.mode != 3 || b.mc || !Wk.odg) return fail(RRTMG_LW_HIP_EARG, "internal: shared gas optics without the mask or the optical-depth array");
+            if (b.share == 1) {
+                LAUNCH("k_layer<mcshare,0>", (k_layer<true, CL_SHARE, 0>), lgrid, lblock, s, G.D, Wn, g, c, la);
+                if (Wn.wide) LAUNCH("k_layer<mcshare,1>", (k_layer<true, CL_SHARE, 1>), wgrid, lblock, s, G.D, Wn, g, c, la);
+            } else {
+                LAUNCH("k_codet", k_codet, dim3((b.nb + BLOCK - 1) / BLOCK, b.nlay), block, s, G.D, Wk, b.nb, b.col0);
+            }
+            return launches_ok();
+        } else return fail(RRTMG_LW_HIP_EARG, "shared gas optics: GCM entries only");
+    }
     // k_layer's CLOUD: 0 clear, 1 cloud (rtrn / rtrnmr), 2 mcica (the sub-column arrays), 3 mcmask (the generator's mask)
     const int cloud = b.mode == 0 ? 0 : b.mode == 3 ? (b.mc ? 2 : 3) : 1;
     if (TUNING && !GCM) return fail(RRTMG_LW_HIP_EARG, "tuning build: GCM entry only");
@@ -977,6 +997,14 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, const Batch &b, const GcmIn &
         // a window of positions x a chunk of levels per workgroup
         const dim3 wgrid((nb + COLSORT_WIN - 1) / COLSORT_WIN, (b.nlay + 1 + FLUX_CH - 1) / FLUX_CH), wblock(COLSORT_WIN);
         const double *pz = GCM ? g.plev : c.pz;
+        if (b.acc != 0) {           // a later sample of an averaging call: its total-sky values join what the caller's arrays hold
+            const double ns = (double)b.nsamp;
+            with_const<0, 1, 2, 3>((b.idrv == 1 ? 2 : 0) + (b.acc == 2 ? 1 : 0), [&](auto V) {
+                constexpr int v = decltype(V)::value;
+                LAUNCH("k_flux_acc", (k_flux_acc<(v & 2) != 0, (v & 1) != 0>), wgrid, wblock, s, G.D, Wk, out, pz, nb, b.col0, b.nct, b.mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0, ns);
+                return 0;
+            });
+        } else
         if (b.idrv == 1) LAUNCH("k_flux", (k_flux<true>), wgrid, wblock, s, G.D, Wk, out, pz, nb, b.col0, b.nct, b.mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0);
         else LAUNCH("k_flux", (k_flux<false>), wgrid, wblock, s, G.D, Wk, out, pz, nb, b.col0, b.nct, b.mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0);
     }
@@ -1249,6 +1277,39 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
     }
     if (split) {                                  // the caller's stream sees the results of every batch
         for (int k = 0; k < std::min(i, 2); k++) HIP_TRY(hipStreamWaitEvent(s, G.ev_done[k].get(), 0));
+    }
+    HIP_TRY(hipEventRecord(G.ev_last.get(), s));
+    G.ev_last_valid = true;
+    return 0;
+}
+
+// All batches of a device-resident call that averages nsamp sub-column samples, on the caller's stream: batch by batch, and within a
+// batch sample by sample, so that what the samples of a batch share stays where it is - the gas codes, the binary-key words and the
+// float64 optical depths that k_layer leaves with the first sample (Batch::share).  Per sample: the per-column kernels, the generator
+// with that sample's seed, k_cloudmc<mask> and k_blocksort, k_layer (sample 0) or k_codet (the others), the sweeps, k_flux (Batch::acc).
+// One prep set, one scratch set, no auxiliary stream: a sample's kernels depend on each other, and the next sample's mask, cloud flags
+// and hand-off levels go where this one's are.
+int run_samples(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOut &out, KissGen gen, int nsamp, int seedstep)
+{
+    if (int rc = ensure_pipeline()) return rc;
+    const int ncol = call.ncall, nlay = call.nlay;
+    const int nbmax = balanced_batch(ncol, eff_batch(nlay));
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));      // an earlier call, possibly on another stream, still owns the workspace
+    ColIn c{};
+    Batch b = call;
+    b.nsamp = nsamp;
+    for (int col0 = 0; col0 < ncol; col0 += nbmax) {
+        b.nb = std::min(nbmax, ncol - col0); b.col0 = col0;
+        const Workspace Wk = ws_for(0, use_colsort(true, call.mode, b.nb));
+        for (int i = 0; i < nsamp; i++) {
+            b.acc = i == 0 ? 0 : (i == nsamp - 1 ? 2 : 1);
+            b.share = i == 0 ? 1 : 2;
+            const int seed = (int)((long long)gen.permuteseed + (long long)i * seedstep);
+            if (int rc = run_prep<true>(s, Wk, b, g, c)) return rc;
+            if (int rc = launch_kiss(s, Wk, call.nct, b.col0, b.nb, nlay, gen.icld, seed, SubcolIn{g.play, g.cldfr, gen.alpha})) return rc;
+            if (int rc = run_layer<true>(s, Wk, b, g, c)) return rc;
+            if (int rc = run_sweep<true>(s, Wk, b, g, c, out)) return rc;
+        }
     }
     HIP_TRY(hipEventRecord(G.ev_last.get(), s));
     G.ev_last_valid = true;
@@ -2088,26 +2149,43 @@ int mt_states(hipStream_t s, uint32_t seed, unsigned long long per, int *M_out, 
 }
 
 // the table of one (draws per sub-column, permuteseed) pair: entries 0 .. KJ_NGROUP-1 jump from the seed to sub-column 8 g, the last one
-// by one sub-column.  One table, rebuilt (after a device synchronisation: an earlier call may still read it) when the pair changes - a host
-// model keeps its permuteseed per call site, so in steady state this is a comparison.
+// by one sub-column.  A set of them (KissTable): a host model keeps its permuteseed per call site and an averaging call its list of seeds,
+// so in steady state this is a search.  A pair the set does not hold takes a slot that has never held a table - nothing reads it: its
+// table is copied on the stream `s`, in front of the generator's launches, with no synchronisation - or, when all have, the slot used
+// longest ago, after a device synchronisation (an earlier launch on another stream may still be reading it): a host that changes its
+// seed with every call pays that synchronisation again once KISS_SLOTS pairs have been seen.  A later call that finds the table and
+// launches on ANOTHER stream reads a finished copy: the copy is ordered in front of the generator of the call that made it, that call ends
+// in G.ev_last, and every call waits for G.ev_last before it launches (run_pipelined, run_samples, generate_mask).
 // (struct KissTable: beside State, which holds one per device)
+std::atomic<long long> g_kiss_built{0};         // tables built since the library was loaded (rrtmg_lw_hip_kiss_tables_built)
 
 int kiss_table(hipStream_t s, int stride, int permuteseed, const KissJump **dev, KissJump *jsub)
 {
     KissTable &T = G.kiss;
     const long long seed = std::max(permuteseed, 0);
-    if (int rc = grow(T.dev, sizeof(T.host), sizeof(T.host), "kissvec jump table")) return rc;
-    if (T.stride != (unsigned long long)stride || T.seed != seed) {
-        // an earlier launch on another stream may still be reading the table
-        HIP_TRY(hipDeviceSynchronize());
-        for (int g = 0; g < KJ_NGROUP; g++) T.host[g] = kiss_jump_entry((unsigned long long)seed + 8ull * g * (unsigned long long)stride);
-        T.host[KJ_NGROUP] = kiss_jump_entry((unsigned long long)stride);
-        T.stride = (unsigned long long)stride; T.seed = seed;
-        HIP_TRY(hipMemcpy(T.dev.get(), T.host, sizeof(T.host), hipMemcpyHostToDevice));
+    constexpr size_t slot_bytes = (KJ_NGROUP + 1) * sizeof(KissJump);
+    if (int rc = grow(T.dev, KISS_SLOTS * slot_bytes, KISS_SLOTS * slot_bytes, "kissvec jump tables")) return rc;
+    if (int rc = grow(T.host, KISS_SLOTS * slot_bytes, KISS_SLOTS * slot_bytes, "kissvec jump tables (host)")) return rc;
+    if (T.slot.empty()) T.slot.resize(KISS_SLOTS);
+    KissSlot *hit = nullptr, *old = &T.slot[0];
+    for (KissSlot &k : T.slot) {
+        if (k.seed == seed && k.stride == (unsigned long long)stride) { hit = &k; break; }
+        if (k.used < old->used) old = &k;
     }
-    (void)s;
-    *dev = T.dev.as<KissJump>();
-    *jsub = T.host[KJ_NGROUP];
+    KissJump *const host = T.host.as<KissJump>() + (size_t)((hit ? hit : old) - &T.slot[0]) * (KJ_NGROUP + 1);
+    if (!hit) {
+        hit = old;
+        if (hit->used != 0) HIP_TRY(hipDeviceSynchronize());
+        hit->seed = -1;
+        for (int g = 0; g < KJ_NGROUP; g++) host[g] = kiss_jump_entry((unsigned long long)seed + 8ull * g * (unsigned long long)stride);
+        host[KJ_NGROUP] = kiss_jump_entry((unsigned long long)stride);
+        HIP_TRY(hipMemcpyAsync(T.dev.as<char>() + (size_t)(hit - &T.slot[0]) * slot_bytes, host, slot_bytes, hipMemcpyHostToDevice, s));
+        hit->stride = (unsigned long long)stride; hit->seed = seed;
+        g_kiss_built++;
+    }
+    hit->used = ++T.clock;
+    *dev = reinterpret_cast<const KissJump *>(T.dev.as<char>() + (size_t)(hit - &T.slot[0]) * slot_bytes);
+    *jsub = host[KJ_NGROUP];
     return 0;
 }
 
@@ -2437,6 +2515,8 @@ void rrtmg_lw_hip_graph_stats(long long *captures, long long *replays)
     if (captures) *captures = g_states[0].graph_captures;
     if (replays) *replays = g_states[0].graph_replays;
 }
+// jump tables of the kissvec generator built so far (kiss_table): does not move in steady state
+long long rrtmg_lw_hip_kiss_tables_built(void) { return g_kiss_built.load(); }
 
 // Batches of up to `ncol` columns are swept one band per workgroup (g_split_max); 0 = never.  Results do not depend on it.  Returns the
 // previous value.
@@ -3612,9 +3692,22 @@ int rrtmg_lw_hip_mcica_subcol(
 #define SUBCOL_PARAMS                                                                                                       \
     int ncol, int nlay, int *icld, int idrv, int permuteseed, int *irng, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw, \
     CLOUD_PARAMS, const double *alpha, const double *tauaer, OUT_PARAMS
-static int mcica_subcol_device(const CallDesc &d, const GcmIn &g, const double *alpha, const FluxOut &out, void *stream)
+// what the averaging entries (rrtmg_lw_hip_run_mcica_samples*) ask of nsamp and seedstep, before anything is written
+static int check_samples(const CallDesc &d, int nsamp, int seedstep)
 {
-    ENTRY_LOCK_FOR(g.play, d.irng && *d.irng != 0);
+    if (nsamp < 1) return fail(RRTMG_LW_HIP_EARG, "nsamp = %d: at least one sample", nsamp);
+    if (nsamp > RRTMG_LW_HIP_MAX_SAMPLES) return fail(RRTMG_LW_HIP_EARG, "nsamp = %d exceeds RRTMG_LW_HIP_MAX_SAMPLES = %d", nsamp, RRTMG_LW_HIP_MAX_SAMPLES);
+    if (seedstep < 1) return fail(RRTMG_LW_HIP_EARG, "seedstep = %d: the seeds of two samples must differ (at least 1; the sub-columns of a sample, rrtmg_lw_hip_gpoints(), is the documented choice)", seedstep);
+    if ((long long)d.permuteseed + (long long)(nsamp - 1) * seedstep > 2147483647ll)
+        return fail(RRTMG_LW_HIP_EARG, "permuteseed + (nsamp - 1) * seedstep = %d + %d * %d is not an int", d.permuteseed, nsamp - 1, seedstep);
+    if (nsamp > 1 && d.irng && *d.irng != 0) return fail(RRTMG_LW_HIP_EARG, "irng = %d with nsamp = %d: several samples are drawn with the kissvec generator (irng = 0) only", *d.irng, nsamp);
+    return 0;
+}
+// the fused call on stream s (the caller holds the lock): the checks, the workspace, the mask buffer, then run_pipelined - or, with
+// nsamp > 1 and cloud, run_samples: the seeds permuteseed + i seedstep batch by batch and sample by sample on that one stream, the gas
+// optics of a batch once (the workspace is then that of the McICA entry with sub-column arrays: W.odg holds the float64 optical depths)
+static int mcica_subcol_device_run(const CallDesc &d, const GcmIn &g, const double *alpha, const FluxOut &out, hipStream_t s, int nsamp = 1, int seedstep = 1)
+{
     if (int rc = check_mcica_build()) return rc;
     if (d.spectral) if (int rc = check_spec(out)) return rc;
     if (!d.icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
@@ -3623,9 +3716,9 @@ static int mcica_subcol_device(const CallDesc &d, const GcmIn &g, const double *
     const int icld_gen = *d.icld;
     if (*d.icld > 3) *d.icld = 2;                                 // what rrtmg_lw does to the generator's icld (src/rrtmg_lw_rad.f90:469)
     const int mode = icld_gen == 0 ? 0 : 3;
-    hipStream_t s = (hipStream_t)stream;
     const int nbmax = balanced_batch(d.ncol, eff_batch(d.nlay));
-    if (int rc = ensure_workspace(d.nlay, nbmax, mode != 0, false, d.idrv, mode)) return rc;      // mask path: no per-g-point cloud arrays
+    // mask path: no per-g-point cloud arrays - but for the float64 optical depths the samples of an averaging call share (W.odg)
+    if (int rc = ensure_workspace(d.nlay, nbmax, mode != 0, mode == 3 && nsamp > 1, d.idrv, mode)) return rc;
     KissGen gen{false, icld_gen, d.permuteseed, alpha};
     if (mode == 3) {
         if (*d.irng == 0) {          // kissvec: every column owns its stream -> generated batch by batch on the auxiliary stream
@@ -3639,7 +3732,23 @@ static int mcica_subcol_device(const CallDesc &d, const GcmIn &g, const double *
             if (int rc = generate_mask(s, d.ncol, d.nlay, icld_gen, d.permuteseed, *d.irng, gp, gc, ga)) return rc;
         }
     }
-    return run_pipelined(s, batch_of(d, mode), g, out, gen);
+    if (mode != 3 || nsamp == 1) return run_pipelined(s, batch_of(d, mode), g, out, gen);          // (no cloud: nothing is drawn, every sample is the same)
+    return run_samples(s, batch_of(d, mode), g, out, gen, nsamp, seedstep);
+}
+static int mcica_subcol_device(const CallDesc &d, const GcmIn &g, const double *alpha, const FluxOut &out, void *stream)
+{
+    ENTRY_LOCK_FOR(g.play, d.irng && *d.irng != 0);
+    return mcica_subcol_device_run(d, g, alpha, out, (hipStream_t)stream);
+}
+#define SAMPLES_PARAMS                                                                                                                        \
+    int ncol, int nlay, int *icld, int idrv, int permuteseed, int nsamp, int seedstep, int *irng, GCM_PARAMS, int inflglw, int iceflglw, int liqflglw, \
+    CLOUD_PARAMS, const double *alpha, const double *tauaer, OUT_PARAMS
+int rrtmg_lw_hip_run_mcica_samples_device(SAMPLES_PARAMS, void *stream)
+{
+    const CallDesc d{ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng};
+    ENTRY_LOCK_FOR(play, irng && *irng != 0);
+    if (int rc = check_samples(d, nsamp, seedstep)) return rc;
+    return mcica_subcol_device_run(d, {GCM_NAMES, CLOUD_NAMES, tauaer}, alpha, {OUT_NAMES}, (hipStream_t)stream, nsamp, seedstep);
 }
 int rrtmg_lw_hip_run_mcica_subcol_device(SUBCOL_PARAMS, void *stream)
 {
@@ -3748,6 +3857,55 @@ int rrtmg_lw_hip_run_mcica_subcol(SUBCOL_PARAMS)
     }
     ENTRY_LOCK;
     return mcica_subcol_host(d, g, alpha, out);
+}
+
+// The mean over nsamp samples from HOST arrays (the entry lock, the first device, no combining).  The samples add up in the output
+// arrays on the device (k_flux_acc), so the call's arrays live there as a whole for its duration - not batch by batch in the staging
+// sets as the single call's do -, the device path runs on them, and the outputs travel back once.
+int rrtmg_lw_hip_run_mcica_samples(SAMPLES_PARAMS)
+{
+    const CallDesc d{ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng};
+    const GcmIn g{GCM_NAMES, CLOUD_NAMES, tauaer};
+    const FluxOut out{OUT_NAMES};
+    ENTRY_LOCK;
+    if (int rc = check_samples(d, nsamp, seedstep)) return rc;
+    if (nsamp == 1 || !icld || !irng || *icld < 1 || *icld > 5) return mcica_subcol_host(d, g, alpha, out);      // (a single sample; no cloud: nothing is drawn; what the single call refuses)
+    if (int rc = check_mcica_build()) return rc;
+    if (int rc = check_subcol_args(ncol, nlay, *icld, irng)) return rc;
+    if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
+    if (!have_outs(out)) return fail(RRTMG_LW_HIP_EARG, "null output array");
+    if (nlay < 4) return fail(RRTMG_LW_HIP_EARG, "the kissvec generator needs at least four layers");
+    const bool two = *icld == 4 || *icld == 5;
+    if (two && !alpha) return fail(RRTMG_LW_HIP_EARG, "icld = 4/5 needs alpha");
+    const double *hin[NA_IN];
+    gcm_pointers(g, two ? alpha : nullptr, hin);
+    for (int a = 0; a < NA_GCM; a++) if (!hin[a]) return fail(RRTMG_LW_HIP_EARG, CALL_ARRAYS[a].cloud ? "null cloud array" : "null input array (argument %d)", a);
+    double *hout[NA_CALL];
+    flux_pointers(out, hout);
+    const size_t L = (size_t)nlay, n = (size_t)ncol;
+    const auto count = [&](int a) { return CALL_ARRAYS[a].inner * rows_of(a, L) * n; };
+    const auto travels = [&](int a) { return a < NA_IN ? hin[a] != nullptr : a < A_DUFLX_DT || idrv == 1; };
+    size_t total = 0;
+    for (int a = 0; a < A_UFLXS; a++) if (travels(a)) total += count(a);
+    HIP_TRY(hipDeviceSynchronize());      // asynchronous device-entry work of earlier calls shares the workspace
+    DevBuf buf;                             // (released when the call is left, on every path)
+    if (int rc = grow(buf, total * 8, total * 8, "arrays of an averaging call")) return rc;
+    const double *din[NA_IN] = {};
+    double *dout[NA_CALL] = {};
+    {
+        double *p = buf.as<double>();
+        for (int a = 0; a < A_UFLXS; a++) {
+            if (!travels(a)) continue;
+            if (a < NA_IN) { if (int rc = bounce_h2d(p, hin[a], count(a) * 8)) return rc; din[a] = p; }
+            else dout[a] = p;
+            p += count(a);
+        }
+    }
+    hipStream_t s = G.stream.get();
+    if (int rc = mcica_subcol_device_run(d, gcm_from(din), din[A_ALPHA], flux_from(dout), s, nsamp, seedstep)) return rc;
+    if (int rc = read_physics_error(s)) return rc;
+    for (int a = A_UFLX; a < A_UFLXS; a++) if (dout[a] && hout[a]) { if (int rc = bounce_d2h(hout[a], dout[a], count(a) * 8)) return rc; }
+    return 0;
 }
 
 // float32 host arrays, alpha too: the entry lock, no combining (like the spectral entry)

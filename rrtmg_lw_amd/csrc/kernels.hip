@@ -1482,6 +1482,10 @@ __device__ __forceinline__ scr_t cell_code(double od, bool series, double bpade)
 // all cells (g-points) of band B of one (layer, column).
 // CLOUD: 0 clear-sky set, 1 one cloud optical depth per band (rtrn / rtrnmr), 2 one per g-point from W.odg (rtrnmc, sub-column
 // arrays), 3 the band's value where the sub-column mask has a bit (rtrnmc, generator mask; gbits = the band's ng mask bits)
+// 5 (CL_SHARE): 3, and the cells' optical depths - secdiff x (gas + aerosol), as they stand in front of the codes - are stored as
+// float64 in W.odg: the first sample of a call that averages several sub-column samples (rrtmg_lw_hip_run_mcica_samples).  They do not
+// depend on the sample; k_codet forms the total codes of the later samples from them, and k_layer does not run again.
+constexpr int CL_SHARE = 5;
 template <int B, int CLOUD, bool LOWER, int N, bool LDS>
 __device__ __forceinline__ void band_cells(const DevTables &T, const Workspace &W, __amdgpu_buffer_rsrc_t kt, const double2 *lds, const Rows<N> &rw, int lay, int col,
                                            bool incol, double secdiff, double taua, int cloudy, double odcld, unsigned gbits)
@@ -1516,6 +1520,16 @@ __device__ __forceinline__ void band_cells(const DevTables &T, const Workspace &
     if constexpr (R.key == K_BINARY) { if (incol) W.fw[((size_t)fw_slot(B) * nlay + (lay - 1)) * ncb + col] = rw.fw; }
     const size_t so0 = ((size_t)QS * nlay + (lay - 1)) * ncb + col;     // scratch cell of the band's first quad
     const size_t qstride = (size_t)nlay * ncb;
+    if constexpr (CLOUD == CL_SHARE) {
+        if (incol) {
+#pragma unroll
+            for (int q = 0; q < NQ; q++) {
+                double2 *po = reinterpret_cast<double2 *>(W.odg + (so0 + q * qstride) * 4);
+                po[0] = double2{od[4 * q], od[4 * q + 1]};
+                po[1] = double2{od[4 * q + 2], od[4 * q + 3]};
+            }
+        }
+    }
     // gas: series for od <= 0.06, else the table (rtrn :372-451; in a cloudy layer the branch taken for the gas terms depends on od alone)
     auto gas_codes = [&]() {
 #pragma unroll
@@ -1589,7 +1603,7 @@ __device__ __forceinline__ void band_cells(const DevTables &T, const Workspace &
                     double odc[GC], tg[GC];
 #pragma unroll
                     for (int k = 0; k < GC; k++) odc[k] = odcld;
-                    if constexpr (CLOUD == 3) {
+                    if constexpr (CLOUD == 3 || CLOUD == CL_SHARE) {
 #pragma unroll
                         for (int k = 0; k < GC; k++) odc[k] = ((gbits >> (4 * q0 + k)) & 1u) ? odcld : 0.0;
                     }
@@ -1779,11 +1793,11 @@ __device__ __forceinline__ void layer_band(const DevTables &T, const Workspace &
     const bool use_lds = __builtin_amdgcn_ballot_w64(!wg.ok) == 0ull;       // wave-uniform: every cell of the wave lies in the staged window
     const size_t ncb = W.ncolb, gcx = (size_t)a.col0 + wg.pc;
     double odcld = 0.0;
-    if constexpr (CLOUD == 1 || CLOUD == 3) { if (cloudy) odcld = W.odcld[((size_t)(B - 1) * W.nlay + (lay - 1)) * ncb + col]; }   // (written for cloudy layers only)
+    if constexpr (CLOUD == 1 || CLOUD == 3 || CLOUD == CL_SHARE) { if (cloudy) odcld = W.odcld[((size_t)(B - 1) * W.nlay + (lay - 1)) * ncb + col]; }   // (written for cloudy layers only)
     const double secdiff = W.percol[(size_t)(PC_SECDIFF + B - 1) * ncb + col];
     const double taua = col_load(a.tauaer + (size_t)a.col0 + (size_t)a.nct * ((lay - 1) + (size_t)W.nlay * (B - 1)), (unsigned)wg.pc * 8u);
     unsigned gbits = 0u;
-    if constexpr (CLOUD == 3) {
+    if constexpr (CLOUD == 3 || CLOUD == CL_SHARE) {
         // the band's bits of the sub-column mask: the one or two words that hold them, read here (all five held from the top of the kernel
         // ended up in scratch memory)
         (void)mw;
@@ -2024,7 +2038,7 @@ __device__ __forceinline__ void layer_cells(const DevTables &T, const Workspace 
     int cloudy = 0;
     // (threads past the last column never take the cloudy branches: nothing of theirs is stored, and with them no lane of a divergent
     // region skips the `if (incol)` at its end - the construct of profiles/round5_exec_hazard.md)
-    if (CLOUD >= 1 && CLOUD <= 3) cloudy = incol ? (W.cflag[(size_t)lay * W.ncolb + col] & 1) : 0;
+    if ((CLOUD >= 1 && CLOUD <= 3) || CLOUD == CL_SHARE) cloudy = incol ? (W.cflag[(size_t)lay * W.ncolb + col] & 1) : 0;
     if constexpr (CLOUD == CL_OPTICS) {
         // setcoef :173-269 for the bands of this workgroup: the layer's Planck integral and that of the level above it; the layer-1 threads
         // add level 0 and the surface terms k_colprep has formed for the sweeps (plankbnd with semiss, its d/dT with idrv = 1)
@@ -2127,6 +2141,68 @@ __global__ __launch_bounds__(LAYER_BLOCK, RRLW_LAYER_WAVES) void k_optics(DevTab
     __shared__ double2 s_tab[STAGE_DOUBLES / 2];
     __shared__ int s_wg[5];
     layer_grid<GCM, CL_OPTICS, WIDE>(T, W, g, c, a, s_tab, s_wg, o);
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_codet : the total-optical-depth codes (S_CODET) of the cloudy layers of one sub-column sample from the float64 optical depths
+//           k_layer<., CL_SHARE, .> left in W.odg, the sample's mask and its cloud optical depths (k_cloudmc<mask>): the cloudy branch
+//           of band_cells, expression for expression - same clamp, same three sub-branches, same table indices -, so that a sample's
+//           codes are those k_layer<mcmask> writes for it.  One thread per (position, layer); a layer without a cloudy sub-column
+//           leaves at once.  Every cell read was stored: k_layer stores all quads of all layers of the batch's columns.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_codet(DevTables T, Workspace W, int ncol, int col0)
+{
+    const int col = blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= ncol) return;
+    const int lay = blockIdx.y + 1, nlay = W.nlay;
+    const size_t ncb = W.ncolb;
+    if (!(W.cflag[(size_t)lay * ncb + col] & 1)) return;
+    const size_t gcx = (size_t)col0 + pcol(W, col);
+    const double *__restrict__ tau_tbl = T.stat + T.sl.tau_tbl;
+    const double bpade = T.bpade;
+    const unsigned *mrow = W.mask + (size_t)(lay - 1) * W.mask_stride + W.mask_col0 + gcx;
+    const size_t qstride = (size_t)nlay * ncb;
+#pragma unroll 1
+    for (int B = 1; B <= NBND; B++) {
+        const int ng = band_ng(B), g0 = band_g0(B), nq = band_nquad(B);
+        const int w0 = g0 >> 5, w1 = (g0 + ng - 1) >> 5;
+        const unsigned long long lo = mrow[(size_t)w0 * nlay * W.mask_stride];
+        const unsigned long long hi = w1 != w0 ? mrow[(size_t)w1 * nlay * W.mask_stride] : 0u;
+        const unsigned gbits = (unsigned)(((lo | (hi << 32)) >> (g0 & 31)) & ((1ull << ng) - 1ull));
+        const double odcld = W.odcld[((size_t)(B - 1) * nlay + (lay - 1)) * ncb + col];
+        const size_t so0 = ((size_t)band_qstart(B) * nlay + (lay - 1)) * ncb + col;
+#pragma unroll 1
+        for (int q = 0; q < nq; q++) {
+            const double2 *po = reinterpret_cast<const double2 *>(W.odg + (so0 + q * qstride) * 4);
+            const double2 a = po[0], b = po[1];
+            double od[4] = {a.x, a.y, b.x, b.y}, odc[4], tg[4], odtot[4];
+            bool tk[4];
+            int it[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int j = 4 * q + k;
+                if (j < ng) { if (!(od[k] >= 0.0)) od[k] = 0.0; }       // rtrn :369
+                odc[k] = ((gbits >> j) & 1u) ? odcld : 0.0;
+                const bool p3 = !(od[k] + odc[k] < 0.06) && !(od[k] <= 0.06);
+                int igk = 0;
+                if (j < ng && p3) igk = lut_index(od[k], bpade);
+                tg[k] = tau_tbl[igk];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int j = 4 * q + k;
+                const bool p1 = od[k] + odc[k] < 0.06;
+                const bool p3 = !p1 && !(od[k] <= 0.06);
+                odtot[k] = (p3 ? tg[k] : od[k]) + odc[k];
+                tk[k] = j < ng && !p1;
+            }
+            quad_indices(odtot[0], odtot[1], odtot[2], odtot[3], tk[0], tk[1], tk[2], tk[3], bpade, it);
+            scr4 c;
+#pragma unroll
+            for (int k = 0; k < 4; k++) c.v[k] = 4 * q + k < ng ? (tk[k] ? -(scr_t)it[k] : (scr_t)odtot[k]) : (scr_t)0;
+            scr_store(W.scr[S_CODET], so0 + q * qstride, c);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4201,9 +4277,21 @@ constexpr unsigned long long FLUX_GSZ1 = 0x1111ull;        // ... as `gsz` state
 template <bool IDRV> struct FluxRaw { Part2 u[FLUX_NG], d[FLUX_NG], q[IDRV ? FLUX_NG : 1]; };      // a level's group partials as loaded
 struct FluxVal { double u, d, uc, dc, du, duc; };
 constexpr int flux_lds_bytes(bool idrv) { return 2 * (idrv ? 6 : 4) * COLSORT_WIN * 8; }           // the exchange tile: 16 KB, 24 KB with d/dT
-template <bool IDRV>
-__global__ __launch_bounds__(COLSORT_WIN) void k_flux(DevTables T, Workspace W, FluxOut out, const double *pz, int ncol, int col0, int nct,
-                                                      int clear_from_total, int ngroups, unsigned long long gsz, int clear_groups)
+// A call that averages several sub-column samples (rrtmg_lw_hip_run_mcica_samples) runs the solver once per sample; k_flux of sample 0
+// stores (ACC = 0, as in every other call), that of a later sample adds its total-sky values to what the caller's arrays hold (ACC = 1),
+// that of the last one adds and divides by the number of samples (ACC = 2): the float64 sum in sample order and one division, no pass
+// of its own over the outputs.  The clear-sky outputs do not depend on the sample: sample 0 has stored them.
+template <int ACC>
+__device__ __forceinline__ void flux_put(double *p, double x, double nsamp)
+{
+#pragma clang fp contract(off)      // (the sample's value rounds before it is added, as the stored value of a single call has)
+    if constexpr (ACC == 0) *p = x;
+    else if constexpr (ACC == 1) *p = *p + x;
+    else *p = (*p + x) / nsamp;
+}
+template <bool IDRV, int ACC>
+__device__ __forceinline__ void flux_body(const DevTables &T, const Workspace &W, const FluxOut &out, const double *pz, int ncol, int col0, int nct,
+                                          int clear_from_total, int ngroups, unsigned long long gsz, int clear_groups, double nsamp)
 {   // gsz: slabs per group, a nibble each (1, or - SweepArgs::split - the group's bands: added first, in their order, like the group's workgroup does)
     constexpr int NV = IDRV ? 6 : 4;                        // values of a level that change places
     __shared__ double s_v[2][NV][COLSORT_WIN];
@@ -4300,14 +4388,21 @@ __global__ __launch_bounds__(COLSORT_WIN) void k_flux(DevTables T, Workspace W, 
         const size_t o = gc + (size_t)nct * lev;
         const double net = u - d, netc = uc - dc;
         if (lev >= k0) {
-            out.uflx[o] = u; out.dflx[o] = d; out.uflxc[o] = uc; out.dflxc[o] = dc;
-            if (out.fnet) { out.fnet[o] = u - d; out.fnetc[o] = uc - dc; }
-            if constexpr (IDRV) { out.duflx_dt[o] = du; out.duflxc_dt[o] = duc; }
+            if constexpr (ACC == 0) {
+                out.uflx[o] = u; out.dflx[o] = d; out.uflxc[o] = uc; out.dflxc[o] = dc;
+                if (out.fnet) { out.fnet[o] = u - d; out.fnetc[o] = uc - dc; }
+                if constexpr (IDRV) { out.duflx_dt[o] = du; out.duflxc_dt[o] = duc; }
+            } else {
+                flux_put<ACC>(out.uflx + o, u, nsamp); flux_put<ACC>(out.dflx + o, d, nsamp);
+                if constexpr (IDRV) flux_put<ACC>(out.duflx_dt + o, du, nsamp);
+            }
         }
         if (lev > kf) {             // net flux and heating rate of the layer below the level
             const double dp = pb - p;
-            out.hr[o - (size_t)nct] = T.heatfac * (nb - net) / dp;
-            out.hrc[o - (size_t)nct] = T.heatfac * (nbc - netc) / dp;
+            if constexpr (ACC == 0) {
+                out.hr[o - (size_t)nct] = T.heatfac * (nb - net) / dp;
+                out.hrc[o - (size_t)nct] = T.heatfac * (nbc - netc) / dp;
+            } else flux_put<ACC>(out.hr + (o - (size_t)nct), T.heatfac * (nb - net) / dp, nsamp);
         }
         pb = p; nb = net; nbc = netc;
     };
@@ -4328,6 +4423,19 @@ __global__ __launch_bounds__(COLSORT_WIN) void k_flux(DevTables T, Workspace W, 
             if (lev < k1 && on) p = pzc[(size_t)nct * (lev + 1)];
         }
     }
+}
+template <bool IDRV>
+__global__ __launch_bounds__(COLSORT_WIN) void k_flux(DevTables T, Workspace W, FluxOut out, const double *pz, int ncol, int col0, int nct,
+                                                      int clear_from_total, int ngroups, unsigned long long gsz, int clear_groups)
+{
+    flux_body<IDRV, 0>(T, W, out, pz, ncol, col0, nct, clear_from_total, ngroups, gsz, clear_groups, 1.0);
+}
+// ... of sample 1 .. nsamp-1 of a call that averages samples (LAST: the one that divides)
+template <bool IDRV, bool LAST>
+__global__ __launch_bounds__(COLSORT_WIN) void k_flux_acc(DevTables T, Workspace W, FluxOut out, const double *pz, int ncol, int col0, int nct,
+                                                          int clear_from_total, int ngroups, unsigned long long gsz, int clear_groups, double nsamp)
+{
+    flux_body<IDRV, LAST ? 2 : 1>(T, W, out, pz, ncol, col0, nct, clear_from_total, ngroups, gsz, clear_groups, nsamp);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -250,7 +250,23 @@ int rrtmg_lw_hip_run_mcica_subcol_device(
  * cloud optics and all sweeps, the clear-sky ones included.
  * nsamp = 1 and *icld = 0 through the host entry ARE rrtmg_lw_hip_run_mcica_subcol behind the entry lock - its fan-out over several
  * initialised devices included; with nsamp > 1 and cloud the host entry runs on the first device.
- * Not offered: *_as, *_view, *_r4 and *_spectral variants, fan-out over several devices, per-sample or variance outputs. */
+ * The sample variance (rrtmg_lw_hip_run_mcica_samples_var, rrtmg_lw_hip_run_mcica_samples_device_view): three optional outputs uflx_var,
+ * dflx_var, hr_var with the shapes of uflx, dflx, hr, each NULL or set on its own.  They hold the UNBIASED sample variance of the nsamp
+ * values X_s, in (W m-2)^2 and (K d-1)^2; the standard error of the returned mean is sqrt(var / nsamp) - what tells a host whether
+ * nsamp = 4 or 16 is enough.  It is formed where the mean is formed, per output element, in float64, every operation rounded on its own
+ * (no fused multiply-add), with S in the mean's array and M in the variance's - no third array, no pass of its own, no workspace:
+ *     sample 0:                       S = X_0                       M = 0
+ *     sample s >= 1, c = s + 1:       S = S + X_s
+ *                                     t = c * X_s - S               (the product rounds, then the difference)
+ *                                     M = M + (t * t) / (c * (c - 1))          (c * (c - 1) is exact)
+ *     last sample, after its update:  mean = S / nsamp              var = M / (nsamp - 1)
+ * so a caller who runs the nsamp single calls and applies these lines gets the same bits, and the mean is bit for bit that of the entries
+ * without variance.  var >= 0 by construction; columns whose samples are identical (no cloud) give exactly 0 or values at rounding
+ * level (below (nsamp x 2^-53)^2: a few 1e-25 for fluxes of 50 - 500 W m-2 and 64 samples).  When nothing is drawn (*icld = 0) the variance arrays are written with exact
+ * zeros - by the kernel that stores the fluxes, so a view is not written outside the call's columns.  The clear-sky outputs and duflx_dt
+ * get no variance.  RRTMG_LW_HIP_EARG before any output is written, with a text that names the argument: a variance pointer together
+ * with nsamp = 1; a variance array that overlaps its mean.
+ * Not offered: *_r4 and *_spectral variants, fan-out over several devices, per-sample outputs, the Mersenne Twister with nsamp > 1. */
 #define RRTMG_LW_HIP_MAX_SAMPLES 64
 int rrtmg_lw_hip_run_mcica_samples(
     int ncol, int nlay, int *icld, int idrv, int permuteseed, int nsamp, int seedstep, int *irng,
@@ -272,6 +288,18 @@ int rrtmg_lw_hip_run_mcica_samples_device(
     const double *reice, const double *reliq, const double *alpha, const double *tauaer,
     double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
     double *duflx_dt, double *duflxc_dt, void *stream);
+/* HOST pointers: rrtmg_lw_hip_run_mcica_samples plus the variances; the three arrays join the per-call allocation on the device.  With
+ * a variance pointer set, *icld = 0 runs on the first device too. */
+int rrtmg_lw_hip_run_mcica_samples_var(
+    int ncol, int nlay, int *icld, int idrv, int permuteseed, int nsamp, int seedstep, int *irng,
+    const double *play, const double *plev, const double *tlay, const double *tlev, const double *tsfc,
+    const double *h2ovmr, const double *o3vmr, const double *co2vmr, const double *ch4vmr, const double *n2ovmr,
+    const double *o2vmr, const double *cfc11vmr, const double *cfc12vmr, const double *cfc22vmr,
+    const double *ccl4vmr, const double *emis, int inflglw, int iceflglw, int liqflglw,
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
+    const double *reice, const double *reliq, const double *alpha, const double *tauaer,
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
+    double *duflx_dt, double *duflxc_dt, double *uflx_var, double *dflx_var, double *hr_var);
 /* jump tables of the kissvec generator built since the library was loaded (a counter, like rrtmg_lw_hip_graph_stats) */
 long long rrtmg_lw_hip_kiss_tables_built(void);
 
@@ -710,6 +738,30 @@ int rrtmg_lw_hip_adjust_tsfc_device_view(const rrtmg_lw_hip_array_view *view, in
     const void *uflx, const void *dflx, const void *duflx_dt,
     const void *uflxc, const void *dflxc, const void *duflxc_dt,
     void *uflx_adj, void *hr_adj, void *uflxc_adj, void *hrc_adj, void *stream);
+/* The mean over nsamp sub-column samples ("The mean over several sub-column samples", above) of DEVICE arrays in the view's form, and
+ * optionally the sample variances uflx_var, dflx_var, hr_var in the same form (hr_var flips with top_first like hr; a float32 output is
+ * the float64 result rounded once, after the last sample).  All three NULL: the mean alone.  {8, 0, 0, 0}: the plain
+ * rrtmg_lw_hip_run_mcica_samples_device, plus variance.  {8, 0, 0, ld} runs in place, sample by sample on the caller's arrays; a
+ * converting form stages a batch's inputs (alpha too) once, runs the samples on the staged arrays and converts the outputs once.  The
+ * results are those of rrtmg_lw_hip_run_mcica_samples_device on float64 reference-form copies of the call's columns, put into the form.
+ * No spectral arguments.  Errors: those of that entry and of the view, and the two variance cases.  Enqueues on `stream`, does not
+ * synchronise; a physics error surfaces through rrtmg_lw_hip_check(stream). */
+int rrtmg_lw_hip_run_mcica_samples_device_view(const rrtmg_lw_hip_array_view *view,
+    int ncol, int nlay, int *icld, int idrv, int permuteseed, int nsamp, int seedstep, int *irng,
+    const void *play, const void *plev, const void *tlay, const void *tlev, const void *tsfc,
+    const void *h2ovmr, const void *o3vmr, const void *co2vmr, const void *ch4vmr, const void *n2ovmr,
+    const void *o2vmr, const void *cfc11vmr, const void *cfc12vmr, const void *cfc22vmr,
+    const void *ccl4vmr, const void *emis, int inflglw, int iceflglw, int liqflglw,
+    const void *cldfr, const void *taucld, const void *cicewp, const void *cliqwp,
+    const void *reice, const void *reliq, const void *alpha, const void *tauaer,
+    void *uflx, void *dflx, void *hr, void *uflxc, void *dflxc, void *hrc,
+    void *duflx_dt, void *duflxc_dt, void *uflx_var, void *dflx_var, void *hr_var, void *stream);
+/* rrtmg_lw_hip_get_alpha on DEVICE arrays in the view's form: dz, cldfrac and alpha are layer arrays ((ld, nlay), or (ncol, nlay) in C
+ * order with layer_fastest = 1), lat is per column.  The value of reference layer k is stored where the form keeps layer k.  Float64
+ * arithmetic, the host entry's bits in the form {8, 0, 0}; a float32 alpha is that value rounded.  Enqueues on `stream`, does not
+ * synchronise.  icld other than 4 or 5: returns 0 and leaves alpha alone, like the host entry.  lat may be NULL unless idcor = 1. */
+int rrtmg_lw_hip_get_alpha_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, int icld, int idcor, double decorr_con,
+    const void *dz, const void *lat, int juldat, const void *cldfrac, void *alpha, void *stream);
 
 /* ---- Host arrays of a host built with 4-byte reals ("_r4") ----------------------------------------------------------------------------
  * A host model that carries RRTMG_LW at the default real kind (no -r8) owns float arrays.  These four entries take them as they are:

@@ -777,13 +777,17 @@ def mcica_subcol_lw(ncol, nlay, icld, permuteseed, irng, play, cldfrac, ciwp, cl
 def rrtmg_lw_mcica_subcol(ncol, nlay, icld, idrv, permuteseed, irng, play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr,
                           ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, iceflglw, liqflglw,
                           cldfr, taucld, cicewp, cliqwp, reice, reliq, alpha, tauaer, spectral=False, out=None, dtype=None,
-                          nsamp=1, seedstep=None):
+                          nsamp=1, seedstep=None, var=False):
     """mcica_subcol_lw followed by the McICA rrtmg_lw in one call; the sub-columns stay on the device as bit masks.
     spectral=True: the fluxes per band as well (see rrtmg_lw); `out`: a dict of preallocated spectral outputs to fill.
     dtype=np.float32: float32 arrays in and out, alpha too (rrtmg_lw_hip_run_mcica_subcol_r4; _real).
     nsamp > 1: the mean of the total-sky outputs over nsamp samples drawn with permuteseed + s * seedstep (seedstep=None: gpoints()),
-    summed in float64 in sample order and divided once; clear-sky outputs are sample 0's (rrtmg_lw_hip_run_mcica_samples)."""
+    summed in float64 in sample order and divided once; clear-sky outputs are sample 0's (rrtmg_lw_hip_run_mcica_samples).
+    var=True (nsamp > 1, float64): the result also holds uflx_var, dflx_var, hr_var, the unbiased sample variances of uflx, dflx, hr
+    over the samples (rrtmg_lw_hip_run_mcica_samples_var; the standard error of the mean is sqrt(var / nsamp))."""
     nsamp, seedstep = _samples(nsamp, seedstep, **{"spectral=True": spectral, "a float32 dtype": dtype is not None and np.dtype(dtype) == np.float32})
+    if var and nsamp == 1:
+        raise ValueError("var=True with nsamp = 1: the sample variance needs at least two samples")
     dt = _real(dtype, spectral)
     a = _gcm_arrays(ncol, nlay, play, plev, tlay, tlev, tsfc,
                     (h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr), emis, dt)
@@ -797,7 +801,10 @@ def rrtmg_lw_mcica_subcol(ncol, nlay, icld, idrv, permuteseed, irng, play, plev,
     if nsamp != 1:
         args[5:5] = [C.c_int(nsamp), C.c_int(seedstep)]
     args += [_p(x) for x in a] + [C.c_int(int(inflglw)), C.c_int(int(iceflglw)), C.c_int(int(liqflglw))] + cld + _out_ptrs(out, idrv)
-    if nsamp != 1:
+    if var:
+        out.update(uflx_var=np.empty((ncol, nlay + 1), order="F"), dflx_var=np.empty((ncol, nlay + 1), order="F"), hr_var=np.empty((ncol, nlay), order="F"))
+        _check(lib().rrtmg_lw_hip_run_mcica_samples_var(*args, *[_p(out[k]) for k in _VAR_OUT]))
+    elif nsamp != 1:
         _check(lib().rrtmg_lw_hip_run_mcica_samples(*args))
     elif spectral:
         _check(lib().rrtmg_lw_hip_run_mcica_subcol_spectral(*args, *_spec_ptrs(out, ncol, nlay)))
@@ -811,12 +818,12 @@ def rrtmg_lw_mcica_subcol(ncol, nlay, icld, idrv, permuteseed, irng, play, plev,
 
 
 def rrtmg_lw_mcica_subcol_from_dict(d, permuteseed, irng, alpha=None, icld=None, idrv=None, spectral=False, out=None, dtype=None,
-                                    nsamp=1, seedstep=None):
+                                    nsamp=1, seedstep=None, var=False):
     icld = d["icld"] if icld is None else icld
     idrv = d["idrv"] if idrv is None else idrv
     return rrtmg_lw_mcica_subcol(d["ncol"], d["nlay"], icld, idrv, permuteseed, irng, *[d[k] for k in _GCM_ORDER], d["inflglw"],
                                  d["iceflglw"], d["liqflglw"], d["cldfr"], d["taucld"], d["cicewp"], d["cliqwp"], d["reice"],
-                                 d["reliq"], alpha, d["tauaer"], spectral=spectral, out=out, dtype=dtype, nsamp=nsamp, seedstep=seedstep)
+                                 d["reliq"], alpha, d["tauaer"], spectral=spectral, out=out, dtype=dtype, nsamp=nsamp, seedstep=seedstep, var=var)
 
 
 def rrtmg_lw_mcica_subcol_device(d, out, permuteseed, irng, alpha=None, icld=None, idrv=None, stream=None, form=None, ld=None,
@@ -864,6 +871,73 @@ def rrtmg_lw_mcica_subcol_device(d, out, permuteseed, irng, alpha=None, icld=Non
         return icld_c.value
     _check(lib().rrtmg_lw_hip_run_mcica_subcol_device(*args))
     return icld_c.value
+
+
+_VAR_OUT = ("uflx_var", "dflx_var", "hr_var")
+
+
+def _checked_view(form, ld, ncol, nlay, tensors):
+    """The `view` argument of a *_view entry, as _view_arg makes it, for a dict of named tensors (None: not given) - without a look at
+    the library: the forms of these arrays do not depend on the number of g-points."""
+    from . import arrays
+    form = arrays.ArrayForm(*(form if form is not None else arrays.REFERENCE))
+    if form.real_bytes not in (4, 8) or form.layer_fastest not in (0, 1) or form.top_first not in (0, 1):
+        raise ValueError(f"bad array form {tuple(form)}")
+    ld = arrays.check_ld(ncol, ld, form)
+    for k, t in tensors.items():
+        if t is not None:
+            arrays.check_tensor(k, t, ncol, nlay, form, ld=ld)
+    return C.byref(_ArrayViewC(*form, ld))
+
+
+def rrtmg_lw_mcica_samples_device(d, out, permuteseed, nsamp, seedstep=None, alpha=None, icld=None, idrv=None, stream=None, form=None, ld=None):
+    """Device-resident mean over nsamp sub-column samples (kissvec generator, seeds permuteseed + s * seedstep; seedstep=None:
+    gpoints()) of the fused generator + solver, in the caller's own array form and width (rrtmg_lw_hip_run_mcica_samples_device_view):
+    `d`, `out`, `alpha`, `form`, `ld` as in rrtmg_lw_mcica_subcol_device with ld= (ld=None: ncol - contiguous tensors of the form).
+    `out` may also hold uflx_var, dflx_var, hr_var (each on its own; shapes of uflx, dflx, hr, in the form): the unbiased sample
+    variances, formed where the mean is formed; the standard error of the mean is sqrt(var / nsamp).  Without them: the mean alone.
+    ValueError before the library is touched: spectral outputs in `out`, a variance with nsamp = 1, tensors that are not the form's."""
+    nsamp = int(nsamp)
+    for k in _SPEC:
+        if out.get(k) is not None:
+            raise ValueError(f"'{k}': the averaging entry has no spectral outputs")
+    for k in _VAR_OUT:
+        if out.get(k) is not None and nsamp == 1:
+            raise ValueError(f"{k} with nsamp = 1: the sample variance needs at least two samples")
+    ncol, nlay = int(d["ncol"]), int(d["nlay"])
+    tensors = {k: d.get(k) for k in _GCM_ORDER + _CLD_ORDER}
+    tensors["alpha"] = alpha
+    tensors.update({k: out.get(k) for k in _FLUX_OUT + _VAR_OUT})
+    view = _checked_view(form, ld or 0, ncol, nlay, tensors)
+    icld = d["icld"] if icld is None else icld
+    idrv = d["idrv"] if idrv is None else idrv
+    seedstep = gpoints() if seedstep is None else int(seedstep)
+    icld_c, irng_c = C.c_int(int(icld)), C.c_int(0)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    args = [view, C.c_int(ncol), C.c_int(nlay), C.byref(icld_c), C.c_int(int(idrv)), C.c_int(int(permuteseed)), C.c_int(nsamp), C.c_int(seedstep),
+            C.byref(irng_c)]
+    args += [ptr(d[k]) for k in _GCM_ORDER]
+    args += [C.c_int(int(d["inflglw"])), C.c_int(int(d["iceflglw"])), C.c_int(int(d["liqflglw"]))]
+    args += [ptr(d[k]) for k in ("cldfr", "taucld", "cicewp", "cliqwp", "reice", "reliq")]
+    args += [ptr(alpha), ptr(d["tauaer"])]
+    args += [ptr(out.get(k)) for k in _FLUX_OUT + _VAR_OUT]
+    _check(lib().rrtmg_lw_hip_run_mcica_samples_device_view(*args, C.c_void_p(stream or 0)))
+    return icld_c.value
+
+
+def get_alpha_device(d, alpha, icld, idcor, decorr_con, juldat, stream=None, form=None, ld=None):
+    """Device-resident get_alpha (rrtmg_lw_hip_get_alpha_device_view): `d` holds torch CUDA tensors dz, cldfr (or cldfrac) (ncol, nlay)
+    and lat (ncol,) - and ncol, nlay - in `form` (None: the reference form), views of fields `ld` columns wide if ld is given; `alpha`
+    the output tensor of the same kind, which the fused McICA entries take as it is.  Enqueues on `stream`, does not synchronise; icld
+    other than 4 or 5 leaves alpha alone."""
+    ncol, nlay = int(d["ncol"]), int(d["nlay"])
+    cldfr = d["cldfr"] if d.get("cldfr") is not None else d.get("cldfrac")
+    view = _checked_view(form, ld or 0, ncol, nlay, {"dz": d.get("dz"), "lat": d.get("lat"), "cldfr": cldfr, "alpha": alpha})
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    _check(lib().rrtmg_lw_hip_get_alpha_device_view(view, C.c_int(ncol), C.c_int(nlay), C.c_int(int(icld)), C.c_int(int(idcor)),
+                                                    C.c_double(float(decorr_con)), ptr(d.get("dz")), ptr(d.get("lat")), C.c_int(int(juldat)),
+                                                    ptr(cldfr), ptr(alpha), C.c_void_p(stream or 0)))
+    return alpha
 
 
 def run_columns_mcica(cols, subs, istart=1, iend=16, icld=None, idrv=None):

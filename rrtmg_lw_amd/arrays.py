@@ -12,6 +12,8 @@ column index fastest, vertical index 0 at the surface, logical shapes as the For
     planklev                                                                        (ncol, nlay+1, 16)
     taug, fracs                                                                     (ncol, nlay, NG)
     tsfc                                                                            (ncol,)
+    dz (ncol, nlay), lat (ncol,)                                                    get_alpha's inputs (api.get_alpha_device)
+    uflx_var, dflx_var (ncol, nlay+1), hr_var (ncol, nlay)                          sample variances (api.rrtmg_lw_mcica_samples_device)
 
 An ArrayForm(real_bytes, layer_fastest, top_first) describes what a device-resident caller holds instead:
 
@@ -46,12 +48,12 @@ import numpy as np
 NBND = 16
 
 LAYER_ARRAYS = ("play", "tlay", "h2ovmr", "o3vmr", "co2vmr", "ch4vmr", "n2ovmr", "o2vmr", "cfc11vmr", "cfc12vmr", "cfc22vmr",
-                "ccl4vmr", "cldfr", "cicewp", "cliqwp", "reice", "reliq", "alpha", "hr", "hrc", "hr_adj", "hrc_adj")
-LEVEL_ARRAYS = ("plev", "tlev", "uflx", "dflx", "uflxc", "dflxc", "duflx_dt", "duflxc_dt", "uflx_adj", "uflxc_adj")
+                "ccl4vmr", "cldfr", "cicewp", "cliqwp", "reice", "reliq", "alpha", "hr", "hrc", "hr_adj", "hrc_adj", "dz", "hr_var")
+LEVEL_ARRAYS = ("plev", "tlev", "uflx", "dflx", "uflxc", "dflxc", "duflx_dt", "duflxc_dt", "uflx_adj", "uflxc_adj", "uflx_var", "dflx_var")
 BAND_ARRAYS = ("emis", "plankbnd", "dplankbnd_dt")                      # (ncol, 16): no vertical axis
 LAYER_X_ARRAYS = ("tauaer", "planklay", "taug", "fracs")                # (ncol, nlay, 16 | NG)
 LEVEL_X_ARRAYS = ("planklev", "uflxs", "dflxs", "uflxcs", "dflxcs")      # (ncol, nlay+1, 16)
-COLUMN_ARRAYS = ("tsfc", "dtsfc")
+COLUMN_ARRAYS = ("tsfc", "dtsfc", "lat")
 ALL_ARRAYS = LAYER_ARRAYS + LEVEL_ARRAYS + BAND_ARRAYS + LAYER_X_ARRAYS + LEVEL_X_ARRAYS + COLUMN_ARRAYS + ("taucld",)
 
 

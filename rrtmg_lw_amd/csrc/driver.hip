@@ -204,7 +204,7 @@ struct Batch {
     int inflag = 0, iceflag = 0, liqflag = 0;
     const McIn *mc = nullptr;                     // mode 3: the sub-column arrays, or null when the sub-columns come from the generator's mask (Workspace::mask)
     int nb = 0, col0 = 0;                         // this batch
-    int acc = 0, nsamp = 1;                       // a sample of a call that averages nsamp of them (run_samples): 0 k_flux stores, 1 adds, 2 adds and divides
+    int acc = 0, nsamp = 1, isamp = 0;            // a sample (isamp = 0 .. nsamp - 1) of a call that averages nsamp of them (run_samples): 0 k_flux stores, 1 adds, 2 adds and divides
     int share = 0;                                // ... 1: k_layer leaves the cells' float64 optical depths in W.odg (the first sample), 2: k_codet forms the
                                                   // sample's total codes from them and k_layer does not run (a later sample of the same batch)
 };
@@ -923,7 +923,7 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, const Batch &b, const GcmIn &
     SweepArgs sa = sweep_args<GCM>(b, g, c, out);
     const bool spec = sa.uflxs != nullptr;
 #ifndef RRLW_TUNE
-    if (G.n1 && b.mode == 0 && GCM && b.istart == 1 && b.iend == 16 && b.idrv == 0 && !spec && n1_lds_bytes(b.nlay) <= N1_LDS_MAX) {
+    if (G.n1 && b.mode == 0 && GCM && b.istart == 1 && b.iend == 16 && b.idrv == 0 && !spec && !out.uflx_var && !out.dflx_var && !out.hr_var && n1_lds_bytes(b.nlay) <= N1_LDS_MAX) {
         // prototype of the north-star mapping (one column per wavefront): replaces the sweeps, k_flux and k_rates of a cloud-free call
         // (it takes no spectral call)
         const dim3 ngrid((nb + N1_WAVES - 1) / N1_WAVES), nblock(64 * N1_WAVES);
@@ -997,6 +997,14 @@ int run_sweep(hipStream_t s, const Workspace &Wk_, const Batch &b, const GcmIn &
         // a window of positions x a chunk of levels per workgroup
         const dim3 wgrid((nb + COLSORT_WIN - 1) / COLSORT_WIN, (b.nlay + 1 + FLUX_CH - 1) / FLUX_CH), wblock(COLSORT_WIN);
         const double *pz = GCM ? g.plev : c.pz;
+        if (out.uflx_var || out.dflx_var || out.hr_var) {      // the call also wants sample variances: sample 0 zeroes them, sample cnt - 1 updates them
+            const double ns = (double)b.nsamp, cnt = b.acc == 0 ? 1.0 : (b.acc == 2 ? ns : (double)b.isamp + 1.0);
+            with_const<0, 1, 2, 3, 4, 5>((b.idrv == 1 ? 3 : 0) + b.acc, [&](auto V) {
+                constexpr int v = decltype(V)::value;
+                LAUNCH("k_flux_var", (k_flux_var<(v >= 3), v % 3>), wgrid, wblock, s, G.D, Wk, out, pz, nb, b.col0, b.nct, b.mode == 0 ? 1 : 0, fg.n, gsz, cfree ? 1 : 0, ns, cnt);
+                return 0;
+            });
+        } else
         if (b.acc != 0) {           // a later sample of an averaging call: its total-sky values join what the caller's arrays hold
             const double ns = (double)b.nsamp;
             with_const<0, 1, 2, 3>((b.idrv == 1 ? 2 : 0) + (b.acc == 2 ? 1 : 0), [&](auto V) {
@@ -1142,7 +1150,7 @@ int run_pipelined(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOu
         const double *gp[] = {g.play, g.plev, g.tlay, g.tlev, g.tsfc, g.h2ovmr, g.o3vmr, g.co2vmr, g.ch4vmr, g.n2ovmr, g.o2vmr, g.cfc11vmr, g.cfc12vmr,
                               g.cfc22vmr, g.ccl4vmr, g.emis, g.cldfr, g.taucld, g.cicewp, g.cliqwp, g.reice, g.reliq, g.tauaer, g.tauctot,
                               out.uflx, out.dflx, out.hr, out.uflxc, out.dflxc, out.hrc, out.duflx_dt, out.duflxc_dt, out.fnet, out.fnetc,
-                              out.uflxs, out.dflxs, out.uflxcs, out.dflxcs};
+                              out.uflxs, out.dflxs, out.uflxcs, out.dflxcs, out.uflx_var, out.dflx_var, out.hr_var};
         key_put(key, gp);
         // (what else decides which kernels run with which arguments: the workspace, the tuning switches)
         // (what the kernel nodes carry BY VALUE: the tables of this initialisation - DevTables with heatfac and the table pointers - on its device)
@@ -1304,6 +1312,7 @@ int run_samples(hipStream_t s, const Batch &call, const GcmIn &g, const FluxOut 
         for (int i = 0; i < nsamp; i++) {
             b.acc = i == 0 ? 0 : (i == nsamp - 1 ? 2 : 1);
             b.share = i == 0 ? 1 : 2;
+            b.isamp = i;
             const int seed = (int)((long long)gen.permuteseed + (long long)i * seedstep);
             if (int rc = run_prep<true>(s, Wk, b, g, c)) return rc;
             if (int rc = launch_kiss(s, Wk, call.nct, b.col0, b.nb, nlay, gen.icld, seed, SubcolIn{g.play, g.cldfr, gen.alpha})) return rc;
@@ -3703,6 +3712,25 @@ static int check_samples(const CallDesc &d, int nsamp, int seedstep)
     if (nsamp > 1 && d.irng && *d.irng != 0) return fail(RRTMG_LW_HIP_EARG, "irng = %d with nsamp = %d: several samples are drawn with the kissvec generator (irng = 0) only", *d.irng, nsamp);
     return 0;
 }
+// ... and of the optional variance arrays: a variance needs two samples, and M of the recurrence cannot live where S does.  level_bytes,
+// layer_bytes: what a (., nlay+1) and a (., nlay) array span from their pointers in the caller's form.
+static int check_var(const FluxOut &o, int nsamp, size_t level_bytes, size_t layer_bytes)
+{
+    const struct { const double *v, *m; size_t n; const char *name; } t[3] = {{o.uflx_var, o.uflx, level_bytes, "uflx"}, {o.dflx_var, o.dflx, level_bytes, "dflx"}, {o.hr_var, o.hr, layer_bytes, "hr"}};
+    for (const auto &e : t) {
+        if (!e.v) continue;
+        if (nsamp == 1) return fail(RRTMG_LW_HIP_EARG, "%s_var with nsamp = 1: the sample variance needs at least two samples (pass NULL)", e.name);
+        const char *v = (const char *)e.v, *m = (const char *)e.m;
+        const size_t n = e.n;
+        if (m && v < m + n && m < v + n) return fail(RRTMG_LW_HIP_EARG, "%s_var aliases %s: the two sums of a sample are kept in the two arrays", e.name, e.name);
+    }
+    return 0;
+}
+static FluxOut with_var(FluxOut o, double *uflx_var, double *dflx_var, double *hr_var)
+{
+    o.uflx_var = uflx_var; o.dflx_var = dflx_var; o.hr_var = hr_var;
+    return o;
+}
 // the fused call on stream s (the caller holds the lock): the checks, the workspace, the mask buffer, then run_pipelined - or, with
 // nsamp > 1 and cloud, run_samples: the seeds permuteseed + i seedstep batch by batch and sample by sample on that one stream, the gas
 // optics of a batch once (the workspace is then that of the McICA entry with sub-column arrays: W.odg holds the float64 optical depths)
@@ -3859,27 +3887,40 @@ int rrtmg_lw_hip_run_mcica_subcol(SUBCOL_PARAMS)
     return mcica_subcol_host(d, g, alpha, out);
 }
 
+}   // extern "C"
 // The mean over nsamp samples from HOST arrays (the entry lock, the first device, no combining).  The samples add up in the output
 // arrays on the device (k_flux_acc), so the call's arrays live there as a whole for its duration - not batch by batch in the staging
 // sets as the single call's do -, the device path runs on them, and the outputs travel back once.
-int rrtmg_lw_hip_run_mcica_samples(SAMPLES_PARAMS)
+// (out.uflx_var, dflx_var, hr_var: rrtmg_lw_hip_run_mcica_samples_var - three more arrays of the per-call allocation; with *icld = 0 the
+// call then takes this path too: sample 0's k_flux writes their zeros)
+static int samples_host(const CallDesc &d, const GcmIn &g, const double *alpha, const FluxOut &out, int nsamp, int seedstep)
 {
-    const CallDesc d{ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng};
-    const GcmIn g{GCM_NAMES, CLOUD_NAMES, tauaer};
-    const FluxOut out{OUT_NAMES};
+    const int ncol = d.ncol, nlay = d.nlay, idrv = d.idrv;
+    int *const icld = d.icld, *const irng = d.irng;
+    double *const duflx_dt = out.duflx_dt, *const duflxc_dt = out.duflxc_dt;
     ENTRY_LOCK;
     if (int rc = check_samples(d, nsamp, seedstep)) return rc;
-    if (nsamp == 1 || !icld || !irng || *icld < 1 || *icld > 5) return mcica_subcol_host(d, g, alpha, out);      // (a single sample; no cloud: nothing is drawn; what the single call refuses)
+    {
+        const size_t n8 = (size_t)std::max(ncol, 0) * 8, L0 = (size_t)std::max(nlay, 0);
+        if (int rc = check_var(out, nsamp, (L0 + 1) * n8, L0 * n8)) return rc;
+    }
+    double *const hvar[3] = {out.uflx_var, out.dflx_var, out.hr_var};
+    const bool var = hvar[0] || hvar[1] || hvar[2];
+    if (nsamp == 1 || !icld || !irng || *icld < (var ? 0 : 1) || *icld > 5) return mcica_subcol_host(d, g, alpha, out);      // (a single sample; no cloud: nothing is drawn; what the single call refuses)
+    const bool cloud = *icld != 0;
     if (int rc = check_mcica_build()) return rc;
     if (int rc = check_subcol_args(ncol, nlay, *icld, irng)) return rc;
     if (idrv == 1 && (!duflx_dt || !duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
     if (!have_outs(out)) return fail(RRTMG_LW_HIP_EARG, "null output array");
-    if (nlay < 4) return fail(RRTMG_LW_HIP_EARG, "the kissvec generator needs at least four layers");
+    if (cloud && nlay < 4) return fail(RRTMG_LW_HIP_EARG, "the kissvec generator needs at least four layers");
     const bool two = *icld == 4 || *icld == 5;
     if (two && !alpha) return fail(RRTMG_LW_HIP_EARG, "icld = 4/5 needs alpha");
     const double *hin[NA_IN];
     gcm_pointers(g, two ? alpha : nullptr, hin);
-    for (int a = 0; a < NA_GCM; a++) if (!hin[a]) return fail(RRTMG_LW_HIP_EARG, CALL_ARRAYS[a].cloud ? "null cloud array" : "null input array (argument %d)", a);
+    for (int a = 0; a < NA_GCM; a++) {
+        if (CALL_ARRAYS[a].cloud && !cloud) hin[a] = nullptr;            // (inatm does not read them: they do not travel)
+        else if (!hin[a]) return fail(RRTMG_LW_HIP_EARG, CALL_ARRAYS[a].cloud ? "null cloud array" : "null input array (argument %d)", a);
+    }
     double *hout[NA_CALL];
     flux_pointers(out, hout);
     const size_t L = (size_t)nlay, n = (size_t)ncol;
@@ -3887,11 +3928,13 @@ int rrtmg_lw_hip_run_mcica_samples(SAMPLES_PARAMS)
     const auto travels = [&](int a) { return a < NA_IN ? hin[a] != nullptr : a < A_DUFLX_DT || idrv == 1; };
     size_t total = 0;
     for (int a = 0; a < A_UFLXS; a++) if (travels(a)) total += count(a);
+    const int var_of[3] = {A_UFLX, A_DFLX, A_HR};       // a variance has its mean's shape
+    for (int k = 0; k < 3; k++) if (hvar[k]) total += count(var_of[k]);
     HIP_TRY(hipDeviceSynchronize());      // asynchronous device-entry work of earlier calls shares the workspace
     DevBuf buf;                             // (released when the call is left, on every path)
     if (int rc = grow(buf, total * 8, total * 8, "arrays of an averaging call")) return rc;
     const double *din[NA_IN] = {};
-    double *dout[NA_CALL] = {};
+    double *dout[NA_CALL] = {}, *dvar[3] = {};
     {
         double *p = buf.as<double>();
         for (int a = 0; a < A_UFLXS; a++) {
@@ -3900,12 +3943,25 @@ int rrtmg_lw_hip_run_mcica_samples(SAMPLES_PARAMS)
             else dout[a] = p;
             p += count(a);
         }
+        for (int k = 0; k < 3; k++) if (hvar[k]) { dvar[k] = p; p += count(var_of[k]); }
     }
     hipStream_t s = G.stream.get();
-    if (int rc = mcica_subcol_device_run(d, gcm_from(din), din[A_ALPHA], flux_from(dout), s, nsamp, seedstep)) return rc;
+    if (int rc = mcica_subcol_device_run(d, gcm_from(din), din[A_ALPHA], with_var(flux_from(dout), dvar[0], dvar[1], dvar[2]), s, nsamp, seedstep)) return rc;
     if (int rc = read_physics_error(s)) return rc;
     for (int a = A_UFLX; a < A_UFLXS; a++) if (dout[a] && hout[a]) { if (int rc = bounce_d2h(hout[a], dout[a], count(a) * 8)) return rc; }
+    for (int k = 0; k < 3; k++) if (hvar[k]) { if (int rc = bounce_d2h(hvar[k], dvar[k], count(var_of[k]) * 8)) return rc; }
     return 0;
+}
+extern "C" {
+int rrtmg_lw_hip_run_mcica_samples(SAMPLES_PARAMS)
+{
+    return samples_host({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng}, {GCM_NAMES, CLOUD_NAMES, tauaer}, alpha, {OUT_NAMES}, nsamp, seedstep);
+}
+// ... with the unbiased sample variances of uflx, dflx and hr (each optional), formed where the mean is (k_flux_var)
+int rrtmg_lw_hip_run_mcica_samples_var(SAMPLES_PARAMS, double *uflx_var, double *dflx_var, double *hr_var)
+{
+    return samples_host({ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng}, {GCM_NAMES, CLOUD_NAMES, tauaer}, alpha,
+                        with_var({OUT_NAMES}, uflx_var, dflx_var, hr_var), nsamp, seedstep);
 }
 
 // float32 host arrays, alpha too: the entry lock, no combining (like the spectral entry)
@@ -4105,6 +4161,71 @@ int mcica_subcol_device_as(const rrtmg_lw_hip_array_form &f, const CallDesc &d, 
         if (int rc = generate_mask(s, d.ncol, d.nlay, icld_gen, d.permuteseed, *d.irng, sg[0], sg[1], two ? sg[2] : nullptr)) return rc;
     }
     return form_solve(f, d, mode, u, uo, s);
+}
+
+// The sample-aware sibling of form_solve (rrtmg_lw_hip_run_mcica_samples_device_view with a converting form, nsamp > 1: the kissvec
+// generator).  Per batch the caller's arrays - alpha too - are staged ONCE, the samples run on the staged arrays as run_samples runs
+// them on a caller's (the sums live in the staged output planes, the variance planes beside them), and the outputs are converted once,
+// after the last sample: a float32 output is rounded once.  The generator draws per staged batch, at column 0 of the staged arrays
+// and of the mask (Workspace::mask_col0 = 0); the whole-call mask of mcica_subcol_device_as holds ONE sample and is not used.
+// Caller holds the entry lock.
+int mcica_samples_as_run(const rrtmg_lw_hip_array_form &f, const CallDesc &d, const GcmIn &u, const void *alpha, const FluxOut &uo, int nsamp, int seedstep, hipStream_t s)
+{
+    if (int rc = check_mcica_build()) return rc;
+    if (!d.icld) return fail(RRTMG_LW_HIP_EARG, "icld is null");
+    if (int rc = check_subcol_args(d.ncol, d.nlay, *d.icld, d.irng)) return rc;
+    if (d.idrv == 1 && (!uo.duflx_dt || !uo.duflxc_dt)) return fail(RRTMG_LW_HIP_EARG, "idrv=1 needs duflx_dt and duflxc_dt");
+    const int icld_gen = *d.icld;
+    const int mode = icld_gen == 0 ? 0 : 3;
+    const bool cloud = mode != 0, two = icld_gen == 4 || icld_gen == 5;
+    const size_t L = (size_t)d.nlay, ncol = (size_t)d.ncol, ldu = d.ld > 0 ? (size_t)d.ld : ncol;
+    const double *up[NA_IN];
+    gcm_pointers(u, two ? (const double *)alpha : nullptr, up);
+    std::vector<FormItem> ins, outs;
+    for (int a = 0; a < NA_IN; a++) {
+        if (a == A_ALPHA ? !two : (CALL_ARRAYS[a].cloud && !cloud)) continue;
+        if (!up[a]) return fail(RRTMG_LW_HIP_EARG, a == A_ALPHA ? "icld = 4/5 needs alpha" : "null input array (argument %d of rrtmg_lw's arrays)", a + 1);
+        ins.push_back(form_item(up[a], a, L, a == A_TAUCLD ? FA_TAUCLD : FA_PLANE));
+    }
+    if (!have_outs(uo)) return fail(RRTMG_LW_HIP_EARG, "null output array");
+    double *uop[NA_CALL];
+    flux_pointers(uo, uop);
+    for (int a = A_UFLX; a < A_UFLXS; a++) if (a < A_DUFLX_DT || d.idrv == 1) outs.push_back(form_item(uop[a], a, L));
+    const size_t nmean = outs.size();
+    // the variance planes: the shape of their means, hr_var flipped with hr
+    double *const uvar[3] = {uo.uflx_var, uo.dflx_var, uo.hr_var};
+    const int var_of[3] = {A_UFLX, A_DFLX, A_HR};
+    int var_item[3] = {-1, -1, -1};
+    for (int k = 0; k < 3; k++) if (uvar[k]) { var_item[k] = (int)outs.size(); outs.push_back(form_item(uvar[k], var_of[k], L)); }
+    if (*d.icld > 3) *d.icld = 2;                                 // what rrtmg_lw does to the generator's icld (src/rrtmg_lw_rad.f90:469)
+    const size_t nbmax = (size_t)balanced_batch(d.ncol, eff_batch(d.nlay));
+    if (int rc = ensure_workspace(d.nlay, (int)nbmax, cloud, cloud, d.idrv, mode)) return rc;
+    if (cloud) if (int rc = prepare_mask((int)nbmax, d.nlay, icld_gen, 0, (const double *)alpha)) return rc;
+    std::vector<double *> si, so;
+    const size_t n_in = form_place(ins, nbmax, nullptr, si), n_out = form_place(outs, nbmax, nullptr, so);
+    if (int rc = ensure_form(G.form_buf, (n_in + n_out) * 8)) return rc;
+    if (int rc = ensure_pipeline()) return rc;
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));      // an earlier call, possibly on another stream, still owns the workspace and the staging
+    int rc = 0;
+    for (size_t col0 = 0; col0 < ncol && rc == 0; col0 += nbmax) {
+        const size_t nb = std::min(nbmax, ncol - col0);
+        const size_t used = form_place(ins, nb, G.form_buf.as<double>(), si);
+        form_place(outs, nb, G.form_buf.as<double>() + used, so);
+        const double *sp[NA_IN] = {};
+        for (size_t k = 0; k < ins.size(); k++) sp[ins[k].pos] = si[k];
+        double *op[NA_CALL] = {}, *vp[3] = {};
+        for (size_t k = 0; k < nmean; k++) op[outs[k].pos] = so[k];
+        for (int k = 0; k < 3; k++) if (var_item[k] >= 0) vp[k] = so[(size_t)var_item[k]];
+        const FluxOut fo = with_var(flux_from(op), vp[0], vp[1], vp[2]);
+        rc = form_launch(s, true, f, ins, si, ldu, col0, nb);
+        G.W.mask_col0 = 0;
+        if (rc == 0) rc = cloud ? run_samples(s, staged_batch(d, mode, (int)nb), gcm_from(sp), fo, KissGen{true, icld_gen, d.permuteseed, sp[A_ALPHA]}, nsamp, seedstep)
+                                : run_batch<true>(s, staged_batch(d, mode, (int)nb), gcm_from(sp), ColIn{}, fo);
+        if (rc == 0) rc = form_launch(s, false, f, outs, so, ldu, col0, nb);
+    }
+    HIP_TRY(hipEventRecord(G.ev_last.get(), s));
+    G.ev_last_valid = true;
+    return rc;
 }
 
 // (declared in front of run_pipelined) the in-place *_view call with the Mersenne-Twister generator: G.form_gen as above, no conversion
@@ -4448,6 +4569,57 @@ int rrtmg_lw_hip_run_mcica_subcol_device_view(const rrtmg_lw_hip_array_view *vie
     const FluxOut out{OUT_NAMES_AS, SPEC_NAMES_AS};
     if (plain) return mcica_subcol_device(d, g, AS_(alpha), out, stream);
     return mcica_subcol_device_as(f, d, g, alpha, out, stream);
+}
+
+// The mean over nsamp samples, and optionally the sample variances, of DEVICE arrays in the caller's own form and width.  {8, 0, 0, ld}
+// runs in place (run_samples: Batch::nct is the stride); a converting form stages per batch (mcica_samples_as_run); a single sample is
+// rrtmg_lw_hip_run_mcica_subcol_device_view.
+int rrtmg_lw_hip_run_mcica_samples_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, int *icld, int idrv, int permuteseed, int nsamp,
+    int seedstep, int *irng, GCM_PARAMS_AS, int inflglw, int iceflglw, int liqflglw, CLOUD_PARAMS_AS, const void *alpha, const void *tauaer, OUT_PARAMS_AS,
+    void *uflx_var, void *dflx_var, void *hr_var, void *stream)
+{
+    rrtmg_lw_hip_array_form f;
+    int ld = 0;
+    bool plain = false;
+    if (int rc = view_check(view, ncol, &f, &ld, &plain)) return rc;
+    CallDesc d{ncol, nlay, icld, idrv, inflglw, iceflglw, liqflglw, permuteseed, irng};
+    d.ld = ld;
+    const GcmIn g{GCM_NAMES_AS, CLOUD_NAMES_AS, AS_(tauaer)};
+    const FluxOut out = with_var({OUT_NAMES_AS}, (double *)uflx_var, (double *)dflx_var, (double *)hr_var);
+    {
+        ENTRY_LOCK_FOR(play, irng && *irng != 0);
+        if (int rc = check_samples(d, nsamp, seedstep)) return rc;
+        // (what an array spans: its last row ends ncol, not ld, columns in; layer-fastest arrays have ld = ncol)
+        const auto span = [&](size_t rows) { return rows == 0 || ncol < 1 ? (size_t)0 : ((rows - 1) * (size_t)ld + (size_t)ncol) * (size_t)f.real_bytes; };
+        if (int rc = check_var(out, nsamp, span((size_t)std::max(nlay, 0) + 1), span((size_t)std::max(nlay, 0)))) return rc;
+        if (plain) return mcica_subcol_device_run(d, g, AS_(alpha), out, (hipStream_t)stream, nsamp, seedstep);
+        if (nsamp > 1) return mcica_samples_as_run(f, d, g, alpha, out, nsamp, seedstep, (hipStream_t)stream);
+    }
+    return mcica_subcol_device_as(f, d, g, alpha, out, stream);      // (one sample, no variance: the entry takes the lock itself)
+}
+
+// alpha of the exponential overlaps from DEVICE arrays in the caller's form, on the caller's stream, no synchronisation (k_alpha_view)
+int rrtmg_lw_hip_get_alpha_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, int icld, int idcor, double decorr_con,
+    const void *dz, const void *lat, int juldat, const void *cldfrac, void *alpha, void *stream)
+{
+    rrtmg_lw_hip_array_form f;
+    int ld = 0;
+    bool plain = false;
+    if (int rc = view_check(view, ncol, &f, &ld, &plain)) return rc;
+    ENTRY_LOCK_FOR(dz);
+    if (int rc = check_common(ncol, nlay)) return rc;
+    if (!(icld == 4 || icld == 5)) return 0;                      // alpha is only defined for the exponential overlaps
+    if (!dz || !cldfrac || (idcor == 1 && !lat)) return fail(RRTMG_LW_HIP_EARG, "null input array (%s)", !dz ? "dz" : !cldfrac ? "cldfrac" : "lat");
+    if (!alpha) return fail(RRTMG_LW_HIP_EARG, "null output array (alpha)");
+    const dim3 grid((ncol + BLOCK - 1) / BLOCK, nlay), block(BLOCK);
+    hipStream_t s = (hipStream_t)stream;
+    if (f.real_bytes == 4)
+        LAUNCH("k_alpha_view<f32>", (k_alpha_view<float>), grid, block, s, ncol, nlay, (size_t)ld, f.layer_fastest, f.top_first, icld, idcor, decorr_con,
+               (const float *)dz, (const float *)lat, juldat, (const float *)cldfrac, (float *)alpha);
+    else
+        LAUNCH("k_alpha_view<f64>", (k_alpha_view<double>), grid, block, s, ncol, nlay, (size_t)ld, f.layer_fastest, f.top_first, icld, idcor, decorr_con,
+               (const double *)dz, (const double *)lat, juldat, (const double *)cldfrac, (double *)alpha);
+    return launches_ok();
 }
 
 int rrtmg_lw_hip_gas_optics_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, int idrv, GCM_PARAMS_AS,

@@ -199,6 +199,7 @@ struct FluxOut {
     double *uflx, *dflx, *hr, *uflxc, *dflxc, *hrc, *duflx_dt, *duflxc_dt;   // stride ncol_total
     double *fnet, *fnetc;                                                     // optional (column entry)
     double *uflxs, *dflxs, *uflxcs, *dflxcs;                                  // optional spectral outputs (ncol_total, nlay+1, 16): written by the sweeps (SweepArgs)
+    double *uflx_var, *dflx_var, *hr_var;                                     // optional, each on its own: sample variances of uflx, dflx, hr (k_flux_var), their shapes
 };
 // Outputs of the gas-optics entries (k_optics), device pointers, column stride = ncol_total, g-point or band index last:
 // taug, fracs (ncol_total, nlay, NGPT); planklay (.., nlay, 16); planklev (.., nlay+1, 16); plankbnd, dplankbnd (.., 16).
@@ -2868,6 +2869,30 @@ __global__ __launch_bounds__(256) void k_subcol_expand(Workspace W, const double
     taucmcl[o] = on ? tauc[(g_band(isub) - 1) + (size_t)NBND * cl] : 0.0;
 }
 
+// 1 / decorrelation length of a column (idcor = 1: from its latitude and the day of the year, :140-152) and the layer's alpha from it
+__device__ __forceinline__ double alpha_decorr_inv(int idcor, double decorr_con, double lat, int juldat)
+{
+    const double am1 = 1.4315, am2 = 2.1219, am4 = -25.584, amr = 7.0;
+    double decorr_len, decorr_inv = 1.0;
+    if (idcor == 1) {                               // latitude / day-of-year dependent decorrelation length, :140-152
+        double am3;
+        if (juldat > 181) am3 = -4. * amr / 365. * (juldat - 272);
+        else am3 = 4. * amr / 365. * (juldat - 91);
+        const double y = lat - am3;
+        decorr_len = (am1 + am2 * exp(-(y * y) / (am4 * am4))) * 1.e3;
+    } else {
+        decorr_len = decorr_con;
+    }
+    if (decorr_len >= 0.0) decorr_inv = 1.0 / decorr_len;
+    return decorr_inv;
+}
+// (dz, cf: the layer's; dzm, cfm: those of the layer below it)
+__device__ __forceinline__ double alpha_of(int icld, double decorr_inv, double dz, double dzm, double cf, double cfm)
+{
+    double a = exp(-(0.5 * (dz + dzm)) * decorr_inv);
+    if (icld == 5 && cf == 0.0 && cfm > 0.0) a = 0.0;
+    return a;
+}
 __global__ __launch_bounds__(256) void k_alpha(int ncol, int nlay, int icld, int idcor, double decorr_con, const double *dz,
                                                const double *lat, int juldat, const double *cldfrac, double *alpha)
 {
@@ -2875,26 +2900,37 @@ __global__ __launch_bounds__(256) void k_alpha(int ncol, int nlay, int icld, int
     if (gc >= (size_t)ncol) return;
     const int k = blockIdx.y;                       // layer index 0 .. nlay-1
     if (!(icld == 4 || icld == 5)) return;
-    const double am1 = 1.4315, am2 = 2.1219, am4 = -25.584, amr = 7.0;
-    double decorr_len, decorr_inv = 1.0;
-    if (idcor == 1) {                               // latitude / day-of-year dependent decorrelation length, :140-152
-        double am3;
-        if (juldat > 181) am3 = -4. * amr / 365. * (juldat - 272);
-        else am3 = 4. * amr / 365. * (juldat - 91);
-        const double y = lat[gc] - am3;
-        decorr_len = (am1 + am2 * exp(-(y * y) / (am4 * am4))) * 1.e3;
-    } else {
-        decorr_len = decorr_con;
-    }
-    if (decorr_len >= 0.0) decorr_inv = 1.0 / decorr_len;
+    const double decorr_inv = alpha_decorr_inv(idcor, decorr_con, idcor == 1 ? lat[gc] : 0.0, juldat);
     const size_t o = gc + (size_t)ncol * k;
     double a = 0.0;
     if (k > 0) {
         const size_t om = o - (size_t)ncol;
-        a = exp(-(0.5 * (dz[o] + dz[om])) * decorr_inv);
-        if (icld == 5 && cldfrac[o] == 0.0 && cldfrac[om] > 0.0) a = 0.0;
+        a = alpha_of(icld, decorr_inv, dz[o], dz[om], cldfrac[o], cldfrac[om]);
     }
     alpha[o] = a;
+}
+// ... on DEVICE arrays in the caller's own form and width (rrtmg_lw_hip_get_alpha_device_view): R the element type, ld the columns
+// between two rows of a column-fastest array, layer_fastest / top_first as rrtmg_lw_hip_array_form states them.  The value of reference
+// layer k goes where the form stores layer k; the layer below it, k - 1, is the NEXT index of a top-first array.  lat is per column.
+template <class R>
+__global__ __launch_bounds__(256) void k_alpha_view(int ncol, int nlay, size_t ld, int layer_fastest, int top_first, int icld, int idcor, double decorr_con,
+                                                    const R *dz, const R *lat, int juldat, const R *cldfrac, R *alpha)
+{
+    const size_t gc = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gc >= (size_t)ncol) return;
+    const int k = blockIdx.y;                       // reference layer index 0 .. nlay-1, 0 at the surface
+    const double decorr_inv = alpha_decorr_inv(idcor, decorr_con, idcor == 1 ? (double)lat[gc] : 0.0, juldat);
+    const auto at = [&](int kr) -> size_t {
+        const size_t kk = (size_t)(top_first ? nlay - 1 - kr : kr);
+        return layer_fastest ? gc * (size_t)nlay + kk : gc + ld * kk;
+    };
+    const size_t o = at(k);
+    double a = 0.0;
+    if (k > 0) {
+        const size_t om = at(k - 1);
+        a = alpha_of(icld, decorr_inv, (double)dz[o], (double)dz[om], (double)cldfrac[o], (double)cldfrac[om]);
+    }
+    alpha[o] = (R)a;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4289,9 +4325,33 @@ __device__ __forceinline__ void flux_put(double *p, double x, double nsamp)
     else if constexpr (ACC == 1) *p = *p + x;
     else *p = (*p + x) / nsamp;
 }
-template <bool IDRV, int ACC>
+// The statistics flavour (STAT, k_flux_var): beside the sum S in the mean's array a second sum M in the variance's array, both formed
+// where the sample's value is - no array, pass or workspace of its own.  x: the value a single call would store for this sample,
+// cnt = s + 1 for sample s.  Sample 0 stores S = x, M = 0; sample s >= 1
+//     S = S + x,   t = cnt x - S  (the product rounds, then the difference),   M = M + t t / (cnt (cnt - 1))
+// (Welford's update of the sum of squared deviations written on the running sum: cnt x - S = cnt (x - mean_cnt), and cnt (cnt - 1) is
+// exact); the last sample leaves mean = S / nsamp - the bits of flux_put<2> - and var = M / (nsamp - 1), the unbiased sample variance.
+// v may be null: the mean alone.
+template <int ACC>
+__device__ __forceinline__ void flux_stat(double *p, double *v, double x, double cnt, double nsamp)
+{
+#pragma clang fp contract(off)      // (every product and quotient rounds on its own: the recurrence is stated operation by operation)
+    if constexpr (ACC == 0) { *p = x; if (v) *v = 0.0; }
+    else {
+        const double S = *p + x;
+        if constexpr (ACC == 1) *p = S; else *p = S / nsamp;
+        if (v) {
+            const double tc = cnt * x;
+            const double t = tc - S;
+            const double tt = t * t;
+            const double M = *v + tt / (cnt * (cnt - 1.0));
+            if constexpr (ACC == 1) *v = M; else *v = M / (nsamp - 1.0);
+        }
+    }
+}
+template <bool IDRV, int ACC, bool STAT = false>
 __device__ __forceinline__ void flux_body(const DevTables &T, const Workspace &W, const FluxOut &out, const double *pz, int ncol, int col0, int nct,
-                                          int clear_from_total, int ngroups, unsigned long long gsz, int clear_groups, double nsamp)
+                                          int clear_from_total, int ngroups, unsigned long long gsz, int clear_groups, double nsamp, double cnt = 1.0)
 {   // gsz: slabs per group, a nibble each (1, or - SweepArgs::split - the group's bands: added first, in their order, like the group's workgroup does)
     constexpr int NV = IDRV ? 6 : 4;                        // values of a level that change places
     __shared__ double s_v[2][NV][COLSORT_WIN];
@@ -4392,6 +4452,11 @@ __device__ __forceinline__ void flux_body(const DevTables &T, const Workspace &W
                 out.uflx[o] = u; out.dflx[o] = d; out.uflxc[o] = uc; out.dflxc[o] = dc;
                 if (out.fnet) { out.fnet[o] = u - d; out.fnetc[o] = uc - dc; }
                 if constexpr (IDRV) { out.duflx_dt[o] = du; out.duflxc_dt[o] = duc; }
+                if constexpr (STAT) { if (out.uflx_var) out.uflx_var[o] = 0.0; if (out.dflx_var) out.dflx_var[o] = 0.0; }
+            } else if constexpr (STAT) {
+                flux_stat<ACC>(out.uflx + o, out.uflx_var ? out.uflx_var + o : nullptr, u, cnt, nsamp);
+                flux_stat<ACC>(out.dflx + o, out.dflx_var ? out.dflx_var + o : nullptr, d, cnt, nsamp);
+                if constexpr (IDRV) flux_put<ACC>(out.duflx_dt + o, du, nsamp);
             } else {
                 flux_put<ACC>(out.uflx + o, u, nsamp); flux_put<ACC>(out.dflx + o, d, nsamp);
                 if constexpr (IDRV) flux_put<ACC>(out.duflx_dt + o, du, nsamp);
@@ -4402,7 +4467,9 @@ __device__ __forceinline__ void flux_body(const DevTables &T, const Workspace &W
             if constexpr (ACC == 0) {
                 out.hr[o - (size_t)nct] = T.heatfac * (nb - net) / dp;
                 out.hrc[o - (size_t)nct] = T.heatfac * (nbc - netc) / dp;
-            } else flux_put<ACC>(out.hr + (o - (size_t)nct), T.heatfac * (nb - net) / dp, nsamp);
+                if constexpr (STAT) { if (out.hr_var) out.hr_var[o - (size_t)nct] = 0.0; }
+            } else if constexpr (STAT) flux_stat<ACC>(out.hr + (o - (size_t)nct), out.hr_var ? out.hr_var + (o - (size_t)nct) : nullptr, T.heatfac * (nb - net) / dp, cnt, nsamp);
+            else flux_put<ACC>(out.hr + (o - (size_t)nct), T.heatfac * (nb - net) / dp, nsamp);
         }
         pb = p; nb = net; nbc = netc;
     };
@@ -4436,6 +4503,14 @@ __global__ __launch_bounds__(COLSORT_WIN) void k_flux_acc(DevTables T, Workspace
                                                           int clear_from_total, int ngroups, unsigned long long gsz, int clear_groups, double nsamp)
 {
     flux_body<IDRV, LAST ? 2 : 1>(T, W, out, pz, ncol, col0, nct, clear_from_total, ngroups, gsz, clear_groups, nsamp);
+}
+// ... of a call that also wants the sample variances (FluxOut::uflx_var, dflx_var, hr_var): sample 0 (ACC = 0) stores and zeroes them,
+// sample cnt - 1 adds (1), the last one adds and divides (2)
+template <bool IDRV, int ACC>
+__global__ __launch_bounds__(COLSORT_WIN) void k_flux_var(DevTables T, Workspace W, FluxOut out, const double *pz, int ncol, int col0, int nct,
+                                                          int clear_from_total, int ngroups, unsigned long long gsz, int clear_groups, double nsamp, double cnt)
+{
+    flux_body<IDRV, ACC, true>(T, W, out, pz, ncol, col0, nct, clear_from_total, ngroups, gsz, clear_groups, nsamp, cnt);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 !  Device-pointer entries for a GPU-resident Fortran host (this library's extension; include/rrtmg_lw_hip.h, "Device arrays with a column
 !  stride"; INTEGRATION.md 4g):
-!      use rrtmg_lw_device, only: rrtmg_lw_dev, rrtmg_lw_mcica_dev, rrtmg_lw_dtsfc_dev, rrtmg_lw_dev_check, rrtmg_lw_dev_status
+!      use rrtmg_lw_device, only: rrtmg_lw_dev, rrtmg_lw_mcica_dev, rrtmg_lw_dtsfc_dev, rrtmg_lw_dev_check, rrtmg_lw_dev_status, &
+!                                 rrtmg_lw_mcica_samples_dev, rrtmg_lw_alpha_dev
 !      call rrtmg_lw_dev(ncol, ld, nlay, icld, idrv, play, plev, ..., uflx, dflx, hr, uflxc, dflxc, hrc &
 !                        [, duflx_dt, duflxc_dt, uflxs, dflxs, uflxcs, dflxcs, stream])
 !      call rrtmg_lw_dev_check([stream])
@@ -29,6 +30,15 @@
 !      rrtmg_lw_dtsfc_dev(ncol, ld, nlay, plev, dtsfc, uflx, dflx, duflx_dt, uflx_adj, hr_adj &
 !                         [, uflxc, dflxc, duflxc_dt, uflxc_adj, hrc_adj, stream])
 !  is rrtmg_lw_dtsfc (module rrtmg_lw_adjust) on device arrays (rrtmg_lw_hip_adjust_tsfc_device_view).
+!      rrtmg_lw_mcica_samples_dev(ncol, ld, nlay, icld, idrv, permuteseed, nsamp, seedstep, irng, play, ..., reliq, alpha, tauaer, &
+!                                 uflx, dflx, hr, uflxc, dflxc, hrc [, duflx_dt, duflxc_dt, uflx_var, dflx_var, hr_var, stream])
+!  is rrtmg_lw_mcica_dev averaged over nsamp samples with the seeds permuteseed + s * seedstep (rrtmg_lw_hip_run_mcica_samples_device_view;
+!  module rrtmg_lw_samples states the mean): uflx, dflx, hr, duflx_dt are means, the clear-sky outputs sample 0's, and the optional
+!  uflx_var, dflx_var (ld,*) and hr_var (ld,*) receive the unbiased sample variances of uflx, dflx, hr (nsamp > 1; the standard error
+!  of a mean is sqrt(var / nsamp)).  irng must be 0 with nsamp > 1.  No spectral outputs.
+!      rrtmg_lw_alpha_dev(ncol, ld, nlay, icld, idcor, decorr_con, dz, lat, juldat, cldfrac, alpha [, stream])
+!  is get_alpha on device arrays (rrtmg_lw_hip_get_alpha_device_view): dz, cldfrac, alpha (ld,*), lat(*); alpha is what the two McICA
+!  routines above take for icld = 4 and 5.  For any other icld alpha is left alone.
       module rrtmg_lw_device
 
       use iso_c_binding
@@ -39,6 +49,7 @@
 
       private
       public :: rrtmg_lw_dev, rrtmg_lw_mcica_dev, rrtmg_lw_dtsfc_dev, rrtmg_lw_dev_check, rrtmg_lw_dev_status
+      public :: rrtmg_lw_mcica_samples_dev, rrtmg_lw_alpha_dev
 
       integer, parameter :: r4 = c_float
 
@@ -50,6 +61,13 @@
       end interface
       interface rrtmg_lw_dtsfc_dev
          module procedure rrtmg_lw_dtsfc_dev_r8, rrtmg_lw_dtsfc_dev_r4, rrtmg_lw_dtsfc_dev_r8_at, rrtmg_lw_dtsfc_dev_r4_at
+      end interface
+
+      interface rrtmg_lw_mcica_samples_dev
+         module procedure rrtmg_lw_mcica_samples_dev_r8, rrtmg_lw_mcica_samples_dev_r4, rrtmg_lw_mcica_samples_dev_r8_at, rrtmg_lw_mcica_samples_dev_r4_at
+      end interface
+      interface rrtmg_lw_alpha_dev
+         module procedure rrtmg_lw_alpha_dev_r8, rrtmg_lw_alpha_dev_r4, rrtmg_lw_alpha_dev_r8_at, rrtmg_lw_alpha_dev_r4_at
       end interface
 
       ! rrtmg_lw_hip_array_view
@@ -94,6 +112,29 @@
             type(c_ptr), value :: plev, dtsfc, uflx, dflx, duflx_dt, uflxc, dflxc, duflxc_dt, uflx_adj, hr_adj, uflxc_adj, hrc_adj, stream
             integer(c_int) :: rc
          end function rrtmg_lw_hip_adjust_tsfc_device_view
+         function rrtmg_lw_hip_run_mcica_samples_device_view(view, ncol, nlay, icld, idrv, permuteseed, nsamp, seedstep, irng, &
+               play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, &
+               inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, alpha, tauaer, &
+               uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt, uflx_var, dflx_var, hr_var, stream) &
+               bind(C, name='rrtmg_lw_hip_run_mcica_samples_device_view') result(rc)
+            import :: c_int, c_ptr, array_view
+            type(array_view), intent(in) :: view
+            integer(c_int), value :: ncol, nlay, idrv, permuteseed, nsamp, seedstep, inflglw, iceflglw, liqflglw
+            integer(c_int), intent(inout) :: icld, irng
+            type(c_ptr), value :: play, plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr
+            type(c_ptr), value :: cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, cldfr, taucld, cicewp, cliqwp, reice, reliq, alpha, tauaer
+            type(c_ptr), value :: uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt, uflx_var, dflx_var, hr_var, stream
+            integer(c_int) :: rc
+         end function rrtmg_lw_hip_run_mcica_samples_device_view
+         function rrtmg_lw_hip_get_alpha_device_view(view, ncol, nlay, icld, idcor, decorr_con, dz, lat, juldat, cldfrac, alpha, stream) &
+               bind(C, name='rrtmg_lw_hip_get_alpha_device_view') result(rc)
+            import :: c_int, c_double, c_ptr, array_view
+            type(array_view), intent(in) :: view
+            integer(c_int), value :: ncol, nlay, icld, idcor, juldat
+            real(c_double), value :: decorr_con
+            type(c_ptr), value :: dz, lat, cldfrac, alpha, stream
+            integer(c_int) :: rc
+         end function rrtmg_lw_hip_get_alpha_device_view
          function rrtmg_lw_hip_check(stream) bind(C, name='rrtmg_lw_hip_check') result(rc)
             import :: c_int, c_ptr
             type(c_ptr), value :: stream
@@ -751,6 +792,330 @@
 
       end subroutine rrtmg_lw_dtsfc_dev_r4_at
 
+      subroutine rrtmg_lw_mcica_samples_dev_r8 &
+            (ncol, ld, nlay, icld, idrv, permuteseed, nsamp, seedstep, irng, play, &
+             plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, &
+             n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, &
+             iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, &
+             alpha, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, &
+             duflx_dt, duflxc_dt, uflx_var, dflx_var, hr_var, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, idrv, inflglw, iceflglw, liqflglw
+      integer(kind=im), intent(inout) :: icld
+      integer(kind=im), intent(in) :: permuteseed, nsamp, seedstep
+      integer(kind=im), intent(inout) :: irng
+      real(kind=rb), target :: play(ld,*), plev(ld,*), tlay(ld,*), tlev(ld,*), tsfc(*), h2ovmr(ld,*)
+      real(kind=rb), target :: o3vmr(ld,*), co2vmr(ld,*), ch4vmr(ld,*), n2ovmr(ld,*), o2vmr(ld,*), cfc11vmr(ld,*)
+      real(kind=rb), target :: cfc12vmr(ld,*), cfc22vmr(ld,*), ccl4vmr(ld,*), emis(ld,*), cldfr(ld,*), taucld(16,ld,*)
+      real(kind=rb), target :: cicewp(ld,*), cliqwp(ld,*), reice(ld,*), reliq(ld,*), tauaer(ld,nlay,*)
+      real(kind=rb), target, optional :: alpha(ld,*)
+      real(kind=rb), target :: uflx(ld,*), dflx(ld,*), hr(ld,*), uflxc(ld,*), dflxc(ld,*), hrc(ld,*)
+      real(kind=rb), target, optional :: duflx_dt(ld,*), duflxc_dt(ld,*), uflx_var(ld,*), dflx_var(ld,*), hr_var(ld,*)
+      type(c_ptr), intent(in), optional :: stream
+
+      type(c_ptr) :: pin(24), pout(11)
+      integer(c_int) :: irng_c
+
+      pin = c_null_ptr
+      pout = c_null_ptr
+      pin(1) = c_loc(play)
+      pin(2) = c_loc(plev)
+      pin(3) = c_loc(tlay)
+      pin(4) = c_loc(tlev)
+      pin(5) = c_loc(tsfc)
+      pin(6) = c_loc(h2ovmr)
+      pin(7) = c_loc(o3vmr)
+      pin(8) = c_loc(co2vmr)
+      pin(9) = c_loc(ch4vmr)
+      pin(10) = c_loc(n2ovmr)
+      pin(11) = c_loc(o2vmr)
+      pin(12) = c_loc(cfc11vmr)
+      pin(13) = c_loc(cfc12vmr)
+      pin(14) = c_loc(cfc22vmr)
+      pin(15) = c_loc(ccl4vmr)
+      pin(16) = c_loc(emis)
+      pin(17) = c_loc(cldfr)
+      pin(18) = c_loc(taucld)
+      pin(19) = c_loc(cicewp)
+      pin(20) = c_loc(cliqwp)
+      pin(21) = c_loc(reice)
+      pin(22) = c_loc(reliq)
+      pin(23) = c_loc(tauaer)
+      if (present(alpha)) pin(24) = c_loc(alpha)
+      pout(1) = c_loc(uflx)
+      pout(2) = c_loc(dflx)
+      pout(3) = c_loc(hr)
+      pout(4) = c_loc(uflxc)
+      pout(5) = c_loc(dflxc)
+      pout(6) = c_loc(hrc)
+      if (present(duflx_dt)) pout(7) = c_loc(duflx_dt)
+      if (present(duflxc_dt)) pout(8) = c_loc(duflxc_dt)
+      if (present(uflx_var)) pout(9) = c_loc(uflx_var)
+      if (present(dflx_var)) pout(10) = c_loc(dflx_var)
+      if (present(hr_var)) pout(11) = c_loc(hr_var)
+      irng_c = int(irng, c_int)
+      call dev_samples(8, ncol, ld, nlay, icld, idrv, int(permuteseed, c_int), int(nsamp, c_int), int(seedstep, c_int), irng_c, &
+            inflglw, iceflglw, liqflglw, pin, pout, stream)
+      irng = int(irng_c, im)
+
+      end subroutine rrtmg_lw_mcica_samples_dev_r8
+
+      subroutine rrtmg_lw_mcica_samples_dev_r4 &
+            (ncol, ld, nlay, icld, idrv, permuteseed, nsamp, seedstep, irng, play, &
+             plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, &
+             n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, &
+             iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, &
+             alpha, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, &
+             duflx_dt, duflxc_dt, uflx_var, dflx_var, hr_var, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, idrv, inflglw, iceflglw, liqflglw
+      integer(kind=im), intent(inout) :: icld
+      integer(kind=im), intent(in) :: permuteseed, nsamp, seedstep
+      integer(kind=im), intent(inout) :: irng
+      real(kind=r4), target :: play(ld,*), plev(ld,*), tlay(ld,*), tlev(ld,*), tsfc(*), h2ovmr(ld,*)
+      real(kind=r4), target :: o3vmr(ld,*), co2vmr(ld,*), ch4vmr(ld,*), n2ovmr(ld,*), o2vmr(ld,*), cfc11vmr(ld,*)
+      real(kind=r4), target :: cfc12vmr(ld,*), cfc22vmr(ld,*), ccl4vmr(ld,*), emis(ld,*), cldfr(ld,*), taucld(16,ld,*)
+      real(kind=r4), target :: cicewp(ld,*), cliqwp(ld,*), reice(ld,*), reliq(ld,*), tauaer(ld,nlay,*)
+      real(kind=r4), target, optional :: alpha(ld,*)
+      real(kind=r4), target :: uflx(ld,*), dflx(ld,*), hr(ld,*), uflxc(ld,*), dflxc(ld,*), hrc(ld,*)
+      real(kind=r4), target, optional :: duflx_dt(ld,*), duflxc_dt(ld,*), uflx_var(ld,*), dflx_var(ld,*), hr_var(ld,*)
+      type(c_ptr), intent(in), optional :: stream
+
+      type(c_ptr) :: pin(24), pout(11)
+      integer(c_int) :: irng_c
+
+      pin = c_null_ptr
+      pout = c_null_ptr
+      pin(1) = c_loc(play)
+      pin(2) = c_loc(plev)
+      pin(3) = c_loc(tlay)
+      pin(4) = c_loc(tlev)
+      pin(5) = c_loc(tsfc)
+      pin(6) = c_loc(h2ovmr)
+      pin(7) = c_loc(o3vmr)
+      pin(8) = c_loc(co2vmr)
+      pin(9) = c_loc(ch4vmr)
+      pin(10) = c_loc(n2ovmr)
+      pin(11) = c_loc(o2vmr)
+      pin(12) = c_loc(cfc11vmr)
+      pin(13) = c_loc(cfc12vmr)
+      pin(14) = c_loc(cfc22vmr)
+      pin(15) = c_loc(ccl4vmr)
+      pin(16) = c_loc(emis)
+      pin(17) = c_loc(cldfr)
+      pin(18) = c_loc(taucld)
+      pin(19) = c_loc(cicewp)
+      pin(20) = c_loc(cliqwp)
+      pin(21) = c_loc(reice)
+      pin(22) = c_loc(reliq)
+      pin(23) = c_loc(tauaer)
+      if (present(alpha)) pin(24) = c_loc(alpha)
+      pout(1) = c_loc(uflx)
+      pout(2) = c_loc(dflx)
+      pout(3) = c_loc(hr)
+      pout(4) = c_loc(uflxc)
+      pout(5) = c_loc(dflxc)
+      pout(6) = c_loc(hrc)
+      if (present(duflx_dt)) pout(7) = c_loc(duflx_dt)
+      if (present(duflxc_dt)) pout(8) = c_loc(duflxc_dt)
+      if (present(uflx_var)) pout(9) = c_loc(uflx_var)
+      if (present(dflx_var)) pout(10) = c_loc(dflx_var)
+      if (present(hr_var)) pout(11) = c_loc(hr_var)
+      irng_c = int(irng, c_int)
+      call dev_samples(4, ncol, ld, nlay, icld, idrv, int(permuteseed, c_int), int(nsamp, c_int), int(seedstep, c_int), irng_c, &
+            inflglw, iceflglw, liqflglw, pin, pout, stream)
+      irng = int(irng_c, im)
+
+      end subroutine rrtmg_lw_mcica_samples_dev_r4
+
+      subroutine rrtmg_lw_mcica_samples_dev_r8_at &
+            (ncol, ld, nlay, icld, idrv, permuteseed, nsamp, seedstep, irng, play, &
+             plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, &
+             n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, &
+             iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, &
+             alpha, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, &
+             duflx_dt, duflxc_dt, uflx_var, dflx_var, hr_var, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, idrv, inflglw, iceflglw, liqflglw
+      integer(kind=im), intent(inout) :: icld
+      integer(kind=im), intent(in) :: permuteseed, nsamp, seedstep
+      integer(kind=im), intent(inout) :: irng
+      real(kind=rb), target :: play, plev, tlay, tlev, tsfc, h2ovmr
+      real(kind=rb), target :: o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr
+      real(kind=rb), target :: cfc12vmr, cfc22vmr, ccl4vmr, emis, cldfr, taucld
+      real(kind=rb), target :: cicewp, cliqwp, reice, reliq, tauaer
+      real(kind=rb), target, optional :: alpha
+      real(kind=rb), target :: uflx, dflx, hr, uflxc, dflxc, hrc
+      real(kind=rb), target, optional :: duflx_dt, duflxc_dt, uflx_var, dflx_var, hr_var
+      type(c_ptr), intent(in), optional :: stream
+
+      type(c_ptr) :: pin(24), pout(11)
+      integer(c_int) :: irng_c
+
+      pin = c_null_ptr
+      pout = c_null_ptr
+      pin(1) = c_loc(play)
+      pin(2) = c_loc(plev)
+      pin(3) = c_loc(tlay)
+      pin(4) = c_loc(tlev)
+      pin(5) = c_loc(tsfc)
+      pin(6) = c_loc(h2ovmr)
+      pin(7) = c_loc(o3vmr)
+      pin(8) = c_loc(co2vmr)
+      pin(9) = c_loc(ch4vmr)
+      pin(10) = c_loc(n2ovmr)
+      pin(11) = c_loc(o2vmr)
+      pin(12) = c_loc(cfc11vmr)
+      pin(13) = c_loc(cfc12vmr)
+      pin(14) = c_loc(cfc22vmr)
+      pin(15) = c_loc(ccl4vmr)
+      pin(16) = c_loc(emis)
+      pin(17) = c_loc(cldfr)
+      pin(18) = c_loc(taucld)
+      pin(19) = c_loc(cicewp)
+      pin(20) = c_loc(cliqwp)
+      pin(21) = c_loc(reice)
+      pin(22) = c_loc(reliq)
+      pin(23) = c_loc(tauaer)
+      if (present(alpha)) pin(24) = c_loc(alpha)
+      pout(1) = c_loc(uflx)
+      pout(2) = c_loc(dflx)
+      pout(3) = c_loc(hr)
+      pout(4) = c_loc(uflxc)
+      pout(5) = c_loc(dflxc)
+      pout(6) = c_loc(hrc)
+      if (present(duflx_dt)) pout(7) = c_loc(duflx_dt)
+      if (present(duflxc_dt)) pout(8) = c_loc(duflxc_dt)
+      if (present(uflx_var)) pout(9) = c_loc(uflx_var)
+      if (present(dflx_var)) pout(10) = c_loc(dflx_var)
+      if (present(hr_var)) pout(11) = c_loc(hr_var)
+      irng_c = int(irng, c_int)
+      call dev_samples(8, ncol, ld, nlay, icld, idrv, int(permuteseed, c_int), int(nsamp, c_int), int(seedstep, c_int), irng_c, &
+            inflglw, iceflglw, liqflglw, pin, pout, stream)
+      irng = int(irng_c, im)
+
+      end subroutine rrtmg_lw_mcica_samples_dev_r8_at
+
+      subroutine rrtmg_lw_mcica_samples_dev_r4_at &
+            (ncol, ld, nlay, icld, idrv, permuteseed, nsamp, seedstep, irng, play, &
+             plev, tlay, tlev, tsfc, h2ovmr, o3vmr, co2vmr, ch4vmr, &
+             n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, inflglw, &
+             iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, &
+             alpha, tauaer, uflx, dflx, hr, uflxc, dflxc, hrc, &
+             duflx_dt, duflxc_dt, uflx_var, dflx_var, hr_var, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, idrv, inflglw, iceflglw, liqflglw
+      integer(kind=im), intent(inout) :: icld
+      integer(kind=im), intent(in) :: permuteseed, nsamp, seedstep
+      integer(kind=im), intent(inout) :: irng
+      real(kind=r4), target :: play, plev, tlay, tlev, tsfc, h2ovmr
+      real(kind=r4), target :: o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr
+      real(kind=r4), target :: cfc12vmr, cfc22vmr, ccl4vmr, emis, cldfr, taucld
+      real(kind=r4), target :: cicewp, cliqwp, reice, reliq, tauaer
+      real(kind=r4), target, optional :: alpha
+      real(kind=r4), target :: uflx, dflx, hr, uflxc, dflxc, hrc
+      real(kind=r4), target, optional :: duflx_dt, duflxc_dt, uflx_var, dflx_var, hr_var
+      type(c_ptr), intent(in), optional :: stream
+
+      type(c_ptr) :: pin(24), pout(11)
+      integer(c_int) :: irng_c
+
+      pin = c_null_ptr
+      pout = c_null_ptr
+      pin(1) = c_loc(play)
+      pin(2) = c_loc(plev)
+      pin(3) = c_loc(tlay)
+      pin(4) = c_loc(tlev)
+      pin(5) = c_loc(tsfc)
+      pin(6) = c_loc(h2ovmr)
+      pin(7) = c_loc(o3vmr)
+      pin(8) = c_loc(co2vmr)
+      pin(9) = c_loc(ch4vmr)
+      pin(10) = c_loc(n2ovmr)
+      pin(11) = c_loc(o2vmr)
+      pin(12) = c_loc(cfc11vmr)
+      pin(13) = c_loc(cfc12vmr)
+      pin(14) = c_loc(cfc22vmr)
+      pin(15) = c_loc(ccl4vmr)
+      pin(16) = c_loc(emis)
+      pin(17) = c_loc(cldfr)
+      pin(18) = c_loc(taucld)
+      pin(19) = c_loc(cicewp)
+      pin(20) = c_loc(cliqwp)
+      pin(21) = c_loc(reice)
+      pin(22) = c_loc(reliq)
+      pin(23) = c_loc(tauaer)
+      if (present(alpha)) pin(24) = c_loc(alpha)
+      pout(1) = c_loc(uflx)
+      pout(2) = c_loc(dflx)
+      pout(3) = c_loc(hr)
+      pout(4) = c_loc(uflxc)
+      pout(5) = c_loc(dflxc)
+      pout(6) = c_loc(hrc)
+      if (present(duflx_dt)) pout(7) = c_loc(duflx_dt)
+      if (present(duflxc_dt)) pout(8) = c_loc(duflxc_dt)
+      if (present(uflx_var)) pout(9) = c_loc(uflx_var)
+      if (present(dflx_var)) pout(10) = c_loc(dflx_var)
+      if (present(hr_var)) pout(11) = c_loc(hr_var)
+      irng_c = int(irng, c_int)
+      call dev_samples(4, ncol, ld, nlay, icld, idrv, int(permuteseed, c_int), int(nsamp, c_int), int(seedstep, c_int), irng_c, &
+            inflglw, iceflglw, liqflglw, pin, pout, stream)
+      irng = int(irng_c, im)
+
+      end subroutine rrtmg_lw_mcica_samples_dev_r4_at
+
+      subroutine rrtmg_lw_alpha_dev_r8 &
+            (ncol, ld, nlay, icld, idcor, decorr_con, dz, lat, juldat, cldfrac, alpha, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, icld, idcor, juldat
+      real(kind=rb), intent(in) :: decorr_con
+      real(kind=rb), target :: dz(ld,*), lat(*), cldfrac(ld,*), alpha(ld,*)
+      type(c_ptr), intent(in), optional :: stream
+
+      call dev_alpha(8, ncol, ld, nlay, icld, idcor, real(decorr_con, c_double), c_loc(dz), c_loc(lat), juldat, c_loc(cldfrac), &
+            c_loc(alpha), stream)
+
+      end subroutine rrtmg_lw_alpha_dev_r8
+
+      subroutine rrtmg_lw_alpha_dev_r4 &
+            (ncol, ld, nlay, icld, idcor, decorr_con, dz, lat, juldat, cldfrac, alpha, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, icld, idcor, juldat
+      real(kind=r4), intent(in) :: decorr_con
+      real(kind=r4), target :: dz(ld,*), lat(*), cldfrac(ld,*), alpha(ld,*)
+      type(c_ptr), intent(in), optional :: stream
+
+      call dev_alpha(4, ncol, ld, nlay, icld, idcor, real(decorr_con, c_double), c_loc(dz), c_loc(lat), juldat, c_loc(cldfrac), &
+            c_loc(alpha), stream)
+
+      end subroutine rrtmg_lw_alpha_dev_r4
+
+      subroutine rrtmg_lw_alpha_dev_r8_at &
+            (ncol, ld, nlay, icld, idcor, decorr_con, dz, lat, juldat, cldfrac, alpha, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, icld, idcor, juldat
+      real(kind=rb), intent(in) :: decorr_con
+      real(kind=rb), target :: dz, lat, cldfrac, alpha
+      type(c_ptr), intent(in), optional :: stream
+
+      call dev_alpha(8, ncol, ld, nlay, icld, idcor, real(decorr_con, c_double), c_loc(dz), c_loc(lat), juldat, c_loc(cldfrac), &
+            c_loc(alpha), stream)
+
+      end subroutine rrtmg_lw_alpha_dev_r8_at
+
+      subroutine rrtmg_lw_alpha_dev_r4_at &
+            (ncol, ld, nlay, icld, idcor, decorr_con, dz, lat, juldat, cldfrac, alpha, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, icld, idcor, juldat
+      real(kind=r4), intent(in) :: decorr_con
+      real(kind=r4), target :: dz, lat, cldfrac, alpha
+      type(c_ptr), intent(in), optional :: stream
+
+      call dev_alpha(4, ncol, ld, nlay, icld, idcor, real(decorr_con, c_double), c_loc(dz), c_loc(lat), juldat, c_loc(cldfrac), &
+            c_loc(alpha), stream)
+
+      end subroutine rrtmg_lw_alpha_dev_r4_at
+
       ! what every specific of rrtmg_lw_dev / rrtmg_lw_mcica_dev ends in: the addresses in the C entry's order - pin: the 23 input arrays
       ! of rrtmg_lw, then alpha; pout: the eight broadband outputs, then the spectral four (null where absent)
       subroutine dev_solve(who, real_bytes, mcica, ncol, ld, nlay, icld, idrv, permuteseed, irng, inflglw, iceflglw, liqflglw, pin, pout, stream)
@@ -786,6 +1151,53 @@
       if (rc /= 0) call rrtmg_lw_hip_abort(who)
       icld = int(icld_c, im)
       end subroutine dev_solve
+
+      ! ... of rrtmg_lw_mcica_samples_dev: pin as above; pout: the eight broadband outputs, then uflx_var, dflx_var, hr_var
+      subroutine dev_samples(real_bytes, ncol, ld, nlay, icld, idrv, permuteseed, nsamp, seedstep, irng, inflglw, iceflglw, liqflglw, pin, pout, stream)
+      integer, intent(in) :: real_bytes
+      integer(kind=im), intent(in) :: ncol, ld, nlay, idrv, inflglw, iceflglw, liqflglw
+      integer(kind=im), intent(inout) :: icld
+      integer(c_int), intent(in) :: permuteseed, nsamp, seedstep
+      integer(c_int), intent(inout) :: irng
+      type(c_ptr), intent(in) :: pin(24), pout(11)
+      type(c_ptr), intent(in), optional :: stream
+
+      type(array_view) :: view
+      type(c_ptr) :: s
+      integer(c_int) :: rc, icld_c
+
+      view = array_view(int(real_bytes, c_int), 0_c_int, 0_c_int, int(ld, c_int))
+      s = c_null_ptr
+      if (present(stream)) s = stream
+      icld_c = int(icld, c_int)
+      rc = rrtmg_lw_hip_run_mcica_samples_device_view(view, int(ncol, c_int), int(nlay, c_int), icld_c, int(idrv, c_int), permuteseed, nsamp, &
+            seedstep, irng, &
+            pin(1), pin(2), pin(3), pin(4), pin(5), pin(6), pin(7), pin(8), pin(9), pin(10), pin(11), pin(12), pin(13), pin(14), pin(15), &
+            pin(16), int(inflglw, c_int), int(iceflglw, c_int), int(liqflglw, c_int), pin(17), pin(18), pin(19), pin(20), pin(21), pin(22), &
+            pin(24), pin(23), pout(1), pout(2), pout(3), pout(4), pout(5), pout(6), pout(7), pout(8), pout(9), pout(10), pout(11), s)
+      if (rc /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_mcica_samples_dev')
+      icld = int(icld_c, im)
+      end subroutine dev_samples
+
+      ! ... of rrtmg_lw_alpha_dev
+      subroutine dev_alpha(real_bytes, ncol, ld, nlay, icld, idcor, decorr_con, dz, lat, juldat, cldfrac, alpha, stream)
+      integer, intent(in) :: real_bytes
+      integer(kind=im), intent(in) :: ncol, ld, nlay, icld, idcor, juldat
+      real(c_double), intent(in) :: decorr_con
+      type(c_ptr), intent(in) :: dz, lat, cldfrac, alpha
+      type(c_ptr), intent(in), optional :: stream
+
+      type(array_view) :: view
+      type(c_ptr) :: s
+      integer(c_int) :: rc
+
+      view = array_view(int(real_bytes, c_int), 0_c_int, 0_c_int, int(ld, c_int))
+      s = c_null_ptr
+      if (present(stream)) s = stream
+      rc = rrtmg_lw_hip_get_alpha_device_view(view, int(ncol, c_int), int(nlay, c_int), int(icld, c_int), int(idcor, c_int), decorr_con, &
+            dz, lat, int(juldat, c_int), cldfrac, alpha, s)
+      if (rc /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_alpha_dev')
+      end subroutine dev_alpha
 
       ! ... and of rrtmg_lw_dtsfc_dev: p in the C entry's order (plev, dtsfc, uflx, dflx, duflx_dt, uflxc, dflxc, duflxc_dt, the four outputs)
       subroutine dev_adjust(real_bytes, ncol, ld, nlay, p, stream)

@@ -763,6 +763,65 @@ int rrtmg_lw_hip_run_mcica_samples_device_view(const rrtmg_lw_hip_array_view *vi
 int rrtmg_lw_hip_get_alpha_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, int icld, int idcor, double decorr_con,
     const void *dz, const void *lat, int juldat, const void *cldfrac, void *alpha, void *stream);
 
+/* ---- Cloud cover as the McICA sub-columns realise it -----------------------------------------------------------------------------------
+ * The fused entries (rrtmg_lw_hip_run_mcica_subcol*, rrtmg_lw_hip_run_mcica_samples*) draw their sub-columns on the device and keep them
+ * as a packed mask only.  These three entries run the same generator stage - deterministic in (icld, permuteseed, irng, play, cldfr,
+ * alpha) - and count that mask, so they report exactly the clouds a fused call with the same arguments saw: a model that diagnoses total
+ * or low / mid / high cover inside radiation gets numbers that agree with the fluxes, a satellite simulator gets the sub-columns
+ * themselves, and neither materialises the (NG, ncol, nlay) arrays of rrtmg_lw_hip_mcica_subcol (about 80 KB per 72-layer column for
+ * cldfmcl alone, against 20 bytes per column and layer of mask).  No solver kernel runs.
+ * With NG = rrtmg_lw_hip_gpoints(), sample s drawn with the seed permuteseed + s * seedstep as the averaging entries define it, and
+ * c(i, k, g, s) in {0, 1} the generator's cldfmcl of column i, layer k (layer 1 at the surface), sub-column g:
+ *     cldtot  (ncol)          the pairs (g, s) with c = 1 in at least one layer, / (NG * nsamp)
+ *     cldcum  (ncol,nlay)     for layer k the pairs with c = 1 in some layer k' >= k, / (NG * nsamp): the cover seen from the top of the
+ *                             atmosphere down to and including layer k.  cldcum(:,1) = cldtot; it does not increase with k.  High /
+ *                             mid / low cover as seen from above are differences of its rows: with k_hi and k_mid the lowest layers
+ *                             of the high and the middle deck, high = cldcum(:,k_hi), mid = cldcum(:,k_mid) - cldcum(:,k_hi) (what
+ *                             the middle deck adds below the high one), low = cldtot - cldcum(:,k_mid); the three add up to cldtot
+ *     cldlay  (ncol,nlay)     the pairs with c(i, k, g, s) = 1, / (NG * nsamp): the realised layer fraction, to be held against cldfr
+ *     submask (ncol,nlay,MW)  unsigned 32-bit, MW = (NG + 31) / 32: bit (g mod 32) of word g / 32 is c(i, k, g, 0); the bits at and
+ *                             above NG are zero.  With nsamp = 1 only.
+ * Each output may be NULL - it is then neither formed nor touched -, at least one must be given.  Every count is an exact integer and
+ * every value ONE IEEE float64 division (double)count / (double)(NG * nsamp) - not a multiplication by a reciprocal -, for a float32
+ * array rounded once more with (float): any implementation of the definitions agrees bit for bit.
+ * icld, irng (in/out: any non-zero value becomes 1), the limits of nlay and alpha (NULL unless icld is 4 or 5) are those of
+ * rrtmg_lw_hip_mcica_subcol_device; icld = 0 writes exact zeros to every given output (radiation saw no cloud) and reads no input.
+ * nsamp and seedstep follow rrtmg_lw_hip_run_mcica_samples, with its error texts: nsamp in 1 .. RRTMG_LW_HIP_MAX_SAMPLES, seedstep >= 1,
+ * the last seed an int, *irng = 0 with nsamp > 1.  RRTMG_LW_HIP_EARG as well, with a text that names the argument: all four outputs
+ * NULL, submask together with nsamp > 1, play or cldfr NULL (icld != 0), alpha NULL with icld 4 / 5.  Every such case is found before
+ * any output is written.
+ * Device entries: DEVICE pointers, the device is that of play (rrtmg_lw_hip_init_devices; with icld = 0 and play NULL that of the
+ * first output given); they enqueue on `stream` and do not
+ * synchronise, a physics error (kissvec: pressures that do not decrease upward) surfaces through rrtmg_lw_hip_check(stream).  The masks
+ * of all columns of the call are drawn at once into the buffer the fused entries use (20 B per column and layer, 32 in the g256
+ * library; counted by rrtmg_lw_hip_workspace_bytes), the jump tables are the fused entries' - a seed they have seen rebuilds nothing,
+ * and the other way round.  Per sample the generator and one counting kernel run; the counts add up in the output arrays (sample 0
+ * stores, the others add, the last one adds and divides: counts are at most 256 x 64, exact in float32 too), which are never read
+ * before they are written.  The entry lock, no graph replay, no combining with other calls, no column batches (rrtmg_lw_hip_set_batch
+ * does not apply).
+ * rrtmg_lw_hip_mcica_cloud_cover_device_view: inputs and floating-point outputs in the view's form ("Device arrays with a column
+ * stride", above) exactly as rrtmg_lw_hip_get_alpha_device_view takes (ncol,nlay) arrays; cldtot is per column, like tsfc.  submask is
+ * always unsigned 32-bit: (ld, nlay, MW) column-fastest - word w of layer k of column i at i + ld * (k + nlay * w) -, or, with
+ * layer_fastest = 1, (ncol, nlay, MW) in C order - at (i * nlay + k) * MW + w.  With top_first = 1 the vertical index k is flipped in
+ * both layouts, as in every other array; "this layer or any above it" is physical and does not flip.  {8, 0, 0, ld} runs on the caller's
+ * arrays in place (irng = 1 with ld > ncol copies play, cldfr and alpha call-wide first, as the fused view entry does); a converting
+ * form stages those three call-wide in float64 and the counting kernel writes the outputs in the form directly.  Nothing outside the
+ * call's ncol columns is read into a result or written.
+ * rrtmg_lw_hip_mcica_cloud_cover: HOST pointers, reference layout.  The first device, no fan-out over several devices.  It allocates
+ * one device buffer for the call - play, cldfr, alpha (icld 4 / 5) and the outputs that are given: 8 B per column and layer each, 8 B
+ * per column for cldtot, 4 MW B per column and layer for submask - beside the mask buffer, releases it when it returns, and copies
+ * the outputs back.  Synchronises. */
+int rrtmg_lw_hip_mcica_cloud_cover(int ncol, int nlay, int icld, int permuteseed, int nsamp, int seedstep, int *irng,
+    const double *play, const double *cldfr, const double *alpha,
+    double *cldtot, double *cldcum, double *cldlay, unsigned *submask);
+int rrtmg_lw_hip_mcica_cloud_cover_device(int ncol, int nlay, int icld, int permuteseed, int nsamp, int seedstep, int *irng,
+    const double *play, const double *cldfr, const double *alpha,
+    double *cldtot, double *cldcum, double *cldlay, unsigned *submask, void *stream);
+int rrtmg_lw_hip_mcica_cloud_cover_device_view(const rrtmg_lw_hip_array_view *view,
+    int ncol, int nlay, int icld, int permuteseed, int nsamp, int seedstep, int *irng,
+    const void *play, const void *cldfr, const void *alpha,
+    void *cldtot, void *cldcum, void *cldlay, unsigned *submask, void *stream);
+
 /* ---- Host arrays of a host built with 4-byte reals ("_r4") ----------------------------------------------------------------------------
  * A host model that carries RRTMG_LW at the default real kind (no -r8) owns float arrays.  These four entries take them as they are:
  * HOST pointers, every floating-point array of the call - inputs and outputs, alpha too - `float`.  Layout, argument order, the in/out

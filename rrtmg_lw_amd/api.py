@@ -940,6 +940,77 @@ def get_alpha_device(d, alpha, icld, idcor, decorr_con, juldat, stream=None, for
     return alpha
 
 
+_COVER_OUT = ("cldtot", "cldcum", "cldlay", "submask")
+
+
+def mask_words():
+    """32-bit words of a sub-column mask: (gpoints() + 31) // 32"""
+    return (gpoints() + 31) // 32
+
+
+def mcica_cloud_cover(ncol, nlay, icld, permuteseed, irng, play, cldfrac, alpha=None, nsamp=1, seedstep=None,
+                      outputs=("cldtot", "cldcum", "cldlay")):
+    """Cloud cover as the McICA sub-columns realise it (rrtmg_lw_hip_mcica_cloud_cover; include/rrtmg_lw_hip.h states the definitions):
+    the generator stage of the fused entries with the same (icld, permuteseed, irng, play, cldfrac, alpha), counted.  numpy arrays
+    (ncol, nlay) as for mcica_subcol_lw; nsamp samples with the seeds permuteseed + s * seedstep (seedstep=None: gpoints()).
+    `outputs`: which of cldtot (ncol,), cldcum, cldlay (ncol, nlay) - float64 - and submask (ncol, nlay, mask_words()), uint32, nsamp = 1
+    only, to form.  Returns a dict of them (Fortran-ordered) and irng as the library left it."""
+    outputs = tuple(outputs)
+    for k in outputs:
+        if k not in _COVER_OUT:
+            raise ValueError(f"unknown output {k!r}: one of {_COVER_OUT}")
+    shapes = {"cldtot": (ncol,), "cldcum": (ncol, nlay), "cldlay": (ncol, nlay), "submask": (ncol, nlay, mask_words())}
+    o = {k: np.zeros(shapes[k], dtype=np.uint32 if k == "submask" else np.float64, order="F") for k in outputs}
+    irng_c = C.c_int(int(irng))
+    null = C.cast(None, _dp)
+    opt = lambda a: _p(_f(a, (ncol, nlay))) if a is not None else null
+    seedstep = gpoints() if seedstep is None else int(seedstep)
+    _check(lib().rrtmg_lw_hip_mcica_cloud_cover(C.c_int(ncol), C.c_int(nlay), C.c_int(int(icld)), C.c_int(int(permuteseed)),
+                                                C.c_int(int(nsamp)), C.c_int(seedstep), C.byref(irng_c), opt(play), opt(cldfrac), opt(alpha),
+                                                *[_p(o[k]) if k in o else null for k in _COVER_OUT]))
+    o["irng"] = irng_c.value
+    return o
+
+
+def mcica_cloud_cover_device(d, out, icld, permuteseed, irng=0, alpha=None, nsamp=1, seedstep=None, stream=None, form=None, ld=None):
+    """Device-resident mcica_cloud_cover: `d` holds torch CUDA tensors play and cldfr (ncol, nlay) - and ncol, nlay -, `alpha` the one
+    of the exponential overlaps, `out` the preallocated output tensors: those of cldtot (ncol,), cldcum, cldlay (ncol, nlay) and submask
+    that it holds are formed, the others are not.  form / ld as in get_alpha_device (rrtmg_lw_hip_mcica_cloud_cover_device_view); with
+    neither the plain rrtmg_lw_hip_mcica_cloud_cover_device.  submask is an int32 (or uint32) tensor of logical shape
+    (ncol, nlay, mask_words()): stored column-fastest - strides (1, ld, ld * nlay) -, or C-contiguous with a layer_fastest form.
+    Enqueues on `stream`, does not synchronise (check(stream) collects a physics error).  Returns irng as the library left it."""
+    import torch
+    ncol, nlay = int(d["ncol"]), int(d["nlay"])
+    for k in out:
+        if k not in _COVER_OUT:
+            raise ValueError(f"unknown output {k!r}: one of {_COVER_OUT}")
+    cldfr = d["cldfr"] if d.get("cldfr") is not None else d.get("cldfrac")
+    tensors = {"play": d.get("play"), "cldfr": cldfr, "alpha": alpha}
+    tensors.update({k: out.get(k) for k in ("cldtot", "cldcum", "cldlay")})
+    view = _checked_view(form, ld or 0, ncol, nlay, tensors)
+    sub = out.get("submask")
+    if sub is not None:
+        from . import arrays
+        f = arrays.ArrayForm(*(form if form is not None else arrays.REFERENCE))
+        w = arrays.check_ld(ncol, ld, f)
+        mw = mask_words()
+        if sub.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+            raise TypeError(f"'submask' is {sub.dtype}: 32-bit words (torch.int32 or torch.uint32)")
+        need = (nlay * mw, mw, 1) if f.layer_fastest else (1, w, w * nlay)
+        if tuple(sub.shape) != (ncol, nlay, mw) or any(n > 1 and a != b for n, a, b in zip(sub.shape, sub.stride(), need)):
+            raise ValueError(f"'submask' has shape {tuple(sub.shape)} and strides {tuple(sub.stride())}: needs {(ncol, nlay, mw)} with strides {need}")
+    seedstep = gpoints() if seedstep is None else int(seedstep)
+    irng_c = C.c_int(int(irng))
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    args = [C.c_int(ncol), C.c_int(nlay), C.c_int(int(icld)), C.c_int(int(permuteseed)), C.c_int(int(nsamp)), C.c_int(seedstep), C.byref(irng_c),
+            ptr(d.get("play")), ptr(cldfr), ptr(alpha)] + [ptr(out.get(k)) for k in _COVER_OUT] + [C.c_void_p(stream or 0)]
+    if form is None and ld is None:
+        _check(lib().rrtmg_lw_hip_mcica_cloud_cover_device(*args))
+    else:
+        _check(lib().rrtmg_lw_hip_mcica_cloud_cover_device_view(view, *args))
+    return irng_c.value
+
+
 def run_columns_mcica(cols, subs, istart=1, iend=16, icld=None, idrv=None):
     """Prepared-column McICA entry: cols[k] (rrtmg_lw_amd.io_rrtm.read_input_rrtm dicts) with sub-columns subs[k] =
     dict(cldfmc, taucmc, ciwpmc, clwpmc (140, nlayers), reicmc, relqmc (nlayers)); one (column, sample) pair per entry.

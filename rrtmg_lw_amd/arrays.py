@@ -14,6 +14,8 @@ column index fastest, vertical index 0 at the surface, logical shapes as the For
     tsfc                                                                            (ncol,)
     dz (ncol, nlay), lat (ncol,)                                                    get_alpha's inputs (api.get_alpha_device)
     uflx_var, dflx_var (ncol, nlay+1), hr_var (ncol, nlay)                          sample variances (api.rrtmg_lw_mcica_samples_device)
+    cldtot (ncol,), cldcum, cldlay (ncol, nlay)                                     realised cloud cover (api.mcica_cloud_cover_device;
+                                                                                    its submask is uint32 and has a layout of its own)
 
 An ArrayForm(real_bytes, layer_fastest, top_first) describes what a device-resident caller holds instead:
 
@@ -48,12 +50,12 @@ import numpy as np
 NBND = 16
 
 LAYER_ARRAYS = ("play", "tlay", "h2ovmr", "o3vmr", "co2vmr", "ch4vmr", "n2ovmr", "o2vmr", "cfc11vmr", "cfc12vmr", "cfc22vmr",
-                "ccl4vmr", "cldfr", "cicewp", "cliqwp", "reice", "reliq", "alpha", "hr", "hrc", "hr_adj", "hrc_adj", "dz", "hr_var")
+                "ccl4vmr", "cldfr", "cicewp", "cliqwp", "reice", "reliq", "alpha", "hr", "hrc", "hr_adj", "hrc_adj", "dz", "hr_var", "cldcum", "cldlay")
 LEVEL_ARRAYS = ("plev", "tlev", "uflx", "dflx", "uflxc", "dflxc", "duflx_dt", "duflxc_dt", "uflx_adj", "uflxc_adj", "uflx_var", "dflx_var")
 BAND_ARRAYS = ("emis", "plankbnd", "dplankbnd_dt")                      # (ncol, 16): no vertical axis
 LAYER_X_ARRAYS = ("tauaer", "planklay", "taug", "fracs")                # (ncol, nlay, 16 | NG)
 LEVEL_X_ARRAYS = ("planklev", "uflxs", "dflxs", "uflxcs", "dflxcs")      # (ncol, nlay+1, 16)
-COLUMN_ARRAYS = ("tsfc", "dtsfc", "lat")
+COLUMN_ARRAYS = ("tsfc", "dtsfc", "lat", "cldtot")
 ALL_ARRAYS = LAYER_ARRAYS + LEVEL_ARRAYS + BAND_ARRAYS + LAYER_X_ARRAYS + LEVEL_X_ARRAYS + COLUMN_ARRAYS + ("taucld",)
 
 

@@ -4531,6 +4531,88 @@ int view_check(const rrtmg_lw_hip_array_view *v, int ncol, rrtmg_lw_hip_array_fo
     return 0;
 }
 
+// ---- cloud cover as the sub-columns realise it (rrtmg_lw_hip_mcica_cloud_cover*, k_cloudcover) -----------------------------------------
+// The generator stage of the fused entries - prepare_mask / launch_kiss with the seeds permuteseed + i seedstep, or generate_mask for
+// the Mersenne Twister - for ALL columns of the call at once, and per sample one k_cloudcover launch that counts the mask into the
+// caller's arrays.  No solver kernel runs; the mask buffer is the fused entries' (G.mask), so the call ends in G.ev_last like theirs.
+struct CoverOut { void *cldtot, *cldcum, *cldlay; unsigned *submask; };
+
+// what the three entries check, in this order, before anything is allocated or enqueued (the pointers: the caller's, host or device)
+int check_cover(int ncol, int nlay, int icld, int permuteseed, int nsamp, int seedstep, int *irng, const void *play, const void *cldfr,
+                const void *alpha, const CoverOut &o)
+{
+    if (int rc = check_mcica_build()) return rc;
+    if (int rc = check_subcol_args(ncol, nlay, icld, irng)) return rc;
+    CallDesc d{ncol, nlay, nullptr, 0, 0, 0, 0, permuteseed, irng};
+    if (int rc = check_samples(d, nsamp, seedstep)) return rc;
+    if (!o.cldtot && !o.cldcum && !o.cldlay && !o.submask)
+        return fail(RRTMG_LW_HIP_EARG, "cloud cover: cldtot, cldcum, cldlay and submask are all null - at least one output");
+    if (o.submask && nsamp > 1) return fail(RRTMG_LW_HIP_EARG, "cloud cover: submask with nsamp = %d: the mask is that of ONE sample (pass NULL, or nsamp = 1)", nsamp);
+    if (icld == 0) return 0;                                      // (nothing is drawn, nothing is read)
+    if (!play) return fail(RRTMG_LW_HIP_EARG, "cloud cover: null input array (play)");
+    if (!cldfr) return fail(RRTMG_LW_HIP_EARG, "cloud cover: null input array (cldfr)");
+    if ((icld == 4 || icld == 5) && !alpha) return fail(RRTMG_LW_HIP_EARG, "icld = 4/5 needs alpha");
+    if (nlay < 4 && *irng == 0) return fail(RRTMG_LW_HIP_EARG, "the kissvec generator needs at least four layers");
+    return 0;
+}
+
+// the call on stream s from DEVICE arrays in the form f, ld columns wide; checked (check_cover), the caller holds the entry lock
+int cover_launch(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, int ld, int icld, int permuteseed, int nsamp, int seedstep, int irng,
+                 const void *play, const void *cldfr, const void *alpha, const CoverOut &o, hipStream_t s)
+{
+    const bool cloud = icld != 0, two = icld == 4 || icld == 5;
+    const bool plain = f.real_bytes == 8 && !f.layer_fastest && !f.top_first;
+    const size_t L = (size_t)nlay, n = (size_t)ncol;
+    if (int rc = ensure_pipeline()) return rc;
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));      // an earlier call, possibly on another stream, still owns the mask and the staging
+    // the generator's inputs: the caller's own where they are float64 reference-form arrays - the kissvec kernels take their width, the
+    // Mersenne-Twister ones arrays as wide as the call -, staged call-wide otherwise, as the fused *_view entries stage them
+    const double *gp = (const double *)play, *gc = (const double *)cldfr, *ga = two ? (const double *)alpha : nullptr;
+    int gw = ld;
+    if (cloud && (!plain || (irng != 0 && ld != ncol))) {
+        std::vector<FormItem> gen = {form_item(play, A_PLAY, L), form_item(cldfr, A_CLDFR, L)};
+        if (two) gen.push_back(form_item(alpha, A_ALPHA, L));
+        std::vector<double *> sg;
+        const size_t need = form_place(gen, n, nullptr, sg);
+        if (int rc = ensure_form(G.form_gen, need * 8)) return rc;
+        form_place(gen, n, G.form_gen.as<double>(), sg);
+        if (int rc = form_launch(s, true, f, gen, sg, (size_t)ld, 0, n)) return rc;
+        gp = sg[0]; gc = sg[1]; ga = two ? sg[2] : nullptr;
+        gw = ncol;
+    }
+    if (cloud && irng == 0) if (int rc = prepare_mask(ncol, nlay, icld, 0, ga)) return rc;
+    CoverArgs a{};
+    a.cldtot = o.cldtot; a.cldcum = o.cldcum; a.cldlay = o.cldlay; a.submask = o.submask;
+    a.ncol = (unsigned long long)ncol; a.ld = (unsigned long long)ld;
+    a.nlay = nlay; a.layer_fastest = f.layer_fastest; a.top_first = f.top_first;
+    a.cloud = cloud ? 1 : 0;
+    const int ns = cloud ? nsamp : 1;                             // (no cloud: every sample is the same zeros)
+    a.denom = (double)(NGPT * ns);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    for (int i = 0; i < ns; i++) {
+        const int seed = (int)((long long)permuteseed + (long long)i * seedstep);
+        if (cloud && irng == 0) { if (int rc = launch_kiss(s, G.W, gw, 0, ncol, nlay, icld, seed, SubcolIn{gp, gc, ga})) return rc; }
+        else if (cloud) { if (int rc = generate_mask(s, ncol, nlay, icld, seed, irng, gp, gc, ga)) return rc; }
+        a.first = i == 0; a.last = i == ns - 1;
+        if (f.real_bytes == 4) LAUNCH("k_cloudcover<f32>", (k_cloudcover<float>), grid, block, s, G.W, a);
+        else LAUNCH("k_cloudcover<f64>", (k_cloudcover<double>), grid, block, s, G.W, a);
+    }
+    if (int rc = launches_ok()) return rc;
+    HIP_TRY(hipEventRecord(G.ev_last.get(), s));
+    G.ev_last_valid = true;
+    return 0;
+}
+
+int cover_device(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, int ld, int icld, int permuteseed, int nsamp, int seedstep, int *irng,
+                 const void *play, const void *cldfr, const void *alpha, const CoverOut &o, void *stream)
+{
+    // (icld = 0 reads no array: the outputs say where the call runs)
+    const void *where = play ? play : o.cldtot ? o.cldtot : o.cldcum ? o.cldcum : o.cldlay ? o.cldlay : (const void *)o.submask;
+    ENTRY_LOCK_FOR(where, irng && *irng != 0);
+    if (int rc = check_cover(ncol, nlay, icld, permuteseed, nsamp, seedstep, irng, play, cldfr, alpha, o)) return rc;
+    return cover_launch(f, ncol, nlay, ld, icld, permuteseed, nsamp, seedstep, *irng, play, cldfr, alpha, o, (hipStream_t)stream);
+}
+
 }   // namespace
 
 extern "C" {
@@ -4620,6 +4702,55 @@ int rrtmg_lw_hip_get_alpha_device_view(const rrtmg_lw_hip_array_view *view, int 
         LAUNCH("k_alpha_view<f64>", (k_alpha_view<double>), grid, block, s, ncol, nlay, (size_t)ld, f.layer_fastest, f.top_first, icld, idcor, decorr_con,
                (const double *)dz, (const double *)lat, juldat, (const double *)cldfrac, (double *)alpha);
     return launches_ok();
+}
+
+// Cloud cover as the McICA sub-columns realise it: DEVICE arrays in the reference form ...
+int rrtmg_lw_hip_mcica_cloud_cover_device(int ncol, int nlay, int icld, int permuteseed, int nsamp, int seedstep, int *irng,
+    const double *play, const double *cldfr, const double *alpha, double *cldtot, double *cldcum, double *cldlay, unsigned *submask, void *stream)
+{
+    return cover_device({8, 0, 0}, ncol, nlay, ncol, icld, permuteseed, nsamp, seedstep, irng, play, cldfr, alpha, {cldtot, cldcum, cldlay, submask}, stream);
+}
+// ... in the caller's form and width ({8, 0, 0, ld}: in place) ...
+int rrtmg_lw_hip_mcica_cloud_cover_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, int icld, int permuteseed, int nsamp,
+    int seedstep, int *irng, const void *play, const void *cldfr, const void *alpha, void *cldtot, void *cldcum, void *cldlay, unsigned *submask,
+    void *stream)
+{
+    rrtmg_lw_hip_array_form f;
+    int ld = 0;
+    bool plain = false;
+    if (int rc = view_check(view, ncol, &f, &ld, &plain)) return rc;
+    return cover_device(f, ncol, nlay, ld, icld, permuteseed, nsamp, seedstep, irng, play, cldfr, alpha, {cldtot, cldcum, cldlay, submask}, stream);
+}
+// ... and HOST arrays: the first device, the call's arrays in one per-call device allocation, the outputs copied back
+int rrtmg_lw_hip_mcica_cloud_cover(int ncol, int nlay, int icld, int permuteseed, int nsamp, int seedstep, int *irng,
+    const double *play, const double *cldfr, const double *alpha, double *cldtot, double *cldcum, double *cldlay, unsigned *submask)
+{
+    ENTRY_LOCK;
+    const CoverOut ho{cldtot, cldcum, cldlay, submask};
+    if (int rc = check_cover(ncol, nlay, icld, permuteseed, nsamp, seedstep, irng, play, cldfr, alpha, ho)) return rc;
+    HIP_TRY(hipDeviceSynchronize());      // asynchronous device-entry work of earlier calls shares the workspace
+    const size_t n = (size_t)ncol, cells = n * (size_t)nlay;
+    const bool cloud = icld != 0, two = icld == 4 || icld == 5;
+    const double *hin[3] = {cloud ? play : nullptr, cloud ? cldfr : nullptr, two ? alpha : nullptr};
+    double *hout[3] = {cldtot, cldcum, cldlay};
+    const size_t nout[3] = {n, cells, cells};
+    size_t bytes = 0;
+    for (int k = 0; k < 3; k++) bytes += (hin[k] ? cells : 0) * 8 + (hout[k] ? nout[k] : 0) * 8;
+    if (submask) bytes += cells * MASK_WORDS * sizeof(unsigned);
+    DevBuf buf;                             // (released when the call is left, on every path)
+    if (int rc = grow(buf, bytes, bytes, "arrays of a cloud-cover call")) return rc;
+    const double *din[3] = {};
+    double *dout[3] = {};
+    double *p = buf.as<double>();
+    for (int k = 0; k < 3; k++) if (hin[k]) { if (int rc = bounce_h2d(p, hin[k], cells * 8)) return rc; din[k] = p; p += cells; }
+    for (int k = 0; k < 3; k++) if (hout[k]) { dout[k] = p; p += nout[k]; }
+    unsigned *const dmask = submask ? reinterpret_cast<unsigned *>(p) : nullptr;
+    hipStream_t s = G.stream.get();
+    if (int rc = cover_launch({8, 0, 0}, ncol, nlay, ncol, icld, permuteseed, nsamp, seedstep, *irng, din[0], din[1], din[2], {dout[0], dout[1], dout[2], dmask}, s)) return rc;
+    if (int rc = read_physics_error(s)) return rc;
+    for (int k = 0; k < 3; k++) if (hout[k]) { if (int rc = bounce_d2h(hout[k], dout[k], nout[k] * 8)) return rc; }
+    if (submask) { if (int rc = bounce_d2h(submask, dmask, cells * MASK_WORDS * sizeof(unsigned))) return rc; }
+    return 0;
 }
 
 int rrtmg_lw_hip_gas_optics_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, int idrv, GCM_PARAMS_AS,

@@ -24,6 +24,7 @@
 //              (column, quad)); a workgroup = the bands of one group, flux partials added over the group in LDS
 //   k_flux     group partials -> fluxes, net fluxes, heating rates           1 thread / (column, chunk of levels)
 //   k_subcol_* McICA sub-column generator (bit masks), k_alpha           see the section below
+//   k_cloudcover  the generator's masks counted: total, cumulative and per-layer cloud cover, the mask itself    1 thread / column
 //
 // Reference lines are cited per routine.  No CPU fallback exists anywhere in this file.
 #include <hip/hip_runtime.h>
@@ -2931,6 +2932,64 @@ __global__ __launch_bounds__(256) void k_alpha_view(int ncol, int nlay, size_t l
         a = alpha_of(icld, decorr_inv, (double)dz[o], (double)dz[om], (double)cldfrac[o], (double)cldfrac[om]);
     }
     alpha[o] = (R)a;
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_cloudcover : rrtmg_lw_hip_mcica_cloud_cover* - what the sub-columns of W.mask (one sample) realise of the cloud field, counted, not
+//               estimated: per (column, layer) the sub-columns that are cloudy in the layer (cldlay) and in the layer or any above it
+//               (cldcum; its value at the surface layer is the total cover, cldtot), and the mask itself with the bits past NGPT cleared
+//               (submask).  Lanes are consecutive columns - for a fixed (word, layer) their mask words are consecutive, and so are the
+//               values of a row of a column-fastest output -; a thread walks its column from the top layer down with the MASK_WORDS
+//               running OR words in registers.  Outputs in the caller's form (R: element type; ld, layer_fastest, top_first as
+//               rrtmg_lw_hip_array_view states them: the count of reference layer k goes where the form keeps layer k), each optional.
+//               Several samples: sample 0 stores its counts (first), the others add theirs to what the arrays hold, the last one also
+//               divides (last) - counts are at most 256 x 64 and exact in float32 too; every value leaves as ONE float64 division
+//               count / denom, rounded to R.  cloud = 0 (icld = 0): no mask is read, every count is zero.
+// ------------------------------------------------------------------------------------------------
+struct CoverArgs {
+    void *cldtot, *cldcum, *cldlay;     // (ncol), (ncol,nlay), (ncol,nlay) of R, or null
+    unsigned *submask;                  // (ncol,nlay,MASK_WORDS): column-fastest rows ld apart, or C order with layer_fastest; or null
+    unsigned long long ncol, ld;
+    int nlay, layer_fastest, top_first;
+    int cloud, first, last;
+    double denom;                       // NGPT x samples
+};
+template <class R>
+__device__ __forceinline__ void cover_put(void *p, size_t at, int count, const CoverArgs &a)
+{
+    if (!p) return;
+    R *const q = static_cast<R *>(p) + at;
+    double v = (double)count;
+    if (!a.first) v += (double)*q;
+    if (a.last) v = v / a.denom;
+    *q = (R)v;
+}
+template <class R>
+__global__ __launch_bounds__(256) void k_cloudcover(Workspace W, CoverArgs a)
+{
+    const size_t gc = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gc >= (size_t)a.ncol) return;
+    const int nlay = a.nlay;
+    unsigned seen[MASK_WORDS] = {};
+    int ccum = 0;
+    for (int l = nlay - 1; l >= 0; l--) {
+        const size_t kk = (size_t)(a.top_first ? nlay - 1 - l : l);
+        int clay = 0;
+        ccum = 0;
+#pragma unroll
+        for (int w = 0; w < MASK_WORDS; w++) {
+            unsigned m = a.cloud ? W.mask[((size_t)w * nlay + l) * W.mask_stride + W.mask_col0 + gc] : 0u;
+            if (w == MASK_WORDS - 1 && (NGPT & 31)) m &= (1u << (NGPT & 31)) - 1u;       // (the generator may leave bits past the last sub-column)
+            seen[w] |= m;
+            clay += __popc(m);
+            ccum += __popc(seen[w]);
+            if (a.submask) a.submask[a.layer_fastest ? (gc * (size_t)nlay + kk) * MASK_WORDS + w : ((size_t)w * nlay + kk) * a.ld + gc] = m;
+        }
+        const size_t at = a.layer_fastest ? gc * (size_t)nlay + kk : gc + a.ld * kk;
+        cover_put<R>(a.cldlay, at, clay, a);
+        cover_put<R>(a.cldcum, at, ccum, a);
+    }
+    cover_put<R>(a.cldtot, gc, ccum, a);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 !  Device-pointer entries for a GPU-resident Fortran host (this library's extension; include/rrtmg_lw_hip.h, "Device arrays with a column
 !  stride"; INTEGRATION.md 4g):
 !      use rrtmg_lw_device, only: rrtmg_lw_dev, rrtmg_lw_mcica_dev, rrtmg_lw_dtsfc_dev, rrtmg_lw_dev_check, rrtmg_lw_dev_status, &
-!                                 rrtmg_lw_mcica_samples_dev, rrtmg_lw_alpha_dev
+!                                 rrtmg_lw_mcica_samples_dev, rrtmg_lw_alpha_dev, rrtmg_lw_cloud_cover_dev
 !      call rrtmg_lw_dev(ncol, ld, nlay, icld, idrv, play, plev, ..., uflx, dflx, hr, uflxc, dflxc, hrc &
 !                        [, duflx_dt, duflxc_dt, uflxs, dflxs, uflxcs, dflxcs, stream])
 !      call rrtmg_lw_dev_check([stream])
@@ -39,6 +39,12 @@
 !      rrtmg_lw_alpha_dev(ncol, ld, nlay, icld, idcor, decorr_con, dz, lat, juldat, cldfrac, alpha [, stream])
 !  is get_alpha on device arrays (rrtmg_lw_hip_get_alpha_device_view): dz, cldfrac, alpha (ld,*), lat(*); alpha is what the two McICA
 !  routines above take for icld = 4 and 5.  For any other icld alpha is left alone.
+!      rrtmg_lw_cloud_cover_dev(ncol, ld, nlay, icld, permuteseed, nsamp, seedstep, irng, play, cldfr &
+!                               [, alpha, cldtot, cldcum, cldlay, submask, stream])
+!  is rrtmg_lw_cloud_cover (module rrtmg_lw_cover) on device arrays (rrtmg_lw_hip_mcica_cloud_cover_device_view): the cloud that
+!  rrtmg_lw_mcica_dev / rrtmg_lw_mcica_samples_dev with the same icld, seeds, irng, play, cldfr and alpha see, counted.  play, cldfr,
+!  alpha, cldcum, cldlay (ld,*), cldtot(*), submask(ld,nlay,*) integer(4); the outputs are optional, each on its own (pass them by
+!  keyword), at least one must be present; submask with nsamp = 1 only.
       module rrtmg_lw_device
 
       use iso_c_binding
@@ -49,7 +55,7 @@
 
       private
       public :: rrtmg_lw_dev, rrtmg_lw_mcica_dev, rrtmg_lw_dtsfc_dev, rrtmg_lw_dev_check, rrtmg_lw_dev_status
-      public :: rrtmg_lw_mcica_samples_dev, rrtmg_lw_alpha_dev
+      public :: rrtmg_lw_mcica_samples_dev, rrtmg_lw_alpha_dev, rrtmg_lw_cloud_cover_dev
 
       integer, parameter :: r4 = c_float
 
@@ -68,6 +74,9 @@
       end interface
       interface rrtmg_lw_alpha_dev
          module procedure rrtmg_lw_alpha_dev_r8, rrtmg_lw_alpha_dev_r4, rrtmg_lw_alpha_dev_r8_at, rrtmg_lw_alpha_dev_r4_at
+      end interface
+      interface rrtmg_lw_cloud_cover_dev
+         module procedure rrtmg_lw_cloud_cover_dev_r8, rrtmg_lw_cloud_cover_dev_r4, rrtmg_lw_cloud_cover_dev_r8_at, rrtmg_lw_cloud_cover_dev_r4_at
       end interface
 
       ! rrtmg_lw_hip_array_view
@@ -135,6 +144,15 @@
             type(c_ptr), value :: dz, lat, cldfrac, alpha, stream
             integer(c_int) :: rc
          end function rrtmg_lw_hip_get_alpha_device_view
+         function rrtmg_lw_hip_mcica_cloud_cover_device_view(view, ncol, nlay, icld, permuteseed, nsamp, seedstep, irng, play, cldfr, alpha, &
+               cldtot, cldcum, cldlay, submask, stream) bind(C, name='rrtmg_lw_hip_mcica_cloud_cover_device_view') result(rc)
+            import :: c_int, c_ptr, array_view
+            type(array_view), intent(in) :: view
+            integer(c_int), value :: ncol, nlay, icld, permuteseed, nsamp, seedstep
+            integer(c_int), intent(inout) :: irng
+            type(c_ptr), value :: play, cldfr, alpha, cldtot, cldcum, cldlay, submask, stream
+            integer(c_int) :: rc
+         end function rrtmg_lw_hip_mcica_cloud_cover_device_view
          function rrtmg_lw_hip_check(stream) bind(C, name='rrtmg_lw_hip_check') result(rc)
             import :: c_int, c_ptr
             type(c_ptr), value :: stream
@@ -1116,6 +1134,94 @@
 
       end subroutine rrtmg_lw_alpha_dev_r4_at
 
+      subroutine rrtmg_lw_cloud_cover_dev_r8 &
+            (ncol, ld, nlay, icld, permuteseed, nsamp, seedstep, irng, play, cldfr, alpha, cldtot, cldcum, cldlay, submask, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, icld, permuteseed, nsamp, seedstep
+      integer(kind=im), intent(inout) :: irng
+      real(kind=rb), target :: play(ld,*), cldfr(ld,*)
+      real(kind=rb), target, optional :: alpha(ld,*), cldtot(*), cldcum(ld,*), cldlay(ld,*)
+      integer(c_int32_t), target, optional :: submask(ld,nlay,*)
+      type(c_ptr), intent(in), optional :: stream
+
+      type(c_ptr) :: p(5)
+
+      p = c_null_ptr
+      if (present(alpha)) p(1) = c_loc(alpha)
+      if (present(cldtot)) p(2) = c_loc(cldtot)
+      if (present(cldcum)) p(3) = c_loc(cldcum)
+      if (present(cldlay)) p(4) = c_loc(cldlay)
+      if (present(submask)) p(5) = c_loc(submask)
+      call dev_cover(8, ncol, ld, nlay, icld, permuteseed, nsamp, seedstep, irng, c_loc(play), c_loc(cldfr), p, stream)
+
+      end subroutine rrtmg_lw_cloud_cover_dev_r8
+
+      subroutine rrtmg_lw_cloud_cover_dev_r4 &
+            (ncol, ld, nlay, icld, permuteseed, nsamp, seedstep, irng, play, cldfr, alpha, cldtot, cldcum, cldlay, submask, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, icld, permuteseed, nsamp, seedstep
+      integer(kind=im), intent(inout) :: irng
+      real(kind=r4), target :: play(ld,*), cldfr(ld,*)
+      real(kind=r4), target, optional :: alpha(ld,*), cldtot(*), cldcum(ld,*), cldlay(ld,*)
+      integer(c_int32_t), target, optional :: submask(ld,nlay,*)
+      type(c_ptr), intent(in), optional :: stream
+
+      type(c_ptr) :: p(5)
+
+      p = c_null_ptr
+      if (present(alpha)) p(1) = c_loc(alpha)
+      if (present(cldtot)) p(2) = c_loc(cldtot)
+      if (present(cldcum)) p(3) = c_loc(cldcum)
+      if (present(cldlay)) p(4) = c_loc(cldlay)
+      if (present(submask)) p(5) = c_loc(submask)
+      call dev_cover(4, ncol, ld, nlay, icld, permuteseed, nsamp, seedstep, irng, c_loc(play), c_loc(cldfr), p, stream)
+
+      end subroutine rrtmg_lw_cloud_cover_dev_r4
+
+      subroutine rrtmg_lw_cloud_cover_dev_r8_at &
+            (ncol, ld, nlay, icld, permuteseed, nsamp, seedstep, irng, play, cldfr, alpha, cldtot, cldcum, cldlay, submask, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, icld, permuteseed, nsamp, seedstep
+      integer(kind=im), intent(inout) :: irng
+      real(kind=rb), target :: play, cldfr
+      real(kind=rb), target, optional :: alpha, cldtot, cldcum, cldlay
+      integer(c_int32_t), target, optional :: submask
+      type(c_ptr), intent(in), optional :: stream
+
+      type(c_ptr) :: p(5)
+
+      p = c_null_ptr
+      if (present(alpha)) p(1) = c_loc(alpha)
+      if (present(cldtot)) p(2) = c_loc(cldtot)
+      if (present(cldcum)) p(3) = c_loc(cldcum)
+      if (present(cldlay)) p(4) = c_loc(cldlay)
+      if (present(submask)) p(5) = c_loc(submask)
+      call dev_cover(8, ncol, ld, nlay, icld, permuteseed, nsamp, seedstep, irng, c_loc(play), c_loc(cldfr), p, stream)
+
+      end subroutine rrtmg_lw_cloud_cover_dev_r8_at
+
+      subroutine rrtmg_lw_cloud_cover_dev_r4_at &
+            (ncol, ld, nlay, icld, permuteseed, nsamp, seedstep, irng, play, cldfr, alpha, cldtot, cldcum, cldlay, submask, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, icld, permuteseed, nsamp, seedstep
+      integer(kind=im), intent(inout) :: irng
+      real(kind=r4), target :: play, cldfr
+      real(kind=r4), target, optional :: alpha, cldtot, cldcum, cldlay
+      integer(c_int32_t), target, optional :: submask
+      type(c_ptr), intent(in), optional :: stream
+
+      type(c_ptr) :: p(5)
+
+      p = c_null_ptr
+      if (present(alpha)) p(1) = c_loc(alpha)
+      if (present(cldtot)) p(2) = c_loc(cldtot)
+      if (present(cldcum)) p(3) = c_loc(cldcum)
+      if (present(cldlay)) p(4) = c_loc(cldlay)
+      if (present(submask)) p(5) = c_loc(submask)
+      call dev_cover(4, ncol, ld, nlay, icld, permuteseed, nsamp, seedstep, irng, c_loc(play), c_loc(cldfr), p, stream)
+
+      end subroutine rrtmg_lw_cloud_cover_dev_r4_at
+
       ! what every specific of rrtmg_lw_dev / rrtmg_lw_mcica_dev ends in: the addresses in the C entry's order - pin: the 23 input arrays
       ! of rrtmg_lw, then alpha; pout: the eight broadband outputs, then the spectral four (null where absent)
       subroutine dev_solve(who, real_bytes, mcica, ncol, ld, nlay, icld, idrv, permuteseed, irng, inflglw, iceflglw, liqflglw, pin, pout, stream)
@@ -1198,6 +1304,28 @@
             dz, lat, int(juldat, c_int), cldfrac, alpha, s)
       if (rc /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_alpha_dev')
       end subroutine dev_alpha
+
+      ! ... of rrtmg_lw_cloud_cover_dev: p = alpha, cldtot, cldcum, cldlay, submask (null where absent)
+      subroutine dev_cover(real_bytes, ncol, ld, nlay, icld, permuteseed, nsamp, seedstep, irng, play, cldfr, p, stream)
+      integer, intent(in) :: real_bytes
+      integer(kind=im), intent(in) :: ncol, ld, nlay, icld, permuteseed, nsamp, seedstep
+      integer(kind=im), intent(inout) :: irng
+      type(c_ptr), intent(in) :: play, cldfr, p(5)
+      type(c_ptr), intent(in), optional :: stream
+
+      type(array_view) :: view
+      type(c_ptr) :: s
+      integer(c_int) :: rc, irng_c
+
+      view = array_view(int(real_bytes, c_int), 0_c_int, 0_c_int, int(ld, c_int))
+      s = c_null_ptr
+      if (present(stream)) s = stream
+      irng_c = int(irng, c_int)
+      rc = rrtmg_lw_hip_mcica_cloud_cover_device_view(view, int(ncol, c_int), int(nlay, c_int), int(icld, c_int), int(permuteseed, c_int), &
+            int(nsamp, c_int), int(seedstep, c_int), irng_c, play, cldfr, p(1), p(2), p(3), p(4), p(5), s)
+      if (rc /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_cloud_cover_dev')
+      irng = int(irng_c, im)
+      end subroutine dev_cover
 
       ! ... and of rrtmg_lw_dtsfc_dev: p in the C entry's order (plev, dtsfc, uflx, dflx, duflx_dt, uflxc, dflxc, duflxc_dt, the four outputs)
       subroutine dev_adjust(real_bytes, ncol, ld, nlay, p, stream)

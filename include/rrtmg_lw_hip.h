@@ -822,6 +822,71 @@ int rrtmg_lw_hip_mcica_cloud_cover_device_view(const rrtmg_lw_hip_array_view *vi
     const void *play, const void *cldfr, const void *alpha,
     void *cldtot, void *cldcum, void *cldlay, unsigned *submask, void *stream);
 
+/* ---- Cloud optics: band optical depths, ncbands, secdiff ---------------------------------------------------------------------------------
+ * The gas-optics entries give the gas optical depth per g-point and the cloud-cover entries the McICA sub-columns; these three give the
+ * remaining pieces of the solver's optical depth: the cloud optical depth per spectral band that cldprop (imca = 0) or cldprmc
+ * (imca = 1) forms from water paths and particle sizes, BEFORE the diffusivity secant; cldprop's band count; and the secants.  No solver
+ * kernel runs, and the solver's own cloud kernels are not the ones used here.
+ * Every value is float64 arithmetic in which each operation rounds on its own (no fused multiply-add) and every division is an IEEE
+ * division, so that any implementation of the definitions below agrees to the bit.  Inputs as in rrtmg_lw_hip_run_nomcica: cldfr, cicewp,
+ * cliqwp, reice, reliq, h2ovmr (ncol,nlay), taucld (16,ncol,nlay), plev (ncol,nlay+1), the flags inflglw, iceflglw, liqflglw.
+ *   taucloud (ncol,nlay,16)   laid out like tauaer.
+ *     imca = 0 (src/rrtmg_lw_cldprop.f90:50-295): for spectral band B of layer k the reference's taucloud(k, ib) with ib = ipat(B, .) for
+ *       the column's FINAL ncbands (the map of src/rrtmg_lw_rtrn.f90:343-349): the cloud optical depth the sweeps use for the g-points of
+ *       band B.  Zero except in layers that enter cldprop: cldfr >= 1e-20 and (cicewp + cliqwp >= 1e-20 or the sum of taucld over the
+ *       bands, added in band order, >= 1e-20).  In an entering layer only the cloud bands ib <= the band count cldprop had reached AT THAT
+ *       LAYER (walking up from the surface) are assigned: a layer worked on while ncbands was 1 stays zero in cloud bands 2..16 even if a
+ *       later layer raises the count.  inflglw = 0: taucld(ib); 1: abscld1 * (cicewp + cliqwp); 2: cicewp * abscoice(ib) + cliqwp *
+ *       abscoliq(ib) with cldprop's table positions, iceind / liqind maps and 1 -> 2 promotion, every interpolation
+ *       tb[i-1] + fint * (tb[i] - tb[i-1]).  The library's one stated deviation holds here too: in an ice-only layer with iceflglw = 1 of
+ *       a 16-band column, cloud bands 6-16 use the fifth Ebert-Curry band.  Layers with 1e-20 <= cldfr < 1e-6 get their cldprop value
+ *       although the sweeps treat them as cloud-free and never read it.
+ *     imca = 1 (src/rrtmg_lw_cldprmc.f90:49-279 on the sub-columns the generator expands from grid-mean inputs): what cldprmc leaves in
+ *       taucmc(ig, k) for a CLOUDY sub-column ig of band B; it does not depend on the mask.  Formed in layers with cldfr >= 1e-20 (below
+ *       that the generator draws no cloudy sub-column; the value is zero).  A cell enters when cicewp + cliqwp >= 1e-20 or taucld(B) >=
+ *       1e-20; one that does not keeps taucld(B).  An entering cell: inflglw = 0: taucld(B); 2: cicewp * abscoice(B) + cliqwp *
+ *       abscoliq(B), iceflglw = 1 through the five-band map per band; 1: the reference's stop (below).
+ *   ncbands (ncol)            int32 whatever the form: imca = 0: cldprop's band count at the end of the column, 1, 5 or 16; imca = 1: 16.
+ *   secdiff (ncol,16)         laid out like emis: the diffusivity secant of each band (rtrn :280-288): 1.66 in bands 1, 4 and 10-16,
+ *                             a0 + a1 * exp(a2 * pwvcm) clamped to [1.5, 1.8] elsewhere, pwvcm the precipitable water of inatm
+ *                             (src/rrtmg_lw_rad.nomcica.f90:795-863) from plev and h2ovmr.  The same for both imca values.
+ * The solver's cloud term of band B is secdiff(icb) * taucloud(B) with icb = ipat(B, .) of the column's ncbands in the deterministic
+ * solver - the reference indexes secdiff by the CLOUD band there (rtrn :323): band 1 for ncbands = 1, bands 1, 2, 3, 3, 3, 4, 4, 4, 5 ...
+ * for 5, B for 16 - and secdiff(B) * taucloud(B) for McICA, in the cells the mask marks.
+ * Each output may be NULL - it is then neither formed nor touched -, at least one must be given.  The six cloud arrays are required
+ * when taucloud or ncbands is given, plev and h2ovmr when secdiff is; arrays a call does not need may be NULL and are not read.
+ * Particle sizes: where a size is read - inflglw = 2, the phase's water path non-zero, liquid with liqflglw = 1 - the bounds and texts
+ * are the solver's ("Cloud particle sizes"): RRTMG_LW_HIP_EPHYSICS from the host entry's return value, from
+ * rrtmg_lw_hip_check(stream) for the device entries.  With imca = 1 a size is checked in EVERY layer with cldfr >= 1e-20 that enters,
+ * whether or not a particular seed would draw a cloudy sub-column there (the fused solver entries check only where one is drawn);
+ * inflglw = 1 with imca = 1 is the reference's stop "INFLAG = 1 OPTION NOT AVAILABLE WITH MCICA" wherever a cell enters.  The outputs
+ * of a failed call are not valid; the next call starts clean.
+ * RRTMG_LW_HIP_EARG, with a text that names the argument and before anything is written: imca other than 0 or 1, the dimension limits
+ * of the other entries, the view rules, a missing required array, all outputs NULL, an output that shares a byte with a needed input
+ * or with another output.
+ * Device entries: DEVICE pointers; the device is that of cldfr (of plev when only secdiff is asked for); they enqueue on `stream` and do
+ * not synchronise.  The entry lock, no graph replay, no combining.  Two kernels: one thread per column (the band-count walk, pwvcm and
+ * secdiff), one thread per (column, layer) (the sixteen band values); (nlay + 1) bytes per column of workspace in the *_as staging buffer.
+ * rrtmg_lw_hip_cloud_optics_device_view: the arrays in the view's form ("Device arrays with a column stride", above), all four fields
+ * with their meaning there: taucld as in the solver entries, taucloud like tauaer, secdiff like emis, ncbands indexed per column.  Every
+ * form is read and written IN PLACE - {8, 0, 0, ld} and the converting ones alike, nothing is staged; a float32 input is widened
+ * exactly, a float32 output is the float64 value rounded once.  Nothing outside the call's ncol columns is read into a result or written.
+ * rrtmg_lw_hip_cloud_optics: HOST pointers, reference layout, the first device; staged in column batches (rrtmg_lw_hip_set_batch, at
+ * most 16 384) through the host-entry staging buffer; the results do not depend on the batch size.  Synchronises. */
+int rrtmg_lw_hip_cloud_optics(int ncol, int nlay, int imca, int inflglw, int iceflglw, int liqflglw,
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
+    const double *reice, const double *reliq, const double *plev, const double *h2ovmr,
+    double *taucloud, int *ncbands, double *secdiff);
+int rrtmg_lw_hip_cloud_optics_device(int ncol, int nlay, int imca, int inflglw, int iceflglw, int liqflglw,
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp,
+    const double *reice, const double *reliq, const double *plev, const double *h2ovmr,
+    double *taucloud, int *ncbands, double *secdiff, void *stream);
+int rrtmg_lw_hip_cloud_optics_device_view(const rrtmg_lw_hip_array_view *view,
+    int ncol, int nlay, int imca, int inflglw, int iceflglw, int liqflglw,
+    const void *cldfr, const void *taucld, const void *cicewp, const void *cliqwp,
+    const void *reice, const void *reliq, const void *plev, const void *h2ovmr,
+    void *taucloud, int *ncbands, void *secdiff, void *stream);
+
 /* ---- Host arrays of a host built with 4-byte reals ("_r4") ----------------------------------------------------------------------------
  * A host model that carries RRTMG_LW at the default real kind (no -r8) owns float arrays.  These four entries take them as they are:
  * HOST pointers, every floating-point array of the call - inputs and outputs, alpha too - `float`.  Layout, argument order, the in/out

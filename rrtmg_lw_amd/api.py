@@ -1011,6 +1011,91 @@ def mcica_cloud_cover_device(d, out, icld, permuteseed, irng=0, alpha=None, nsam
     return irng_c.value
 
 
+_CLOUD_OPTICS_IN = ("cldfr", "taucld", "cicewp", "cliqwp", "reice", "reliq", "plev", "h2ovmr")
+_CLOUD_OPTICS_OUT = ("taucloud", "ncbands", "secdiff")
+
+
+def _cloud_optics_needed(given):
+    """the inputs a cloud-optics call reads: the six cloud arrays for taucloud or ncbands, plev and h2ovmr for secdiff"""
+    if not given:
+        raise ValueError(f"cloud optics: no output given - at least one of {_CLOUD_OPTICS_OUT}")
+    return (_CLOUD_OPTICS_IN[:6] if ("taucloud" in given or "ncbands" in given) else ()) + (_CLOUD_OPTICS_IN[6:] if "secdiff" in given else ())
+
+
+def cloud_optics(d, imca=0, out=None):
+    """Cloud optical depth per spectral band before the diffusivity secant, cldprop's band count and the secants
+    (rrtmg_lw_hip_cloud_optics; include/rrtmg_lw_hip.h states the definitions): imca = 0 cldprop, 1 cldprmc on a cloudy sub-column.
+    `d` as for rrtmg_lw_from_dict: ncol, nlay, the three cloud flags, numpy float64 arrays cldfr, cicewp, cliqwp, reice, reliq
+    (ncol, nlay), taucld (16, ncol, nlay) - for taucloud or ncbands - and plev (ncol, nlay+1), h2ovmr (ncol, nlay) - for secdiff.
+    Returns a dict of Fortran-ordered arrays taucloud (ncol, nlay, 16), ncbands (ncol,) int32, secdiff (ncol, 16).  `out` may hold
+    preallocated arrays; an output set to None there is not formed (and its inputs are not needed).  An array of another dtype or
+    shape is refused (TypeError / ValueError), not converted."""
+    ncol, nlay = int(d["ncol"]), int(d["nlay"])
+    shapes = {"taucloud": (ncol, nlay, NBND), "ncbands": (ncol,), "secdiff": (ncol, NBND)}
+    out = {} if out is None else out
+    for k in out:
+        if k not in _CLOUD_OPTICS_OUT:
+            raise ValueError(f"unknown output {k!r}: one of {_CLOUD_OPTICS_OUT}")
+    for k in _CLOUD_OPTICS_OUT:
+        if k not in out:
+            out[k] = np.zeros(shapes[k], dtype=np.int32 if k == "ncbands" else np.float64, order="F")
+    given = [k for k in _CLOUD_OPTICS_OUT if out[k] is not None]
+    needed = _cloud_optics_needed(given)
+    in_shapes = {k: (ncol, nlay) for k in _CLOUD_OPTICS_IN}
+    in_shapes.update(taucld=(NBND, ncol, nlay), plev=(ncol, nlay + 1))
+    null = C.cast(None, _dp)
+    ins = []
+    for k in _CLOUD_OPTICS_IN:
+        if k not in needed:
+            ins.append(null)
+            continue
+        a = d.get(k)
+        if not isinstance(a, np.ndarray) or a.dtype != np.float64:
+            raise TypeError(f"cloud optics: {k!r} must be a numpy float64 array, not {getattr(a, 'dtype', type(a).__name__)}")
+        a = _f(a, in_shapes[k])
+        ins.append(a)
+    outs = [_p(_out_ok(out[k], shapes[k], k, np.int32 if k == "ncbands" else np.float64)) if out[k] is not None else null for k in _CLOUD_OPTICS_OUT]
+    _check(lib().rrtmg_lw_hip_cloud_optics(C.c_int(ncol), C.c_int(nlay), C.c_int(int(imca)), C.c_int(int(d["inflglw"])),
+                                           C.c_int(int(d["iceflglw"])), C.c_int(int(d["liqflglw"])),
+                                           *[a if a is null else _p(a) for a in ins], *outs))
+    return out
+
+
+def cloud_optics_device(d, out, imca=0, stream=None, form=None, ld=None):
+    """Device-resident cloud_optics: `d` holds torch CUDA tensors as for rrtmg_lw_device - of them cldfr, taucld, cicewp, cliqwp, reice,
+    reliq are read for taucloud or ncbands, plev and h2ovmr for secdiff -, ncol, nlay and the three cloud flags; `out` the preallocated
+    output tensors: those of taucloud (like tauaer), ncbands ((ncol,) torch.int32, whatever the form) and secdiff (like emis) that it
+    holds are formed, the others are not.  form / ld as in get_alpha_device (rrtmg_lw_hip_cloud_optics_device_view; every form runs on
+    the tensors in place); with neither the plain rrtmg_lw_hip_cloud_optics_device.  A tensor that is not exactly the form's - dtype,
+    shape, strides - is refused.  Enqueues on `stream`, does not synchronise (check(stream) collects a particle-size stop)."""
+    import torch
+    ncol, nlay = int(d["ncol"]), int(d["nlay"])
+    for k in out:
+        if k not in _CLOUD_OPTICS_OUT:
+            raise ValueError(f"unknown output {k!r}: one of {_CLOUD_OPTICS_OUT}")
+    given = [k for k in _CLOUD_OPTICS_OUT if out.get(k) is not None]
+    needed = _cloud_optics_needed(given)
+    tensors = {k: d.get(k) for k in needed}
+    for k in needed:
+        if tensors[k] is None:
+            raise ValueError(f"cloud optics: input {k!r} is missing")
+    tensors.update({k: out.get(k) for k in ("taucloud", "secdiff")})
+    view = _checked_view(form, ld or 0, ncol, nlay, tensors)
+    nb = out.get("ncbands")
+    if nb is not None:
+        if nb.dtype != torch.int32:
+            raise TypeError(f"'ncbands' is {nb.dtype}: it is torch.int32 whatever the array form")
+        if tuple(nb.shape) != (ncol,) or (ncol > 1 and nb.stride(0) != 1):
+            raise ValueError(f"'ncbands' has shape {tuple(nb.shape)} and strides {tuple(nb.stride())}: needs {(ncol,)}, contiguous")
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    args = [C.c_int(ncol), C.c_int(nlay), C.c_int(int(imca)), C.c_int(int(d["inflglw"])), C.c_int(int(d["iceflglw"])), C.c_int(int(d["liqflglw"]))]
+    args += [ptr(tensors.get(k)) for k in _CLOUD_OPTICS_IN] + [ptr(out.get(k)) for k in _CLOUD_OPTICS_OUT] + [C.c_void_p(stream or 0)]
+    if form is None and ld is None:
+        _check(lib().rrtmg_lw_hip_cloud_optics_device(*args))
+    else:
+        _check(lib().rrtmg_lw_hip_cloud_optics_device_view(view, *args))
+
+
 def run_columns_mcica(cols, subs, istart=1, iend=16, icld=None, idrv=None):
     """Prepared-column McICA entry: cols[k] (rrtmg_lw_amd.io_rrtm.read_input_rrtm dicts) with sub-columns subs[k] =
     dict(cldfmc, taucmc, ciwpmc, clwpmc (140, nlayers), reicmc, relqmc (nlayers)); one (column, sample) pair per entry.

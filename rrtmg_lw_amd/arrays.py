@@ -16,6 +16,8 @@ column index fastest, vertical index 0 at the surface, logical shapes as the For
     uflx_var, dflx_var (ncol, nlay+1), hr_var (ncol, nlay)                          sample variances (api.rrtmg_lw_mcica_samples_device)
     cldtot (ncol,), cldcum, cldlay (ncol, nlay)                                     realised cloud cover (api.mcica_cloud_cover_device;
                                                                                     its submask is uint32 and has a layout of its own)
+    taucloud (ncol, nlay, 16), secdiff (ncol, 16)                                   cloud optics (api.cloud_optics_device; its ncbands is
+                                                                                    int32, (ncol,), in every form)
 
 An ArrayForm(real_bytes, layer_fastest, top_first) describes what a device-resident caller holds instead:
 
@@ -52,8 +54,8 @@ NBND = 16
 LAYER_ARRAYS = ("play", "tlay", "h2ovmr", "o3vmr", "co2vmr", "ch4vmr", "n2ovmr", "o2vmr", "cfc11vmr", "cfc12vmr", "cfc22vmr",
                 "ccl4vmr", "cldfr", "cicewp", "cliqwp", "reice", "reliq", "alpha", "hr", "hrc", "hr_adj", "hrc_adj", "dz", "hr_var", "cldcum", "cldlay")
 LEVEL_ARRAYS = ("plev", "tlev", "uflx", "dflx", "uflxc", "dflxc", "duflx_dt", "duflxc_dt", "uflx_adj", "uflxc_adj", "uflx_var", "dflx_var")
-BAND_ARRAYS = ("emis", "plankbnd", "dplankbnd_dt")                      # (ncol, 16): no vertical axis
-LAYER_X_ARRAYS = ("tauaer", "planklay", "taug", "fracs")                # (ncol, nlay, 16 | NG)
+BAND_ARRAYS = ("emis", "plankbnd", "dplankbnd_dt", "secdiff")           # (ncol, 16): no vertical axis
+LAYER_X_ARRAYS = ("tauaer", "planklay", "taug", "fracs", "taucloud")    # (ncol, nlay, 16 | NG)
 LEVEL_X_ARRAYS = ("planklev", "uflxs", "dflxs", "uflxcs", "dflxcs")      # (ncol, nlay+1, 16)
 COLUMN_ARRAYS = ("tsfc", "dtsfc", "lat", "cldtot")
 ALL_ARRAYS = LAYER_ARRAYS + LEVEL_ARRAYS + BAND_ARRAYS + LAYER_X_ARRAYS + LEVEL_X_ARRAYS + COLUMN_ARRAYS + ("taucld",)
@@ -84,7 +86,7 @@ def reference_shape(name, ncol, nlay, ng=140):
         return (ncol, NBND)
     if name == "taucld":
         return (NBND, ncol, nlay)
-    if name in ("tauaer", "planklay"):
+    if name in ("tauaer", "planklay", "taucloud"):
         return (ncol, nlay, NBND)
     if name in ("taug", "fracs"):
         return (ncol, nlay, ng)

@@ -4613,6 +4613,87 @@ int cover_device(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, int ld, i
     return cover_launch(f, ncol, nlay, ld, icld, permuteseed, nsamp, seedstep, *irng, play, cldfr, alpha, o, (hipStream_t)stream);
 }
 
+// ---- cloud optics (rrtmg_lw_hip_cloud_optics*, k_cloudoptics_col / k_cloudoptics) ---------------------------------------------------------
+// cldprop's / cldprmc's optical depth per spectral band before the diffusivity secant, cldprop's band count and the secants, formed by two
+// kernels of their own straight from and into the caller's arrays in the caller's form; no solver kernel runs and none is shared.  The
+// one piece of workspace is the band-count walk's (nlay + 1) bytes per column, at the head of the *_as staging buffer (G.form_buf).
+struct CloudOpticsIn { const void *cldfr, *taucld, *cicewp, *cliqwp, *reice, *reliq, *plev, *h2ovmr; };
+struct CloudOpticsOut { void *taucloud; int *ncbands; void *secdiff; };
+
+// what the three entries check, in this order, before anything is allocated or enqueued (the pointers: the caller's, host or device);
+// ld: the column extent of the arrays, real_bytes: their element size
+int check_cloud_optics(int ncol, int nlay, int ld, int real_bytes, int imca, const CloudOpticsIn &in, const CloudOpticsOut &o)
+{
+    if (int rc = check_common(ncol, nlay)) return rc;
+    if (imca != 0 && imca != 1) return fail(RRTMG_LW_HIP_EARG, "cloud optics: imca = %d - 0 (cldprop) or 1 (cldprmc)", imca);
+    if (!o.taucloud && !o.ncbands && !o.secdiff)
+        return fail(RRTMG_LW_HIP_EARG, "cloud optics: taucloud, ncbands and secdiff are all null - at least one output");
+    struct Range { const char *name; const void *p; size_t bytes; bool need; };
+    const size_t n = (size_t)ncol, w = (size_t)ld, L = (size_t)nlay, rb = (size_t)real_bytes;
+    const bool cloud = o.taucloud || o.ncbands, sec = o.secdiff != nullptr;
+    // (an array of R rows ld columns apart reaches from the call's first column to its last one in row R - 1)
+    const size_t lay = (w * (L - 1) + n) * rb, lev = (w * L + n) * rb;
+    const Range ins[] = {{"cldfr", in.cldfr, lay, cloud}, {"taucld", in.taucld, NBND * lay, cloud}, {"cicewp", in.cicewp, lay, cloud},
+                         {"cliqwp", in.cliqwp, lay, cloud}, {"reice", in.reice, lay, cloud}, {"reliq", in.reliq, lay, cloud},
+                         {"plev", in.plev, lev, sec}, {"h2ovmr", in.h2ovmr, lay, sec}};
+    const Range outs[] = {{"taucloud", o.taucloud, (w * (L * NBND - 1) + n) * rb, false}, {"ncbands", o.ncbands, n * sizeof(int), false},
+                          {"secdiff", o.secdiff, (w * (NBND - 1) + n) * rb, false}};
+    for (const Range &i : ins)
+        if (i.need && !i.p) return fail(RRTMG_LW_HIP_EARG, "cloud optics: null input array (%s)", i.name);
+    const auto meet = [](const Range &x, const Range &y) {
+        const uintptr_t a = (uintptr_t)x.p, b = (uintptr_t)y.p;
+        return x.p && y.p && a < b + y.bytes && b < a + x.bytes;
+    };
+    for (size_t k = 0; k < 3; k++) {
+        for (const Range &i : ins)
+            if (i.need && meet(outs[k], i)) return fail(RRTMG_LW_HIP_EARG, "cloud optics: output %s overlaps input %s", outs[k].name, i.name);
+        for (size_t j = 0; j < k; j++)
+            if (meet(outs[k], outs[j])) return fail(RRTMG_LW_HIP_EARG, "cloud optics: output %s overlaps output %s", outs[k].name, outs[j].name);
+    }
+    return 0;
+}
+
+// the call on stream s from DEVICE arrays in the form f, ld columns wide; checked (check_cloud_optics), the caller holds the entry lock
+int cloud_optics_launch(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, int ld, int imca, int inflag, int iceflag, int liqflag,
+                        const CloudOpticsIn &in, const CloudOpticsOut &o, hipStream_t s)
+{
+    const bool cloud = o.taucloud || o.ncbands;
+    if (int rc = ensure_pipeline()) return rc;
+    if (cloud) if (int rc = ensure_form(G.form_buf, ((size_t)nlay + 1) * (size_t)ncol)) return rc;
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));      // an earlier call, possibly on another stream, still owns the staging buffer
+    CloudOpticsArgs a{};
+    if (cloud) { a.cldfr = in.cldfr; a.taucld = in.taucld; a.cicewp = in.cicewp; a.cliqwp = in.cliqwp; a.reice = in.reice; a.reliq = in.reliq; }
+    if (o.secdiff) { a.plev = in.plev; a.h2ovmr = in.h2ovmr; }
+    a.taucloud = o.taucloud; a.secdiff = o.secdiff; a.ncbands = o.ncbands;
+    a.nbat = cloud ? G.form_buf.as<unsigned char>() : nullptr;
+    a.ncol = (unsigned long long)ncol; a.ld = (unsigned long long)ld;
+    a.nlay = nlay; a.layer_fastest = f.layer_fastest; a.top_first = f.top_first;
+    a.imca = imca; a.inflag = inflag; a.iceflag = iceflag; a.liqflag = liqflag;
+    a.err = G.d_err.as<int>();
+    // (thread-per-column: one wave per workgroup, so that a call of one wave per 64 columns spreads over the CUs - run_prep)
+    const dim3 cgrid((unsigned)(((size_t)ncol + 63) / 64)), cblock(64);
+    const dim3 lgrid((unsigned)(((size_t)ncol + BLOCK - 1) / BLOCK), (unsigned)nlay), lblock(BLOCK);
+    if (f.real_bytes == 4) {
+        LAUNCH("k_cloudoptics_col<f32>", (k_cloudoptics_col<float>), cgrid, cblock, s, a);
+        if (cloud) LAUNCH("k_cloudoptics<f32>", (k_cloudoptics<float>), lgrid, lblock, s, G.D, a);
+    } else {
+        LAUNCH("k_cloudoptics_col<f64>", (k_cloudoptics_col<double>), cgrid, cblock, s, a);
+        if (cloud) LAUNCH("k_cloudoptics<f64>", (k_cloudoptics<double>), lgrid, lblock, s, G.D, a);
+    }
+    if (int rc = launches_ok()) return rc;
+    HIP_TRY(hipEventRecord(G.ev_last.get(), s));
+    G.ev_last_valid = true;
+    return 0;
+}
+
+int cloud_optics_device(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, int ld, int imca, int inflag, int iceflag, int liqflag,
+                        const CloudOpticsIn &in, const CloudOpticsOut &o, void *stream)
+{
+    ENTRY_LOCK_FOR(in.cldfr ? in.cldfr : in.plev);
+    if (int rc = check_cloud_optics(ncol, nlay, ld, f.real_bytes, imca, in, o)) return rc;
+    return cloud_optics_launch(f, ncol, nlay, ld, imca, inflag, iceflag, liqflag, in, o, (hipStream_t)stream);
+}
+
 }   // namespace
 
 extern "C" {
@@ -4750,6 +4831,61 @@ int rrtmg_lw_hip_mcica_cloud_cover(int ncol, int nlay, int icld, int permuteseed
     if (int rc = read_physics_error(s)) return rc;
     for (int k = 0; k < 3; k++) if (hout[k]) { if (int rc = bounce_d2h(hout[k], dout[k], nout[k] * 8)) return rc; }
     if (submask) { if (int rc = bounce_d2h(submask, dmask, cells * MASK_WORDS * sizeof(unsigned))) return rc; }
+    return 0;
+}
+
+// Cloud optics - cldprop's / cldprmc's optical depths per spectral band, the band count, the diffusivity secants: DEVICE arrays in the
+// reference form ...
+int rrtmg_lw_hip_cloud_optics_device(int ncol, int nlay, int imca, int inflglw, int iceflglw, int liqflglw,
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp, const double *reice, const double *reliq,
+    const double *plev, const double *h2ovmr, double *taucloud, int *ncbands, double *secdiff, void *stream)
+{
+    return cloud_optics_device({8, 0, 0}, ncol, nlay, ncol, imca, inflglw, iceflglw, liqflglw,
+                               {cldfr, taucld, cicewp, cliqwp, reice, reliq, plev, h2ovmr}, {taucloud, ncbands, secdiff}, stream);
+}
+// ... in the caller's form and width (every form runs on the caller's arrays: nothing is staged) ...
+int rrtmg_lw_hip_cloud_optics_device_view(const rrtmg_lw_hip_array_view *view, int ncol, int nlay, int imca, int inflglw, int iceflglw, int liqflglw,
+    const void *cldfr, const void *taucld, const void *cicewp, const void *cliqwp, const void *reice, const void *reliq,
+    const void *plev, const void *h2ovmr, void *taucloud, int *ncbands, void *secdiff, void *stream)
+{
+    rrtmg_lw_hip_array_form f;
+    int ld = 0;
+    bool plain = false;
+    if (int rc = view_check(view, ncol, &f, &ld, &plain)) return rc;
+    return cloud_optics_device(f, ncol, nlay, ld, imca, inflglw, iceflglw, liqflglw,
+                               {cldfr, taucld, cicewp, cliqwp, reice, reliq, plev, h2ovmr}, {taucloud, ncbands, secdiff}, stream);
+}
+// ... and HOST arrays: the first device, column batches through the host-entry staging buffer (a column's values do not depend on its
+// neighbours, so the results do not depend on the batch size)
+int rrtmg_lw_hip_cloud_optics(int ncol, int nlay, int imca, int inflglw, int iceflglw, int liqflglw,
+    const double *cldfr, const double *taucld, const double *cicewp, const double *cliqwp, const double *reice, const double *reliq,
+    const double *plev, const double *h2ovmr, double *taucloud, int *ncbands, double *secdiff)
+{
+    ENTRY_LOCK;
+    if (int rc = check_cloud_optics(ncol, nlay, ncol, 8, imca, {cldfr, taucld, cicewp, cliqwp, reice, reliq, plev, h2ovmr}, {taucloud, ncbands, secdiff})) return rc;
+    HIP_TRY(hipDeviceSynchronize());      // asynchronous device-entry work of earlier calls shares the staging
+    const size_t n = (size_t)ncol, L = (size_t)nlay;
+    const bool cloud = taucloud || ncbands, sec = secdiff != nullptr;
+    const auto in = [](const double *p, bool on, size_t inner, size_t rows) { return HostIn{on ? p : nullptr, inner, rows, nullptr}; };
+    std::vector<HostIn> ins = {in(cldfr, cloud, 1, L), in(taucld, cloud, NBND, L), in(cicewp, cloud, 1, L), in(cliqwp, cloud, 1, L),
+                               in(reice, cloud, 1, L), in(reliq, cloud, 1, L), in(plev, sec, 1, L + 1), in(h2ovmr, sec, 1, L)};
+    // (ncbands: int32, one 8-byte slot per column in the staging; copied back by hand below - h stays null for stage_out)
+    std::vector<HostOut> outs = {HostOut{taucloud, taucloud ? NBND * L : 0, nullptr, taucloud != nullptr}, HostOut{nullptr, ncbands ? (size_t)1 : 0, nullptr, false},
+                                 HostOut{secdiff, sec ? (size_t)NBND : 0, nullptr, sec}};
+    const int nbmax = balanced_batch(ncol, std::min(eff_batch(nlay), HOST_BATCH));
+    if (int rc = stage_alloc(ins, outs, (size_t)nbmax)) return rc;
+    hipStream_t s = G.stream.get();
+    for (size_t col0 = 0; col0 < n; col0 += (size_t)nbmax) {
+        const size_t nb = std::min((size_t)nbmax, n - col0);
+        if (int rc = stage_in(ins, n, col0, nb, s)) return rc;
+        int *const dnb = ncbands ? reinterpret_cast<int *>(outs[1].d) : nullptr;
+        if (int rc = cloud_optics_launch({8, 0, 0}, (int)nb, nlay, (int)nb, imca, inflglw, iceflglw, liqflglw,
+                                         {ins[0].d, ins[1].d, ins[2].d, ins[3].d, ins[4].d, ins[5].d, ins[6].d, ins[7].d},
+                                         {taucloud ? outs[0].d : nullptr, dnb, sec ? outs[2].d : nullptr}, s)) return rc;
+        if (int rc = read_physics_error(s)) return rc;
+        if (int rc = stage_out(outs, n, col0, nb, s)) return rc;
+        if (ncbands) { if (int rc = bounce_d2h(ncbands + col0, dnb, nb * sizeof(int))) return rc; }
+    }
     return 0;
 }
 

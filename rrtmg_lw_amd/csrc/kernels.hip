@@ -25,6 +25,7 @@
 //   k_flux     group partials -> fluxes, net fluxes, heating rates           1 thread / (column, chunk of levels)
 //   k_subcol_* McICA sub-column generator (bit masks), k_alpha           see the section below
 //   k_cloudcover  the generator's masks counted: total, cumulative and per-layer cloud cover, the mask itself    1 thread / column
+//   k_cloudoptics_col / k_cloudoptics   cldprop / cldprmc as OUTPUTS: band optical depths before the secant, ncbands, secdiff    1 thread / column, / (column, layer)
 //
 // Reference lines are cited per routine.  No CPU fallback exists anywhere in this file.
 #include <hip/hip_runtime.h>
@@ -2990,6 +2991,271 @@ __global__ __launch_bounds__(256) void k_cloudcover(Workspace W, CoverArgs a)
         cover_put<R>(a.cldcum, at, ccum, a);
     }
     cover_put<R>(a.cldtot, gc, ccum, a);
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_cloudoptics_col / k_cloudoptics : rrtmg_lw_hip_cloud_optics* - the cloud optical depth per spectral band as cldprop (imca = 0,
+//               src/rrtmg_lw_cldprop.f90:173-293, with rtrn's band -> cloud-band map, src/rrtmg_lw_rtrn.f90:343-349) or cldprmc (imca = 1,
+//               src/rrtmg_lw_cldprmc.f90:173-273, on the cloudy cells the generator expands from the grid-mean inputs) forms it, BEFORE the
+//               diffusivity secant, and the secants themselves (rtrn :280-288 from inatm's pwvcm).  The table logic is k_cloudlay's and
+//               k_cloudmc's, restated here under contract(off): every product, sum and quotient rounds on its own, so that the values
+//               are defined operation by operation (include/rrtmg_lw_hip.h); the solver's kernels are not touched.
+//               Inputs are read and outputs stored in the caller's form (R: element type; ld, layer_fastest, top_first as
+//               rrtmg_lw_hip_array_view states them), lanes = consecutive columns.
+//   k_cloudoptics_col  one thread per column: the walk that carries cldprop's band count from layer to layer (k_cloudscan's) - the count
+//               in effect at every layer and the final one go to `nbat` ([nlay + 1][ncol] bytes), the final one to ncbands -, and the
+//               column sums of inatm -> pwvcm -> secdiff (k_colprep's).
+//   k_cloudoptics      one thread per (column, layer): the sixteen band values of the cell.
+// ------------------------------------------------------------------------------------------------
+struct CloudOpticsArgs {
+    const void *cldfr, *taucld, *cicewp, *cliqwp, *reice, *reliq, *plev, *h2ovmr;      // of R; the cloud six null when neither taucloud nor ncbands is asked for
+    void *taucloud, *secdiff;           // (ncol,nlay,16) like tauaer, (ncol,16) like emis, of R, or null
+    int *ncbands;                       // (ncol) or null
+    unsigned char *nbat;                // [nlay + 1][ncol]: the band count cldprop had reached at each layer; row nlay: at the end of the column
+    unsigned long long ncol, ld;
+    int nlay, layer_fastest, top_first;
+    int imca, inflag, iceflag, liqflag;
+    int *err;
+};
+template <class R> __device__ __forceinline__ double co_get(const void *p, size_t at) { return (double)static_cast<const R *>(p)[at]; }
+// where the form keeps element (column i, reference layer k) of a (ncol,nlay) array ...
+__device__ __forceinline__ size_t co_lay(const CloudOpticsArgs &a, size_t i, int k)
+{
+    const size_t kk = (size_t)(a.top_first ? a.nlay - 1 - k : k);
+    return a.layer_fastest ? i * (size_t)a.nlay + kk : i + a.ld * kk;
+}
+// ... and band b of taucld at that cell: (16,ld,nlay), or (ncol,nlay,16) in C order
+__device__ __forceinline__ size_t co_tau(const CloudOpticsArgs &a, size_t i, int k, int b)
+{
+    const size_t kk = (size_t)(a.top_first ? a.nlay - 1 - k : k);
+    return a.layer_fastest ? (i * (size_t)a.nlay + kk) * NBND + b : (size_t)b + (size_t)NBND * (i + a.ld * kk);
+}
+template <class R>
+__device__ __forceinline__ double co_tauctot(const CloudOpticsArgs &a, size_t i, int k)      // cldprop :180-183, in band order
+{
+#pragma clang fp contract(off)
+    double tauctot = 0.0;
+    for (int ib = 0; ib < NBND; ib++) tauctot = tauctot + co_get<R>(a.taucld, co_tau(a, i, k, ib));
+    return tauctot;
+}
+
+template <class R>
+__global__ __launch_bounds__(256) void k_cloudoptics_col(CloudOpticsArgs a)
+{
+#pragma clang fp contract(off)
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)a.ncol) return;
+    const int nlay = a.nlay;
+    if (a.nbat) {
+        int ncbands = a.imca ? NBND : 1;
+        if (!a.imca) {
+#pragma unroll 4
+            for (int k = 0; k < nlay; k++) {
+                const size_t at = co_lay(a, i, k);
+                const double cf = co_get<R>(a.cldfr, at), ciwp = co_get<R>(a.cicewp, at), clwp = co_get<R>(a.cliqwp, at);
+                const double cwp = ciwp + clwp;
+                bool enters = cf >= 1.e-20 && cwp >= 1.e-20;
+                if (cf >= 1.e-20 && !enters) enters = co_tauctot<R>(a, i, k) >= 1.e-20;
+                if (enters) {
+                    if (a.inflag == 0 || a.inflag == 1) ncbands = 16;
+                    else if (a.inflag == 2) {
+                        if (ciwp != 0.0) { if (a.iceflag == 1) ncbands = 5; else if (a.iceflag == 2 || a.iceflag == 3) ncbands = 16; }
+                        if (clwp != 0.0 && a.liqflag == 1) ncbands = 16;
+                    }
+                }
+                a.nbat[(size_t)k * a.ncol + i] = (unsigned char)ncbands;
+            }
+        }
+        a.nbat[(size_t)nlay * a.ncol + i] = (unsigned char)ncbands;
+        if (a.ncbands) a.ncbands[i] = ncbands;
+    }
+    if (!a.secdiff) return;
+    // inatm's column sums (src/rrtmg_lw_rad.nomcica.f90:795-863) and rtrn's secants (:280-288), as k_colprep forms them
+    const double amd = 28.9660, amw = 18.0160, avogad = 6.02214199e+23, grav = 9.8066;
+    const size_t nlev = (size_t)nlay + 1;
+    const auto lev_at = [&](int k) {
+        const size_t kk = (size_t)(a.top_first ? nlay - k : k);
+        return a.layer_fastest ? i * nlev + kk : i + a.ld * kk;
+    };
+    const double pz0 = co_get<R>(a.plev, lev_at(0));
+    double amttl = 0.0, wvttl = 0.0, pzlo = pz0;
+#pragma unroll 8
+    for (int k = 0; k < nlay; k++) {
+        const double w1v = co_get<R>(a.h2ovmr, co_lay(a, i, k));
+        const double pzl = co_get<R>(a.plev, lev_at(k + 1));
+        const double amm = (1. - w1v) * amd + w1v * amw;
+        const double coldry = (pzlo - pzl) * 1.e3 * avogad / (1.e2 * grav * amm * (1. + w1v));
+        pzlo = pzl;
+        const double w1 = coldry * w1v;
+        amttl = amttl + coldry + w1;
+        wvttl = wvttl + w1;
+    }
+    const double wvsh = (amw * wvttl) / (amd * amttl);
+    const double pwvcm = wvsh * (1.e3 * pz0) / (1.e2 * grav);
+    const double a0[16] = {1.66, 1.55, 1.58, 1.66, 1.54, 1.454, 1.89, 1.33, 1.668, 1.66, 1.66, 1.66, 1.66, 1.66, 1.66, 1.66};
+    const double a1[16] = {0.00, 0.25, 0.22, 0.00, 0.13, 0.446, -0.10, 0.40, -0.006, 0.00, 0.00, 0.00, 0.00, 0.00, 0.00, 0.00};
+    const double a2[16] = {0.00, -12.0, -11.7, 0.00, -0.72, -0.243, 0.19, -0.062, 0.414, 0.00, 0.00, 0.00, 0.00, 0.00, 0.00, 0.00};
+#pragma unroll
+    for (int b = 0; b < NBND; b++) {
+        double sd = 1.66;
+        if (!(b == 0 || b == 3 || b >= 9)) {
+            sd = a0[b] + a1[b] * exp(a2[b] * pwvcm);
+            if (sd > 1.80) sd = 1.80;
+            if (sd < 1.50) sd = 1.50;
+        }
+        static_cast<R *>(a.secdiff)[a.layer_fastest ? i * NBND + b : i + a.ld * b] = (R)sd;
+    }
+}
+
+template <class R>
+__global__ __launch_bounds__(256) void k_cloudoptics(DevTables T, CloudOpticsArgs a)
+{
+#pragma clang fp contract(off)
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)a.ncol) return;
+    const int k = blockIdx.y, nlay = a.nlay;
+    const double *S = T.stat;
+    const double *absice1 = S + T.sl.absice1, *absice2 = S + T.sl.absice2, *absice3 = S + T.sl.absice3, *absliq1 = S + T.sl.absliq1;
+    const double cldmin = 1.e-20;
+    const size_t at = co_lay(a, i, k);
+    const double cf = co_get<R>(a.cldfr, at), ciwp = co_get<R>(a.cicewp, at), clwp = co_get<R>(a.cliqwp, at);
+    const double cwp = ciwp + clwp;
+    const int inflag = a.inflag, iceflag = a.iceflag, liqflag = a.liqflag;
+    // (a band's value leaves as soon as it is formed: sixteen values indexed by a loop counter would live in scratch memory)
+    const size_t kk = (size_t)(a.top_first ? nlay - 1 - k : k);
+    const auto put = [&](int B, double v) {
+        if (a.taucloud) static_cast<R *>(a.taucloud)[a.layer_fastest ? (i * (size_t)nlay + kk) * NBND + (B - 1) : i + a.ld * (kk + (size_t)nlay * (B - 1))] = (R)v;
+    };
+    int err = 0;
+    bool formed = false;
+    if (!a.imca) {
+        // cldprop: the layer as a whole enters or does not; k_cloudlay's decisions
+        bool enters = cf >= cldmin && cwp >= cldmin;
+        if (cf >= cldmin && !enters) enters = co_tauctot<R>(a, i, k) >= cldmin;
+        if (enters) {
+            formed = true;
+            const int nb_at = a.nbat[(size_t)k * a.ncol + i], ncbands = a.nbat[(size_t)nlay * a.ncol + i];
+            int icemode = -1, liqmode = -1, iceind = 0, liqind = 0, index_i = 1, index_l = 1;
+            double radice = 0.0, ice_single = 0.0, fint_i = 0.0, liq_single = 0.0, fint_l = 0.0;
+            if (inflag == 2) {
+                radice = co_get<R>(a.reice, at);
+                if (ciwp == 0.0) { icemode = 0; ice_single = 0.0; iceind = 0; }
+                else if (iceflag == 0) {
+                    if (radice < 10.0) err = E_ICE_SMALL;
+                    icemode = 0; ice_single = T.absice0[0] + T.absice0[1] / radice; iceind = 0;
+                } else if (iceflag == 1) {
+                    if (radice < 13.0 || radice > 130.) err = E_ICE_BOUNDS;
+                    icemode = 1; iceind = 1;
+                } else if (iceflag == 2) {
+                    if (radice < 5.0 || radice > 131.0) err = E_ICE_BOUNDS;
+                    const double factor = (radice - 2.) / 3.;
+                    index_i = (int)factor; if (index_i == 43) index_i = 42;
+                    fint_i = factor - (double)index_i;
+                    index_i = clampi(index_i, 1, 42);           // (a size out of bounds, or NaN: the call fails or is garbage, but reads inside the table)
+                    icemode = 2; iceind = 2;
+                } else if (iceflag == 3) {
+                    if (radice < 5.0 || radice > 140.0) err = E_ICE_GEN_BOUNDS;
+                    const double factor = (radice - 2.) / 3.;
+                    index_i = (int)factor; if (index_i == 46) index_i = 45;
+                    fint_i = factor - (double)index_i;
+                    index_i = clampi(index_i, 1, 45);
+                    icemode = 3; iceind = 2;
+                } else err = E_BAD_FLAG;
+                if (clwp == 0.0) { liqmode = 0; liq_single = 0.0; liqind = 0; if (iceind == 1) iceind = 2; }
+                else if (liqflag == 0) { liqmode = 0; liq_single = T.absliq0; liqind = 0; if (iceind == 1) iceind = 2; }
+                else if (liqflag == 1) {
+                    const double radliq = co_get<R>(a.reliq, at);
+                    if ((radliq < 2.5 || radliq > 60.) && !err) err = E_LIQ_BOUNDS;      // (both sizes out: the reference stops at the ice check)
+                    index_l = (int)(radliq - 1.5);
+                    if (index_l == 0) index_l = 1;
+                    if (index_l == 58) index_l = 57;
+                    fint_l = radliq - 1.5 - (double)index_l;
+                    index_l = clampi(index_l, 1, 57);
+                    liqmode = 1; liqind = 2;
+                } else err = E_BAD_FLAG;
+            }
+#pragma unroll 1
+            for (int B = 1; B <= NBND; B++) {
+                const int ib = ncbands == 1 ? 1 : (ncbands == 5 ? icb_map(B, 1) : B);      // rtrn :343-349
+                double v = 0.0;
+                if (ib > nb_at) v = 0.0;                                                   // (not assigned while cldprop carried fewer bands)
+                else if (inflag == 0) v = co_get<R>(a.taucld, co_tau(a, i, k, ib - 1));
+                else if (inflag == 1) v = T.abscld1 * cwp;
+                else if (inflag == 2) {
+                    int ki = icb_map(ib, iceind);
+                    const int kl = icb_map(ib, liqind);
+                    if (icemode == 1 && ki > 5) ki = 5;         // the stated deviation: k_cloudlay, include/rrtmg_lw_hip.h
+                    double ai = 0.0, al = 0.0;
+                    if (icemode == 0) ai = ice_single;
+                    else if (icemode == 1) ai = absice1[2 * (ki - 1)] + absice1[2 * (ki - 1) + 1] / radice;
+                    else if (icemode == 2) { const double *tb = absice2 + 43 * (ki - 1); ai = tb[index_i - 1] + fint_i * (tb[index_i] - tb[index_i - 1]); }
+                    else if (icemode == 3) { const double *tb = absice3 + 46 * (ki - 1); ai = tb[index_i - 1] + fint_i * (tb[index_i] - tb[index_i - 1]); }
+                    if (liqmode == 0) al = liq_single;
+                    else if (liqmode == 1) { const double *tb = absliq1 + 58 * (kl - 1); al = tb[index_l - 1] + fint_l * (tb[index_l] - tb[index_l - 1]); }
+                    v = ciwp * ai + clwp * al;
+                }
+                put(B, v);
+            }
+        }
+    } else if (cf >= cldmin) {
+        formed = true;
+        // cldprmc on a cloudy sub-column of this layer (the generator gives it the grid-mean values): every band's cell on its own
+        const bool water = cwp >= cldmin;
+        int ice_err = 0, liq_err = 0, index_i = 1, index_l = 1;
+        double radice = 0.0, fint_i = 0.0, fint_l = 0.0;
+        bool sized = false;
+#pragma unroll 1
+        for (int B = 1; B <= NBND; B++) {
+            const double tb_in = co_get<R>(a.taucld, co_tau(a, i, k, B - 1));
+            double v = tb_in;
+            if (water || tb_in >= cldmin) {                                 // cldprmc :181-183 with cldfmc = 1
+                if (inflag == 1) err = E_MC_INFLAG1;
+                else if (inflag == 2) {
+                    if (!sized) {                                           // the table positions (band independent), k_cloudmc's
+                        sized = true;
+                        if (ciwp != 0.0) {
+                            radice = co_get<R>(a.reice, at);
+                            if (iceflag == 0) { if (radice < 10.0) ice_err = E_ICE_SMALL; }
+                            else if (iceflag == 1) { if (radice < 13.0 || radice > 130.) ice_err = E_ICE_BOUNDS; }
+                            else if (iceflag == 2 || iceflag == 3) {
+                                const int top = iceflag == 2 ? 43 : 46;
+                                if (radice < 5.0 || radice > (iceflag == 2 ? 131.0 : 140.0)) ice_err = iceflag == 2 ? E_ICE_BOUNDS : E_ICE_GEN_BOUNDS;
+                                const double factor = (radice - 2.) / 3.;
+                                index_i = (int)factor; if (index_i == top) index_i = top - 1;
+                                fint_i = factor - (double)index_i;
+                                index_i = clampi(index_i, 1, top - 1);
+                            }
+                        }
+                        if (clwp != 0.0 && liqflag == 1) {
+                            const double radliq = co_get<R>(a.reliq, at);
+                            if (radliq < 2.5 || radliq > 60.) liq_err = E_LIQ_BOUNDS;
+                            index_l = (int)(radliq - 1.5);
+                            if (index_l == 0) index_l = 1;
+                            if (index_l == 58) index_l = 57;
+                            fint_l = radliq - 1.5 - (double)index_l;
+                            index_l = clampi(index_l, 1, 57);
+                        }
+                        if (!err) err = ice_err ? ice_err : liq_err;        // (ice is checked first: cldprmc :204-254)
+                    }
+                    double ai = 0.0, al = 0.0;
+                    if (ciwp != 0.0) {
+                        if (iceflag == 0) ai = T.absice0[0] + T.absice0[1] / radice;
+                        else if (iceflag == 1) { const int icx = icb_map(B, 1); ai = absice1[2 * (icx - 1)] + absice1[2 * (icx - 1) + 1] / radice; }
+                        else if (iceflag == 2) { const double *tb = absice2 + 43 * (B - 1); ai = tb[index_i - 1] + fint_i * (tb[index_i] - tb[index_i - 1]); }
+                        else if (iceflag == 3) { const double *tb = absice3 + 46 * (B - 1); ai = tb[index_i - 1] + fint_i * (tb[index_i] - tb[index_i - 1]); }
+                    }
+                    if (clwp != 0.0) {
+                        if (liqflag == 0) al = T.absliq0;
+                        else if (liqflag == 1) { const double *tb = absliq1 + 58 * (B - 1); al = tb[index_l - 1] + fint_l * (tb[index_l] - tb[index_l - 1]); }
+                    }
+                    v = ciwp * ai + clwp * al;
+                }
+            }
+            put(B, v);
+        }
+    }
+    if (err) atomicCAS(a.err, 0, err);
+    if (!formed) for (int B = 1; B <= NBND; B++) put(B, 0.0);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 !  Device-pointer entries for a GPU-resident Fortran host (this library's extension; include/rrtmg_lw_hip.h, "Device arrays with a column
 !  stride"; INTEGRATION.md 4g):
 !      use rrtmg_lw_device, only: rrtmg_lw_dev, rrtmg_lw_mcica_dev, rrtmg_lw_dtsfc_dev, rrtmg_lw_dev_check, rrtmg_lw_dev_status, &
-!                                 rrtmg_lw_mcica_samples_dev, rrtmg_lw_alpha_dev, rrtmg_lw_cloud_cover_dev
+!                                 rrtmg_lw_mcica_samples_dev, rrtmg_lw_alpha_dev, rrtmg_lw_cloud_cover_dev, rrtmg_lw_cloud_optics_dev
 !      call rrtmg_lw_dev(ncol, ld, nlay, icld, idrv, play, plev, ..., uflx, dflx, hr, uflxc, dflxc, hrc &
 !                        [, duflx_dt, duflxc_dt, uflxs, dflxs, uflxcs, dflxcs, stream])
 !      call rrtmg_lw_dev_check([stream])
@@ -45,6 +45,11 @@
 !  rrtmg_lw_mcica_dev / rrtmg_lw_mcica_samples_dev with the same icld, seeds, irng, play, cldfr and alpha see, counted.  play, cldfr,
 !  alpha, cldcum, cldlay (ld,*), cldtot(*), submask(ld,nlay,*) integer(4); the outputs are optional, each on its own (pass them by
 !  keyword), at least one must be present; submask with nsamp = 1 only.
+!      rrtmg_lw_cloud_optics_dev(ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq &
+!                                [, plev, h2ovmr, taucloud, ncbands, secdiff, stream])
+!  is rrtmg_lw_cloud_optics (module rrtmg_lw_optics) on device arrays (rrtmg_lw_hip_cloud_optics_device_view): cldfr, cicewp, cliqwp,
+!  reice, reliq, plev, h2ovmr (ld,*), taucld(16,ld,*), taucloud(ld,nlay,*), secdiff(ld,*), ncbands(*) integer(4); the outputs are
+!  optional, each on its own (pass them by keyword), at least one must be present; secdiff needs plev and h2ovmr.
       module rrtmg_lw_device
 
       use iso_c_binding
@@ -55,7 +60,7 @@
 
       private
       public :: rrtmg_lw_dev, rrtmg_lw_mcica_dev, rrtmg_lw_dtsfc_dev, rrtmg_lw_dev_check, rrtmg_lw_dev_status
-      public :: rrtmg_lw_mcica_samples_dev, rrtmg_lw_alpha_dev, rrtmg_lw_cloud_cover_dev
+      public :: rrtmg_lw_mcica_samples_dev, rrtmg_lw_alpha_dev, rrtmg_lw_cloud_cover_dev, rrtmg_lw_cloud_optics_dev
 
       integer, parameter :: r4 = c_float
 
@@ -77,6 +82,10 @@
       end interface
       interface rrtmg_lw_cloud_cover_dev
          module procedure rrtmg_lw_cloud_cover_dev_r8, rrtmg_lw_cloud_cover_dev_r4, rrtmg_lw_cloud_cover_dev_r8_at, rrtmg_lw_cloud_cover_dev_r4_at
+      end interface
+
+      interface rrtmg_lw_cloud_optics_dev
+         module procedure rrtmg_lw_cloud_optics_dev_r8, rrtmg_lw_cloud_optics_dev_r4, rrtmg_lw_cloud_optics_dev_r8_at, rrtmg_lw_cloud_optics_dev_r4_at
       end interface
 
       ! rrtmg_lw_hip_array_view
@@ -153,6 +162,14 @@
             type(c_ptr), value :: play, cldfr, alpha, cldtot, cldcum, cldlay, submask, stream
             integer(c_int) :: rc
          end function rrtmg_lw_hip_mcica_cloud_cover_device_view
+         function rrtmg_lw_hip_cloud_optics_device_view(view, ncol, nlay, imca, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, &
+               reice, reliq, plev, h2ovmr, taucloud, ncbands, secdiff, stream) bind(C, name='rrtmg_lw_hip_cloud_optics_device_view') result(rc)
+            import :: c_int, c_ptr, array_view
+            type(array_view), intent(in) :: view
+            integer(c_int), value :: ncol, nlay, imca, inflglw, iceflglw, liqflglw
+            type(c_ptr), value :: cldfr, taucld, cicewp, cliqwp, reice, reliq, plev, h2ovmr, taucloud, ncbands, secdiff, stream
+            integer(c_int) :: rc
+         end function rrtmg_lw_hip_cloud_optics_device_view
          function rrtmg_lw_hip_check(stream) bind(C, name='rrtmg_lw_hip_check') result(rc)
             import :: c_int, c_ptr
             type(c_ptr), value :: stream
@@ -1221,6 +1238,117 @@
       call dev_cover(4, ncol, ld, nlay, icld, permuteseed, nsamp, seedstep, irng, c_loc(play), c_loc(cldfr), p, stream)
 
       end subroutine rrtmg_lw_cloud_cover_dev_r4_at
+
+      subroutine rrtmg_lw_cloud_optics_dev_r8 &
+            (ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, plev, h2ovmr, &
+             taucloud, ncbands, secdiff, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw
+      real(kind=rb), target :: cldfr(ld,*), taucld(16,ld,*), cicewp(ld,*), cliqwp(ld,*), reice(ld,*), reliq(ld,*)
+      real(kind=rb), target, optional :: plev(ld,*), h2ovmr(ld,*), taucloud(ld,nlay,*), secdiff(ld,*)
+      integer(c_int32_t), target, optional :: ncbands(*)
+      type(c_ptr), intent(in), optional :: stream
+
+      type(c_ptr) :: p(11)
+
+      p = c_null_ptr
+      p(1) = c_loc(cldfr); p(2) = c_loc(taucld); p(3) = c_loc(cicewp); p(4) = c_loc(cliqwp); p(5) = c_loc(reice); p(6) = c_loc(reliq)
+      if (present(plev)) p(7) = c_loc(plev)
+      if (present(h2ovmr)) p(8) = c_loc(h2ovmr)
+      if (present(taucloud)) p(9) = c_loc(taucloud)
+      if (present(ncbands)) p(10) = c_loc(ncbands)
+      if (present(secdiff)) p(11) = c_loc(secdiff)
+      call dev_cloud_optics(8, ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw, p, stream)
+
+      end subroutine rrtmg_lw_cloud_optics_dev_r8
+
+      subroutine rrtmg_lw_cloud_optics_dev_r4 &
+            (ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, plev, h2ovmr, &
+             taucloud, ncbands, secdiff, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw
+      real(kind=r4), target :: cldfr(ld,*), taucld(16,ld,*), cicewp(ld,*), cliqwp(ld,*), reice(ld,*), reliq(ld,*)
+      real(kind=r4), target, optional :: plev(ld,*), h2ovmr(ld,*), taucloud(ld,nlay,*), secdiff(ld,*)
+      integer(c_int32_t), target, optional :: ncbands(*)
+      type(c_ptr), intent(in), optional :: stream
+
+      type(c_ptr) :: p(11)
+
+      p = c_null_ptr
+      p(1) = c_loc(cldfr); p(2) = c_loc(taucld); p(3) = c_loc(cicewp); p(4) = c_loc(cliqwp); p(5) = c_loc(reice); p(6) = c_loc(reliq)
+      if (present(plev)) p(7) = c_loc(plev)
+      if (present(h2ovmr)) p(8) = c_loc(h2ovmr)
+      if (present(taucloud)) p(9) = c_loc(taucloud)
+      if (present(ncbands)) p(10) = c_loc(ncbands)
+      if (present(secdiff)) p(11) = c_loc(secdiff)
+      call dev_cloud_optics(4, ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw, p, stream)
+
+      end subroutine rrtmg_lw_cloud_optics_dev_r4
+
+      subroutine rrtmg_lw_cloud_optics_dev_r8_at &
+            (ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, plev, h2ovmr, &
+             taucloud, ncbands, secdiff, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw
+      real(kind=rb), target :: cldfr, taucld, cicewp, cliqwp, reice, reliq
+      real(kind=rb), target, optional :: plev, h2ovmr, taucloud, secdiff
+      integer(c_int32_t), target, optional :: ncbands
+      type(c_ptr), intent(in), optional :: stream
+
+      type(c_ptr) :: p(11)
+
+      p = c_null_ptr
+      p(1) = c_loc(cldfr); p(2) = c_loc(taucld); p(3) = c_loc(cicewp); p(4) = c_loc(cliqwp); p(5) = c_loc(reice); p(6) = c_loc(reliq)
+      if (present(plev)) p(7) = c_loc(plev)
+      if (present(h2ovmr)) p(8) = c_loc(h2ovmr)
+      if (present(taucloud)) p(9) = c_loc(taucloud)
+      if (present(ncbands)) p(10) = c_loc(ncbands)
+      if (present(secdiff)) p(11) = c_loc(secdiff)
+      call dev_cloud_optics(8, ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw, p, stream)
+
+      end subroutine rrtmg_lw_cloud_optics_dev_r8_at
+
+      subroutine rrtmg_lw_cloud_optics_dev_r4_at &
+            (ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, plev, h2ovmr, &
+             taucloud, ncbands, secdiff, stream)
+
+      integer(kind=im), intent(in) :: ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw
+      real(kind=r4), target :: cldfr, taucld, cicewp, cliqwp, reice, reliq
+      real(kind=r4), target, optional :: plev, h2ovmr, taucloud, secdiff
+      integer(c_int32_t), target, optional :: ncbands
+      type(c_ptr), intent(in), optional :: stream
+
+      type(c_ptr) :: p(11)
+
+      p = c_null_ptr
+      p(1) = c_loc(cldfr); p(2) = c_loc(taucld); p(3) = c_loc(cicewp); p(4) = c_loc(cliqwp); p(5) = c_loc(reice); p(6) = c_loc(reliq)
+      if (present(plev)) p(7) = c_loc(plev)
+      if (present(h2ovmr)) p(8) = c_loc(h2ovmr)
+      if (present(taucloud)) p(9) = c_loc(taucloud)
+      if (present(ncbands)) p(10) = c_loc(ncbands)
+      if (present(secdiff)) p(11) = c_loc(secdiff)
+      call dev_cloud_optics(4, ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw, p, stream)
+
+      end subroutine rrtmg_lw_cloud_optics_dev_r4_at
+
+      ! ... of rrtmg_lw_cloud_optics_dev: p in the C entry's order (the six cloud arrays, plev, h2ovmr, taucloud, ncbands, secdiff; null where absent)
+      subroutine dev_cloud_optics(real_bytes, ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw, p, stream)
+      integer, intent(in) :: real_bytes
+      integer(kind=im), intent(in) :: ncol, ld, nlay, imca, inflglw, iceflglw, liqflglw
+      type(c_ptr), intent(in) :: p(11)
+      type(c_ptr), intent(in), optional :: stream
+
+      type(array_view) :: view
+      type(c_ptr) :: s
+      integer(c_int) :: rc
+
+      view = array_view(int(real_bytes, c_int), 0_c_int, 0_c_int, int(ld, c_int))
+      s = c_null_ptr
+      if (present(stream)) s = stream
+      rc = rrtmg_lw_hip_cloud_optics_device_view(view, int(ncol, c_int), int(nlay, c_int), int(imca, c_int), int(inflglw, c_int), &
+            int(iceflglw, c_int), int(liqflglw, c_int), p(1), p(2), p(3), p(4), p(5), p(6), p(7), p(8), p(9), p(10), p(11), s)
+      if (rc /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_cloud_optics_dev')
+      end subroutine dev_cloud_optics
 
       ! what every specific of rrtmg_lw_dev / rrtmg_lw_mcica_dev ends in: the addresses in the C entry's order - pin: the 23 input arrays
       ! of rrtmg_lw, then alpha; pout: the eight broadband outputs, then the spectral four (null where absent)

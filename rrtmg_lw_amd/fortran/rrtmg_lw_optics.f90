@@ -9,6 +9,17 @@
 !  ngptlw = rrtmg_lw_hip_gpoints() (140, or 256 with librrtmg_lw_hip_g256.so).  The Planck outputs are optional; an absent one is not
 !  formed.  dplankbnd_dt present = idrv 1.  Arrays larger than the declared shapes (pcols > ncol) or strided sections are accepted as
 !  in rrtmg_lw_rad: the inputs go across as the section (1:ncol, ...), the outputs through temporaries where they are not exactly sized.
+!
+!  Cloud optics (include/rrtmg_lw_hip.h, "Cloud optics: band optical depths, ncbands, secdiff"):
+!      use rrtmg_lw_optics, only: rrtmg_lw_cloud_optics
+!      call rrtmg_lw_cloud_optics(ncol, nlay, imca, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq &
+!                                 [, plev, h2ovmr] [, taucloud] [, ncbands] [, secdiff])
+!  The cloud inputs of rrtmg_lw (taucld (nbndlw,ncol,nlay)); imca = 0: cldprop, 1: cldprmc on a cloudy sub-column.  Outputs, each optional,
+!  at least one present (pass them by keyword):
+!      taucloud       (ncol,nlay,nbndlw)  cloud optical depth per spectral band, before the diffusivity secant
+!      ncbands        (ncol)              cldprop's band count at the end of the column (16 with imca = 1)
+!      secdiff        (ncol,nbndlw)       the diffusivity secants; needs plev (ncol,nlay+1) and h2ovmr (ncol,nlay)
+!  Larger arrays (pcols > ncol) as above.  A particle size out of bounds ends the program with the reference's text (rrtmg_lw_hip_abort).
       module rrtmg_lw_optics
 
       use iso_c_binding
@@ -17,9 +28,17 @@
 
       implicit none
 
-      public :: rrtmg_lw_gas_optics
+      public :: rrtmg_lw_gas_optics, rrtmg_lw_cloud_optics
 
       interface
+         function rrtmg_lw_hip_cloud_optics(ncol, nlay, imca, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, &
+               plev, h2ovmr, taucloud, ncbands, secdiff) bind(C, name='rrtmg_lw_hip_cloud_optics') result(rc)
+            import :: c_int, c_double, c_ptr
+            integer(c_int), value :: ncol, nlay, imca, inflglw, iceflglw, liqflglw
+            real(c_double), intent(in) :: cldfr(*), taucld(*), cicewp(*), cliqwp(*), reice(*), reliq(*)
+            type(c_ptr), value :: plev, h2ovmr, taucloud, ncbands, secdiff
+            integer(c_int) :: rc
+         end function rrtmg_lw_hip_cloud_optics
          function rrtmg_lw_hip_gas_optics(ncol, nlay, idrv, play, plev, tlay, tlev, tsfc, &
                h2ovmr, o3vmr, co2vmr, ch4vmr, n2ovmr, o2vmr, cfc11vmr, cfc12vmr, cfc22vmr, ccl4vmr, emis, &
                taug, fracs, planklay, planklev, plankbnd, dplankbnd_dt) bind(C, name='rrtmg_lw_hip_gas_optics') result(rc)
@@ -92,6 +111,62 @@
       if (allocated(t6)) dplankbnd_dt(1:ncol, 1:16) = t6
 
       end subroutine rrtmg_lw_gas_optics
+
+      subroutine rrtmg_lw_cloud_optics &
+            (ncol    ,nlay    ,imca    ,inflglw ,iceflglw,liqflglw, &
+             cldfr   ,taucld  ,cicewp  ,cliqwp  ,reice   ,reliq   , &
+             plev    ,h2ovmr  ,taucloud,ncbands ,secdiff)
+
+      integer(kind=im), intent(in) :: ncol, nlay
+      integer(kind=im), intent(in) :: imca            ! 0: cldprop, 1: cldprmc on a cloudy sub-column
+      integer(kind=im), intent(in) :: inflglw, iceflglw, liqflglw
+      real(kind=rb), intent(in) :: cldfr(:,:)         ! Cloud fraction                      (ncol,nlay)
+      real(kind=rb), intent(in) :: taucld(:,:,:)      ! In-cloud optical depth              (nbndlw,ncol,nlay)
+      real(kind=rb), intent(in) :: cicewp(:,:), cliqwp(:,:), reice(:,:), reliq(:,:)
+      real(kind=rb), intent(in), optional :: plev(:,:), h2ovmr(:,:)                     ! (ncol,nlay+1), (ncol,nlay): with secdiff
+      real(kind=rb), intent(out), optional, target :: taucloud(:,:,:)                   ! (ncol,nlay,nbndlw)
+      integer(kind=im), intent(out), optional :: ncbands(:)                             ! (ncol)
+      real(kind=rb), intent(out), optional, target :: secdiff(:,:)                      ! (ncol,nbndlw)
+
+      integer(c_int) :: rc
+      real(c_double), allocatable, target :: t1(:,:,:), t3(:,:), hp(:,:), hh(:,:)
+      integer(c_int), allocatable, target :: nb(:)
+      type(c_ptr) :: p1, p2, p3, pp, ph
+
+      call check_extent('cldfr', size(cldfr,1), size(cldfr,2), ncol, nlay)
+      call check_extent('taucld', size(taucld,2), size(taucld,3), ncol, nlay)
+      p1 = c_null_ptr; p2 = c_null_ptr; p3 = c_null_ptr; pp = c_null_ptr; ph = c_null_ptr
+      if (present(taucloud)) call out3('taucloud', taucloud, t1, p1, ncol, nlay, 16)
+      if (present(ncbands)) then
+         if (size(ncbands) < ncol) then
+            write(*,'(a)') 'rrtmg_lw_cloud_optics: ncbands smaller than (ncol)'
+            error stop 1
+         endif
+         allocate(nb(ncol))
+         p2 = c_loc(nb)
+      endif
+      if (present(secdiff)) then
+         if (.not. (present(plev) .and. present(h2ovmr))) then
+            write(*,'(a)') 'rrtmg_lw_cloud_optics: secdiff needs plev and h2ovmr'
+            error stop 1
+         endif
+         call check_extent('plev', size(plev,1), size(plev,2), ncol, nlay+1)
+         call check_extent('h2ovmr', size(h2ovmr,1), size(h2ovmr,2), ncol, nlay)
+         call out2('secdiff', secdiff, t3, p3, ncol)
+         allocate(hp(ncol, nlay+1), hh(ncol, nlay))
+         hp = plev(1:ncol, 1:nlay+1)
+         hh = h2ovmr(1:ncol, 1:nlay)
+         pp = c_loc(hp); ph = c_loc(hh)
+      endif
+      rc = rrtmg_lw_hip_cloud_optics(int(ncol, c_int), int(nlay, c_int), int(imca, c_int), int(inflglw, c_int), int(iceflglw, c_int), &
+            int(liqflglw, c_int), cldfr(1:ncol,1:nlay), taucld(1:16,1:ncol,1:nlay), cicewp(1:ncol,1:nlay), cliqwp(1:ncol,1:nlay), &
+            reice(1:ncol,1:nlay), reliq(1:ncol,1:nlay), pp, ph, p1, p2, p3)
+      if (rc /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_cloud_optics')
+      if (allocated(t1)) taucloud(1:ncol, 1:nlay, 1:16) = t1
+      if (allocated(nb)) ncbands(1:ncol) = int(nb, kind=im)
+      if (allocated(t3)) secdiff(1:ncol, 1:16) = t3
+
+      end subroutine rrtmg_lw_cloud_optics
 
       ! an output (n1,n2,n3): exactly sized, contiguous actuals go across in place; larger or strided ones through the temporary t,
       ! copied back after the call

@@ -887,6 +887,76 @@ int rrtmg_lw_hip_cloud_optics_device_view(const rrtmg_lw_hip_array_view *view,
     const void *reice, const void *reliq, const void *plev, const void *h2ovmr,
     void *taucloud, int *ncbands, void *secdiff, void *stream);
 
+/* ---- The solver on the caller's optical depths and sources -------------------------------------------------------------------------------
+ * The gas-optics, cloud-optics and cloud-cover entries hand out every piece the solver consumes; these two turn such arrays - the
+ * library's own, or a host's changed ones (an emulator in place of taumol, another cloud parametrisation, aerosol terms, perturbed
+ * optical depths) - back into fluxes and heating rates: the level loops of rtrn (src/rrtmg_lw_rtrn.f90:361-604) and rtrnmc
+ * (src/rrtmg_lw_rtrnmc.f90) in float64, each operation rounding on its own, on the float64 tables exp_tbl, tfn_tbl, tau_tbl of
+ * src/rrtmg_lw_init.f90:125-142.  Two kernels of their own; the production sweeps and their cell codes are not used.
+ * All arrays float64, column-fastest, layer 1 at the surface, laid out as the optics entries write them (NG = rrtmg_lw_hip_gpoints(),
+ * MW = (NG + 31) / 32, band of g: ngb):
+ *   plev (ncol,nlay+1); emis, plankbnd, dplankbnd_dt (ncol,16); tau, fracs (ncol,nlay,NG); planklay, odcld (ncol,nlay,16);
+ *   planklev (ncol,nlay+1,16), level 0 the surface; cldfr (ncol,nlay); submask (ncol,nlay,MW) unsigned 32-bit as
+ *   rrtmg_lw_hip_mcica_cloud_cover writes it; the outputs as in rrtmg_lw_hip_run_nomcica.
+ *   tau    the clear-sky optical depth along the diffusivity path, secdiff(band of g) * (taug + tauaer(band of g)): the caller forms it.
+ *          A negative value is taken as 0 (rtrn :372).
+ *   odcld  the cloud optical depth along the same path per spectral band B: from the cloud-optics outputs secdiff(icb) * taucloud(B) for
+ *          cloud = 1 and secdiff(B) * taucloud(B) for cloud = 2 ("Cloud optics", above).
+ * cloud = 0: cldfr, odcld and submask are not read; the total-sky outputs equal the clear-sky ones.
+ * cloud = 1: rtrn, random overlap: layer k is cloudy when cldfr(k) >= 1e-6, with cf = cldfr(k), odc = odcld(k, B) in every g-point of B.
+ * cloud = 2: rtrnmc: layer k is cloudy when any of the NG bits of submask(k, .) is set (bits at and above NG are ignored); in cell (k, g)
+ *            cf = 1, odc = odcld(k, B) where bit g is set, cf = 0, odc = 0 where it is not.
+ * efc = (1 - exp(-odc)) * cf.  Per g-point of band B, with od = max(tau, 0), f = fracs, blay = planklay(k, B), dup = planklev(k, B) - blay
+ * (the layer's upper interface), ddn = planklev(k-1, B) - blay, idx(x) = int(1e4 * (x / (bpade + x)) + 0.5), bpade = 1 / 0.278, the
+ * division an IEEE division, rec_6 = 0.166667:
+ *   a clear layer:  od <= 0.06: atrans = od - 0.5 * od * od, t = rec_6 * od;  else  i = idx(od), atrans = 1 - exp_tbl(i), t = tfn_tbl(i);
+ *                   bbd = f * (blay + ddn * t), bbu = f * (blay + dup * t);
+ *                   down  rad = rad + (bbd - rad) * atrans;   up  rad = rad + (bbu - rad) * atrans,  drad = drad * (1 - atrans)
+ *   a cloudy layer: odtot = od + odc.  odtot < 0.06: atrans, t as above, atot = odtot - 0.5 * odtot * odtot, tt = rec_6 * odtot;
+ *                   else od <= 0.06: atrans, t as above, j = idx(odtot), atot = 1 - exp_tbl(j), tt = tfn_tbl(j);
+ *                   else i = idx(od), od = tau_tbl(i), atrans = 1 - exp_tbl(i), t = tfn_tbl(i), odtot = od + odc, j, atot, tt as before;
+ *                   bbd, bbu as above, bbdtot = f * (blay + ddn * tt), bbutot = f * (blay + dup * tt), gassrc = bbd * atrans going down
+ *                   (atrans * f * (blay + t * ddn) in the third case), bbu * atrans going up;
+ *                   rad = rad - rad * (atrans + efc * (1 - atrans)) + gassrc + cf * (bb.tot * atot - gassrc);
+ *                   up  drad = drad * cf * (1 - atot) + drad * (1 - cf) * (1 - atrans)
+ *   The downward radiance starts at 0 above the top layer; at the surface rad = f(1) * plankbnd(B) + (1 - emis(B)) * rad_down and, with
+ *   idrv = 1, drad = f(1) * dplankbnd_dt(B).  The clear-sky stream is the total one down to the first cloudy layer met from the top
+ *   (iclddn) - in a column without cloud everywhere -; from there on, down and up again, it takes the clear-layer step with the cell's
+ *   atrans, bbd and bbu.  The branch tests are the reference's, literally: odtot < 0.06, od <= 0.06.
+ *   flux(level) = fluxfac * sum over B of delwave(B) * 0.5 * sum over the g-points of B of rad (the derivatives alike); the order of
+ *   these sums is the library's.  hr(l) = heatfac * (net(l) - net(l+1)) / (plev(l) - plev(l+1)), net = up - down, as
+ *   rrtmg_lw_hip_adjust_tsfc defines it.
+ * uflx, dflx and hr are required; uflxc, dflxc and hrc are all set or all NULL; dplankbnd_dt, duflx_dt and duflxc_dt are needed with
+ * idrv = 1 only and not touched otherwise.  A NULL output is neither formed nor touched.
+ * RRTMG_LW_HIP_EARG, with a text that names the argument and before anything is written: cloud other than 0, 1, 2; idrv other than 0,
+ * 1; a missing required array; a half-given clear-sky triple; the dimension limits of the other entries; an output that shares a byte
+ * with an input the call reads or with another output.  There are no physics errors: a non-finite input gives non-finite output in its
+ * own column only.
+ * rrtmg_lw_hip_solve_device: DEVICE pointers; the device is that of tau; it enqueues on `stream` and does not synchronise.  The entry
+ * lock, no graph replay, no combining.  Column batches of rrtmg_lw_hip_effective_batch(nlay); per batch k_solve - one thread per (column,
+ * band), the band's g-points four at a time in registers, the upward sweep reading tau and fracs again instead of keeping per-level values -
+ * and k_solve_flux, one thread per column.  The only workspace is the per-band partial sums, 16 x (nlay + 1) x 8 B per column of a
+ * batch for each of upward, downward (cloud = 0), their clear-sky pair (cloud != 0) and the derivatives (idrv = 1); counted in
+ * rrtmg_lw_hip_workspace_bytes.  A column's results do not depend on its neighbours or on the batch size, to the last bit.
+ * rrtmg_lw_hip_solve: HOST pointers, the first device; staged in column batches (rrtmg_lw_hip_set_batch, at most 16 384) through the
+ * host-entry staging buffer, as rrtmg_lw_hip_cloud_optics does.  Synchronises.
+ * Not offered: rtrnmr (maximum-random overlap), array forms and views, _r4, spectral outputs, fan-out over several devices, graph
+ * replay. */
+int rrtmg_lw_hip_solve(int ncol, int nlay, int cloud, int idrv,
+    const double *plev, const double *emis,
+    const double *tau, const double *fracs,
+    const double *planklay, const double *planklev, const double *plankbnd, const double *dplankbnd_dt,
+    const double *cldfr, const double *odcld, const unsigned *submask,
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
+    double *duflx_dt, double *duflxc_dt);
+int rrtmg_lw_hip_solve_device(int ncol, int nlay, int cloud, int idrv,
+    const double *plev, const double *emis,
+    const double *tau, const double *fracs,
+    const double *planklay, const double *planklev, const double *plankbnd, const double *dplankbnd_dt,
+    const double *cldfr, const double *odcld, const unsigned *submask,
+    double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc,
+    double *duflx_dt, double *duflxc_dt, void *stream);
+
 /* ---- Host arrays of a host built with 4-byte reals ("_r4") ----------------------------------------------------------------------------
  * A host model that carries RRTMG_LW at the default real kind (no -r8) owns float arrays.  These four entries take them as they are:
  * HOST pointers, every floating-point array of the call - inputs and outputs, alpha too - `float`.  Layout, argument order, the in/out

@@ -1096,6 +1096,97 @@ def cloud_optics_device(d, out, imca=0, stream=None, form=None, ld=None):
         _check(lib().rrtmg_lw_hip_cloud_optics_device_view(view, *args))
 
 
+_SOLVE_IN = ("plev", "emis", "tau", "fracs", "planklay", "planklev", "plankbnd", "dplankbnd_dt", "cldfr", "odcld", "submask")
+_SOLVE_OUT = ("uflx", "dflx", "hr", "uflxc", "dflxc", "hrc", "duflx_dt", "duflxc_dt")
+
+
+def _solve_shapes(ncol, nlay):
+    ng, mw = gpoints(), mask_words()
+    ins = dict(plev=(ncol, nlay + 1), emis=(ncol, NBND), tau=(ncol, nlay, ng), fracs=(ncol, nlay, ng), planklay=(ncol, nlay, NBND),
+               planklev=(ncol, nlay + 1, NBND), plankbnd=(ncol, NBND), dplankbnd_dt=(ncol, NBND), cldfr=(ncol, nlay), odcld=(ncol, nlay, NBND),
+               submask=(ncol, nlay, mw))
+    lev, lay = (ncol, nlay + 1), (ncol, nlay)
+    outs = dict(uflx=lev, dflx=lev, hr=lay, uflxc=lev, dflxc=lev, hrc=lay, duflx_dt=lev, duflxc_dt=lev)
+    return ins, outs
+
+
+def _solve_needed(cloud, idrv):
+    """the inputs a solve call reads"""
+    return _SOLVE_IN[:7] + (("dplankbnd_dt",) if idrv == 1 else ()) + (("cldfr",) if cloud == 1 else ()) + (("odcld",) if cloud in (1, 2) else ()) + \
+        (("submask",) if cloud == 2 else ())
+
+
+def solve(d, cloud=0, idrv=0, out=None):
+    """Fluxes and heating rates from the caller's optical depths and sources (rrtmg_lw_hip_solve; include/rrtmg_lw_hip.h states the
+    recurrences): cloud = 0 no cloud, 1 rtrn on cldfr and odcld, 2 rtrnmc on submask and odcld.  `d`: ncol, nlay and Fortran-ordered
+    numpy float64 arrays plev (ncol, nlay+1), emis, plankbnd (ncol, 16), tau, fracs (ncol, nlay, gpoints()), planklay (ncol, nlay, 16),
+    planklev (ncol, nlay+1, 16), with idrv = 1 dplankbnd_dt (ncol, 16), with cloud = 1 cldfr (ncol, nlay), with cloud != 0 odcld
+    (ncol, nlay, 16), with cloud = 2 submask (ncol, nlay, mask_words()) uint32 - the layouts gas_optics, cloud_optics and
+    mcica_cloud_cover return.  Returns a dict of Fortran-ordered arrays uflx, dflx, uflxc, dflxc (ncol, nlay+1), hr, hrc (ncol, nlay) and,
+    with idrv = 1, duflx_dt, duflxc_dt.  `out` may hold preallocated arrays; the clear-sky triple set to None there is not formed.
+    An array of another dtype or shape is refused (TypeError / ValueError), not converted."""
+    ncol, nlay, cloud, idrv = int(d["ncol"]), int(d["nlay"]), int(cloud), int(idrv)
+    in_shapes, out_shapes = _solve_shapes(ncol, nlay)
+    out = {} if out is None else out
+    for k in out:
+        if k not in _SOLVE_OUT:
+            raise ValueError(f"unknown output {k!r}: one of {_SOLVE_OUT}")
+    for k in _SOLVE_OUT:
+        if k not in out and (idrv == 1 or not k.startswith("du")):
+            out[k] = np.zeros(out_shapes[k], order="F")
+    null = C.cast(None, _dp)
+    ins = []
+    for k in _SOLVE_IN:
+        if k not in _solve_needed(cloud, idrv):
+            ins.append(null)
+            continue
+        a, want = d.get(k), np.uint32 if k == "submask" else np.float64
+        if not isinstance(a, np.ndarray) or a.dtype != want:
+            raise TypeError(f"solve: {k!r} must be a numpy {np.dtype(want).name} array, not {getattr(a, 'dtype', type(a).__name__)}")
+        ins.append(_f(a, in_shapes[k], dtype=want))
+    outs = [_p(_out_ok(out[k], out_shapes[k], k)) if out.get(k) is not None else null for k in _SOLVE_OUT]
+    _check(lib().rrtmg_lw_hip_solve(C.c_int(ncol), C.c_int(nlay), C.c_int(cloud), C.c_int(idrv), *[a if a is null else _p(a) for a in ins], *outs))
+    return out
+
+
+def solve_device(d, out, cloud=0, idrv=None, stream=None):
+    """Device-resident solve: `d` holds ncol, nlay and torch CUDA float64 tensors in the reference form (column-fastest; submask
+    torch.int32 or torch.uint32) under the names of solve, `out` the preallocated output tensors: uflx, dflx, hr, the clear-sky triple
+    all or none, duflx_dt and duflxc_dt with idrv = 1 (idrv = None: 1 when `out` holds duflx_dt).  A tensor that is not exactly the
+    reference form - dtype, shape, strides - is refused.  Enqueues on `stream`, does not synchronise."""
+    import torch
+    ncol, nlay, cloud = int(d["ncol"]), int(d["nlay"]), int(cloud)
+    for k in out:
+        if k not in _SOLVE_OUT:
+            raise ValueError(f"unknown output {k!r}: one of {_SOLVE_OUT}")
+    idrv = (1 if out.get("duflx_dt") is not None else 0) if idrv is None else int(idrv)
+    in_shapes, out_shapes = _solve_shapes(ncol, nlay)
+    needed = _solve_needed(cloud, idrv)
+
+    def ok(k, t, shape):
+        if k == "submask":
+            if t.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                raise TypeError(f"'submask' is {t.dtype}: 32-bit words (torch.int32 or torch.uint32)")
+        elif t.dtype != torch.float64:
+            raise TypeError(f"solve: {k!r} is {t.dtype}: torch.float64")
+        need, s = [], 1
+        for n in shape:
+            need.append(s)
+            s *= n
+        if not t.is_cuda or tuple(t.shape) != tuple(shape) or any(n > 1 and a != b for n, a, b in zip(shape, t.stride(), need)):
+            raise ValueError(f"solve: {k!r} has shape {tuple(t.shape)} and strides {tuple(t.stride())}: needs a CUDA tensor of shape {tuple(shape)} with strides {tuple(need)}")
+        return t
+
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    args = [C.c_int(ncol), C.c_int(nlay), C.c_int(cloud), C.c_int(idrv)]
+    for k in _SOLVE_IN:
+        if k in needed and d.get(k) is None:
+            raise ValueError(f"solve: input {k!r} is missing")
+        args.append(ptr(ok(k, d[k], in_shapes[k]) if k in needed else None))
+    args += [ptr(ok(k, out[k], out_shapes[k]) if out.get(k) is not None else None) for k in _SOLVE_OUT] + [C.c_void_p(stream or 0)]
+    _check(lib().rrtmg_lw_hip_solve_device(*args))
+
+
 def run_columns_mcica(cols, subs, istart=1, iend=16, icld=None, idrv=None):
     """Prepared-column McICA entry: cols[k] (rrtmg_lw_amd.io_rrtm.read_input_rrtm dicts) with sub-columns subs[k] =
     dict(cldfmc, taucmc, ciwpmc, clwpmc (140, nlayers), reicmc, relqmc (nlayers)); one (column, sample) pair per entry.

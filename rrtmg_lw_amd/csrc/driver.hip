@@ -4694,6 +4694,94 @@ int cloud_optics_device(const rrtmg_lw_hip_array_form &f, int ncol, int nlay, in
     return cloud_optics_launch(f, ncol, nlay, ld, imca, inflag, iceflag, liqflag, in, o, (hipStream_t)stream);
 }
 
+// ---- the solver on the caller's optical depths and sources (rrtmg_lw_hip_solve*, k_solve / k_solve_flux) -----------------------------------
+// rtrn's / rtrnmc's level loops in float64 by two kernels of their own; the one piece of workspace is the per-band partial sums of a
+// column batch, at the head of the *_as staging buffer (G.form_buf).
+struct SolveIn { const double *plev, *emis, *tau, *fracs, *planklay, *planklev, *plankbnd, *dplankbnd_dt, *cldfr, *odcld; const unsigned *submask; };
+struct SolveOut { double *uflx, *dflx, *hr, *uflxc, *dflxc, *hrc, *duflx_dt, *duflxc_dt; };
+
+// what both entries check, in this order, before anything is allocated or enqueued (the pointers: the caller's, host or device)
+int check_solve(int ncol, int nlay, int cloud, int idrv, const SolveIn &in, const SolveOut &o)
+{
+    if (int rc = check_common(ncol, nlay)) return rc;
+    if (cloud < 0 || cloud > 2) return fail(RRTMG_LW_HIP_EARG, "solve: cloud = %d - 0 (none), 1 (rtrn: cldfr, odcld) or 2 (rtrnmc: submask, odcld)", cloud);
+    if (idrv != 0 && idrv != 1) return fail(RRTMG_LW_HIP_EARG, "solve: idrv = %d - 0 or 1", idrv);
+    struct Range { const char *name; const void *p; size_t bytes; bool need; };
+    const size_t n = (size_t)ncol, L = (size_t)nlay;
+    const size_t lay = n * L * 8, lev = n * (L + 1) * 8, bnd = n * NBND * 8;
+    const Range ins[] = {{"plev", in.plev, lev, true}, {"emis", in.emis, bnd, true}, {"tau", in.tau, lay * NGPT, true}, {"fracs", in.fracs, lay * NGPT, true},
+                         {"planklay", in.planklay, lay * NBND, true}, {"planklev", in.planklev, lev * NBND, true}, {"plankbnd", in.plankbnd, bnd, true},
+                         {"dplankbnd_dt", in.dplankbnd_dt, bnd, idrv == 1}, {"cldfr", in.cldfr, lay, cloud == 1}, {"odcld", in.odcld, lay * NBND, cloud != 0},
+                         {"submask", in.submask, n * L * MASK_WORDS * sizeof(unsigned), cloud == 2}};
+    const Range outs[] = {{"uflx", o.uflx, lev, true}, {"dflx", o.dflx, lev, true}, {"hr", o.hr, lay, true}, {"uflxc", o.uflxc, lev, false},
+                          {"dflxc", o.dflxc, lev, false}, {"hrc", o.hrc, lay, false}, {"duflx_dt", o.duflx_dt, lev, idrv == 1}, {"duflxc_dt", o.duflxc_dt, lev, idrv == 1}};
+    for (const Range &i : ins)
+        if (i.need && !i.p) return fail(RRTMG_LW_HIP_EARG, "solve: null input array (%s)", i.name);
+    for (const Range &x : outs)
+        if (x.need && !x.p) return fail(RRTMG_LW_HIP_EARG, "solve: null output array (%s)", x.name);
+    if ((!o.uflxc || !o.dflxc || !o.hrc) && (o.uflxc || o.dflxc || o.hrc))
+        return fail(RRTMG_LW_HIP_EARG, "solve: uflxc, dflxc and hrc must be all null or all set (%s is null)", !o.uflxc ? "uflxc" : !o.dflxc ? "dflxc" : "hrc");
+    const auto meet = [](const Range &x, const Range &y) {
+        const uintptr_t a = (uintptr_t)x.p, b = (uintptr_t)y.p;
+        return x.p && y.p && a < b + y.bytes && b < a + x.bytes;
+    };
+    for (size_t k = 0; k < 8; k++) {
+        if (k >= 6 && idrv != 1) continue;                  // (not formed, not touched)
+        for (const Range &i : ins)
+            if (i.need && meet(outs[k], i)) return fail(RRTMG_LW_HIP_EARG, "solve: output %s overlaps input %s", outs[k].name, i.name);
+        for (size_t j = 0; j < k; j++)
+            if (meet(outs[k], outs[j])) return fail(RRTMG_LW_HIP_EARG, "solve: output %s overlaps output %s", outs[k].name, outs[j].name);
+    }
+    return 0;
+}
+
+// the slots of the per-band partials a call forms: without cloud the clear-sky stream is the total one
+int solve_slots(int cloud, int idrv, int *slot)
+{
+    const bool own = cloud != 0;
+    slot[SV_U] = 0; slot[SV_D] = 1;
+    slot[SV_UC] = own ? 2 : 0; slot[SV_DC] = own ? 3 : 1;
+    const int n = own ? 4 : 2;
+    slot[SV_DU] = idrv == 1 ? n : -1;
+    slot[SV_DUC] = idrv == 1 ? (own ? n + 1 : n) : -1;
+    return n + (idrv == 1 ? (own ? 2 : 1) : 0);
+}
+
+// ncol columns on stream s from DEVICE arrays ld columns wide, in batches of at most nbmax columns; checked (check_solve), the caller holds
+// the entry lock
+int solve_launch(int ncol, int nlay, int ld, int nbmax, int cloud, int idrv, const SolveIn &in, const SolveOut &o, hipStream_t s)
+{
+    if (int rc = ensure_pipeline()) return rc;
+    SolveArgs a{};
+    const int nslot = solve_slots(cloud, idrv, a.slot);
+    const size_t L = (size_t)nlay, nbm = (size_t)std::min(ncol, nbmax);
+    if (int rc = ensure_form(G.form_buf, (size_t)nslot * NBND * (L + 1) * nbm * 8)) return rc;
+    if (G.ev_last_valid) HIP_TRY(hipStreamWaitEvent(s, G.ev_last.get(), 0));      // an earlier call, possibly on another stream, still owns the staging buffer
+    a.part = G.form_buf.as<double>();
+    a.ld = (unsigned long long)ld; a.nlay = nlay; a.cloud = cloud;
+    for (size_t c0 = 0; c0 < (size_t)ncol; c0 += nbm) {
+        const size_t nb = std::min(nbm, (size_t)ncol - c0);
+        const auto at = [&](const double *p) { return p ? p + c0 : nullptr; };
+        a.plev = at(in.plev); a.emis = at(in.emis); a.tau = at(in.tau); a.fracs = at(in.fracs); a.planklay = at(in.planklay); a.planklev = at(in.planklev);
+        a.plankbnd = at(in.plankbnd); a.dplankbnd_dt = idrv == 1 ? at(in.dplankbnd_dt) : nullptr;
+        a.cldfr = cloud == 1 ? at(in.cldfr) : nullptr; a.odcld = cloud != 0 ? at(in.odcld) : nullptr;
+        a.submask = cloud == 2 ? in.submask + c0 : nullptr;
+        const auto ot = [&](double *p) { return p ? p + c0 : nullptr; };
+        a.uflx = ot(o.uflx); a.dflx = ot(o.dflx); a.hr = ot(o.hr); a.uflxc = ot(o.uflxc); a.dflxc = ot(o.dflxc); a.hrc = ot(o.hrc);
+        a.duflx_dt = idrv == 1 ? ot(o.duflx_dt) : nullptr; a.duflxc_dt = idrv == 1 ? ot(o.duflxc_dt) : nullptr;
+        a.nb = (unsigned long long)nb;
+        // (one wave per workgroup: a call of one wave per 64 columns and band spreads over the CUs)
+        const dim3 grid((unsigned)((nb + 63) / 64), NBND), cgrid((unsigned)((nb + 63) / 64)), block(64);
+        if (idrv == 1) LAUNCH("k_solve<1>", (k_solve<1>), grid, block, s, G.D, a);
+        else LAUNCH("k_solve<0>", (k_solve<0>), grid, block, s, G.D, a);
+        LAUNCH("k_solve_flux", k_solve_flux, cgrid, block, s, G.D, a);
+    }
+    if (int rc = launches_ok()) return rc;
+    HIP_TRY(hipEventRecord(G.ev_last.get(), s));
+    G.ev_last_valid = true;
+    return 0;
+}
+
 }   // namespace
 
 extern "C" {
@@ -4886,6 +4974,59 @@ int rrtmg_lw_hip_cloud_optics(int ncol, int nlay, int imca, int inflglw, int ice
         if (int rc = stage_out(outs, n, col0, nb, s)) return rc;
         if (ncbands) { if (int rc = bounce_d2h(ncbands + col0, dnb, nb * sizeof(int))) return rc; }
     }
+    return 0;
+}
+
+// The solver on the caller's optical depths and sources - rtrn's / rtrnmc's level loops, fluxes and heating rates: DEVICE arrays in the
+// reference form, column batches of rrtmg_lw_hip_effective_batch(nlay) ...
+int rrtmg_lw_hip_solve_device(int ncol, int nlay, int cloud, int idrv, const double *plev, const double *emis, const double *tau, const double *fracs,
+    const double *planklay, const double *planklev, const double *plankbnd, const double *dplankbnd_dt, const double *cldfr, const double *odcld,
+    const unsigned *submask, double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc, double *duflx_dt, double *duflxc_dt,
+    void *stream)
+{
+    ENTRY_LOCK_FOR(tau);
+    const SolveIn in{plev, emis, tau, fracs, planklay, planklev, plankbnd, dplankbnd_dt, cldfr, odcld, submask};
+    const SolveOut o{uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt};
+    if (int rc = check_solve(ncol, nlay, cloud, idrv, in, o)) return rc;
+    return solve_launch(ncol, nlay, ncol, eff_batch(nlay), cloud, idrv, in, o, (hipStream_t)stream);
+}
+// ... and HOST arrays: the first device, column batches through the host-entry staging buffer (a column's values do not depend on its
+// neighbours, so the results do not depend on the batch size)
+int rrtmg_lw_hip_solve(int ncol, int nlay, int cloud, int idrv, const double *plev, const double *emis, const double *tau, const double *fracs,
+    const double *planklay, const double *planklev, const double *plankbnd, const double *dplankbnd_dt, const double *cldfr, const double *odcld,
+    const unsigned *submask, double *uflx, double *dflx, double *hr, double *uflxc, double *dflxc, double *hrc, double *duflx_dt, double *duflxc_dt)
+{
+    ENTRY_LOCK;
+    if (int rc = check_solve(ncol, nlay, cloud, idrv, {plev, emis, tau, fracs, planklay, planklev, plankbnd, dplankbnd_dt, cldfr, odcld, submask},
+                             {uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt})) return rc;
+    HIP_TRY(hipDeviceSynchronize());      // asynchronous device-entry work of earlier calls shares the staging
+    const size_t n = (size_t)ncol, L = (size_t)nlay;
+    const bool dt = idrv == 1, clr = uflxc != nullptr;
+    const auto in = [](const double *p, bool on, size_t rows) { return HostIn{on ? p : nullptr, 1, rows, nullptr}; };
+    std::vector<HostIn> ins = {in(plev, true, L + 1), in(emis, true, NBND), in(tau, true, L * NGPT), in(fracs, true, L * NGPT), in(planklay, true, L * NBND),
+                               in(planklev, true, (L + 1) * NBND), in(plankbnd, true, NBND), in(dplankbnd_dt, dt, NBND), in(cldfr, cloud == 1, L),
+                               in(odcld, cloud != 0, L * NBND)};
+    // (submask: 32-bit words, MW per column and layer, in 8-byte slots of the staging; copied in by hand below - no host pointer for stage_out)
+    const size_t mrows = L * MASK_WORDS;
+    std::vector<HostOut> outs = {HostOut{uflx, L + 1, nullptr, true}, HostOut{dflx, L + 1, nullptr, true}, HostOut{hr, L, nullptr, true},
+                                 HostOut{uflxc, clr ? L + 1 : 0, nullptr, clr}, HostOut{dflxc, clr ? L + 1 : 0, nullptr, clr}, HostOut{hrc, clr ? L : 0, nullptr, clr},
+                                 HostOut{duflx_dt, dt ? L + 1 : 0, nullptr, dt}, HostOut{duflxc_dt, dt ? L + 1 : 0, nullptr, dt},
+                                 HostOut{nullptr, cloud == 2 ? (mrows + 1) / 2 : 0, nullptr, false}};
+    const int nbmax = balanced_batch(ncol, std::min(eff_batch(nlay), HOST_BATCH));
+    if (int rc = stage_alloc(ins, outs, (size_t)nbmax)) return rc;
+    hipStream_t s = G.stream.get();
+    for (size_t col0 = 0; col0 < n; col0 += (size_t)nbmax) {
+        const size_t nb = std::min((size_t)nbmax, n - col0);
+        if (int rc = stage_in(ins, n, col0, nb, s)) return rc;
+        unsigned *const dmask = cloud == 2 ? reinterpret_cast<unsigned *>(outs[8].d) : nullptr;
+        if (dmask) { if (int rc = bounce_h2d_rows(dmask, submask + col0, nb * sizeof(unsigned), n * sizeof(unsigned), mrows)) return rc; }
+        const auto od = [&](int k) { return outs[k].active ? outs[k].d : nullptr; };
+        if (int rc = solve_launch((int)nb, nlay, (int)nb, (int)nb, cloud, idrv,
+                                  {ins[0].d, ins[1].d, ins[2].d, ins[3].d, ins[4].d, ins[5].d, ins[6].d, ins[7].d, ins[8].d, ins[9].d, dmask},
+                                  {od(0), od(1), od(2), od(3), od(4), od(5), od(6), od(7)}, s)) return rc;
+        if (int rc = stage_out(outs, n, col0, nb, s)) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }
 

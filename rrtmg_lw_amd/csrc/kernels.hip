@@ -26,6 +26,8 @@
 //   k_subcol_* McICA sub-column generator (bit masks), k_alpha           see the section below
 //   k_cloudcover  the generator's masks counted: total, cumulative and per-layer cloud cover, the mask itself    1 thread / column
 //   k_cloudoptics_col / k_cloudoptics   cldprop / cldprmc as OUTPUTS: band optical depths before the secant, ncbands, secdiff    1 thread / column, / (column, layer)
+//   k_solve / k_solve_flux   rtrn / rtrnmc on the CALLER's optical depths and sources, float64 tables, no cell codes (rrtmg_lw_hip_solve*)
+//                                                                       1 thread / (column, band), 1 thread / column
 //
 // Reference lines are cited per routine.  No CPU fallback exists anywhere in this file.
 #include <hip/hip_runtime.h>
@@ -5263,6 +5265,300 @@ __global__ __launch_bounds__(256) void k_form_out(const FormTable t)          //
         const unsigned c = ty + 4u * it, col = ct * FORM_TILE + c, j = jt * FORM_TILE + lane;
         if (col >= nb || j >= R) continue;
         form_store<T>(e.user, (col0 + col) * (unsigned long long)R + j, tile[lane][c]);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_solve / k_solve_flux : rrtmg_lw_hip_solve* - fluxes and heating rates from the CALLER's optical depths and sources: the level loops
+//               of rtrn (cloud = 1, src/rrtmg_lw_rtrn.f90:361-540) and rtrnmc (cloud = 2, src/rrtmg_lw_rtrnmc.f90) in float64 on the float64
+//               tables (T.sl.lut {exp_tbl, tfn_tbl}, T.sl.tau_tbl), every operation rounding on its own (contract(off)).  Kernels of their
+//               own: no cell codes, nothing shared with k_sweepc / k_sweepz / k_layer.
+//   k_solve       one thread per (column, band), lanes = consecutive columns (every load a coalesced row), blockIdx.y = band.  A thread
+//               takes its band's g-points four at a time (SOLVE_CHUNK: their radiances stay in registers; all sixteen at once spilt)
+//               down and up through the levels and adds each level's sum over the chunk to the band's partial, which it alone
+//               touches.  Nothing indexed by level is kept: the upward sweep reads tau and fracs again and forms atrans, atot and the
+//               source terms again - the same numbers - (2 x 16 B per cell and sweep) rather than writing and reading four values
+//               per cell (64 B).  A column's lanes exchange nothing.
+//   k_solve_flux  one thread per column: the band sum (x wtdiff x delwave, then x fluxfac - rtrn :549-604), net fluxes, heating rates.
+//   Element offsets are 64-bit throughout (size_t): ncol x nlay x NG passes 2^31.  Threads past the batch's last column return first.
+// ------------------------------------------------------------------------------------------------
+struct SolveArgs {
+    const double *plev, *emis, *tau, *fracs, *planklay, *planklev, *plankbnd, *dplankbnd_dt, *cldfr, *odcld;    // the caller's, at the batch's first column
+    const unsigned *submask;
+    double *uflx, *dflx, *hr, *uflxc, *dflxc, *hrc, *duflx_dt, *duflxc_dt;                                      // (k_solve_flux)
+    double *part;                       // [SV_N][16][nlay + 1][nb]  sums over a band's g-points; the slots a call does not form are not there
+    unsigned long long nb, ld;          // columns of the batch, column extent of the caller's arrays
+    int nlay, cloud;
+    int slot[6];                        // where u, d, uc, dc, du, duc lie in `part` (clear = total where the streams coincide), -1: not formed
+};
+enum { SV_U, SV_D, SV_UC, SV_DC, SV_DU, SV_DUC };
+
+// what rtrn forms of one cell: the gas and total absorptivities and the Planck source terms towards both interfaces
+struct SolveCell { double atrans, atot, bbd, bbdtot, bbugas, bbutot, gassrc; };
+
+// table position of an optical depth: lut_index, kept inside the table whatever the value (a non-finite one poisons the cell instead)
+__device__ __forceinline__ int solve_index(double od, double bpade)
+{
+    const int i = lut_index(od, bpade);
+    return i < 0 ? 0 : i > 10000 ? 10000 : i;
+}
+
+__device__ __forceinline__ SolveCell solve_cell(const double *__restrict__ lut, const double *__restrict__ tau_tbl, double bpade, bool cldy,
+                                                double odepth, double odc, double plfrac, double blay, double dplankup, double dplankdn)
+{
+#pragma clang fp contract(off)
+    const double rec_6 = 0.166667;
+    SolveCell c;
+    const double poison = (odepth - odepth) + (odc - odc);      // 0, or NaN where an optical depth is infinite or NaN: it has no table position
+    if (odepth < 0.0) odepth = 0.0;
+    if (cldy) {
+        double odtot = odepth + odc;
+        if (odtot < 0.06) {
+            c.atrans = odepth - 0.5 * odepth * odepth;
+            const double odepth_rec = rec_6 * odepth;
+            c.bbd = plfrac * (blay + dplankdn * odepth_rec);
+            c.gassrc = c.bbd * c.atrans;
+            c.atot = odtot - 0.5 * odtot * odtot;
+            const double odtot_rec = rec_6 * odtot;
+            c.bbdtot = plfrac * (blay + dplankdn * odtot_rec);
+            c.bbugas = plfrac * (blay + dplankup * odepth_rec);
+            c.bbutot = plfrac * (blay + dplankup * odtot_rec);
+        } else if (odepth <= 0.06) {
+            c.atrans = odepth - 0.5 * odepth * odepth;
+            const double odepth_rec = rec_6 * odepth;
+            c.bbd = plfrac * (blay + dplankdn * odepth_rec);
+            c.gassrc = c.bbd * c.atrans;
+            const int ittot = solve_index(odtot, bpade);
+            const double tfactot = lut[2 * ittot + 1];
+            c.bbdtot = plfrac * (blay + tfactot * dplankdn);
+            c.atot = 1. - lut[2 * ittot];
+            c.bbugas = plfrac * (blay + dplankup * odepth_rec);
+            c.bbutot = plfrac * (blay + tfactot * dplankup);
+        } else {
+            const int itgas = solve_index(odepth, bpade);
+            odepth = tau_tbl[itgas];
+            c.atrans = 1. - lut[2 * itgas];
+            const double tfacgas = lut[2 * itgas + 1];
+            c.gassrc = c.atrans * plfrac * (blay + tfacgas * dplankdn);
+            odtot = odepth + odc;
+            const int ittot = solve_index(odtot, bpade);
+            const double tfactot = lut[2 * ittot + 1];
+            c.bbdtot = plfrac * (blay + tfactot * dplankdn);
+            c.bbd = plfrac * (blay + tfacgas * dplankdn);
+            c.atot = 1. - lut[2 * ittot];
+            c.bbugas = plfrac * (blay + tfacgas * dplankup);
+            c.bbutot = plfrac * (blay + tfactot * dplankup);
+        }
+    } else {
+        c.atot = 0.0; c.bbdtot = 0.0; c.bbutot = 0.0; c.gassrc = 0.0;
+        if (odepth <= 0.06) {
+            c.atrans = odepth - 0.5 * odepth * odepth;
+            odepth = rec_6 * odepth;
+            c.bbd = plfrac * (blay + dplankdn * odepth);
+            c.bbugas = plfrac * (blay + dplankup * odepth);
+        } else {
+            const int itr = solve_index(odepth, bpade);
+            c.atrans = 1. - lut[2 * itr];
+            const double tausfac = lut[2 * itr + 1];
+            c.bbd = plfrac * (blay + tausfac * dplankdn);
+            c.bbugas = plfrac * (blay + tausfac * dplankup);
+        }
+    }
+    if (poison != 0.0) c.atrans = poison;
+    return c;
+}
+
+// the cloud terms of a level: rtrn's per layer, rtrnmc's per g-point from the sub-column mask (solve_bit)
+struct SolveCloud { bool cldy; double cf, odc, efc; };
+__device__ __forceinline__ SolveCloud solve_cloud(const SolveArgs &a, size_t i, int k, int b)
+{
+#pragma clang fp contract(off)
+    SolveCloud c{};
+    if (a.cloud == 0) return c;
+    const size_t ld = (size_t)a.ld, L = (size_t)a.nlay;
+    if (a.cloud == 1) {
+        c.cf = a.cldfr[i + ld * (size_t)k];
+        c.cldy = c.cf >= 1.e-6;
+    } else {
+        unsigned any = 0;
+#pragma unroll
+        for (int w = 0; w < MASK_WORDS; w++) {
+            unsigned m = a.submask[i + ld * ((size_t)k + L * (size_t)w)];
+            if (w == MASK_WORDS - 1 && (NGPT & 31) != 0) m &= (1u << (NGPT & 31)) - 1u;
+            any |= m;
+        }
+        c.cldy = any != 0;
+        c.cf = 1.0;
+    }
+    if (c.cldy) {
+        c.odc = a.odcld[i + ld * ((size_t)k + L * (size_t)b)];
+        c.efc = (1. - exp(-c.odc)) * c.cf;
+    }
+    return c;
+}
+// bit g of the mask of (column i, layer k): g < NGPT
+__device__ __forceinline__ bool solve_bit(const SolveArgs &a, size_t i, int k, int g)
+{
+    return ((a.submask[i + (size_t)a.ld * ((size_t)k + (size_t)a.nlay * (size_t)(g >> 5))] >> (g & 31)) & 1u) != 0;
+}
+
+constexpr int SOLVE_CHUNK = 4;          // g-points a thread carries through the levels at a time
+
+template <int IDRV>
+__global__ __launch_bounds__(64) void k_solve(const DevTables T, const SolveArgs a)
+{
+#pragma clang fp contract(off)
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= (size_t)a.nb) return;
+    const int b = blockIdx.y, nlay = a.nlay;
+    const int ng = T.band[b].ng, g0 = T.band[b].gstart;
+    const size_t ld = (size_t)a.ld, L = (size_t)nlay, nb = (size_t)a.nb, nlev = L + 1;
+    const double *__restrict__ lut = T.stat + T.sl.lut;
+    const double *__restrict__ tau_tbl = T.stat + T.sl.tau_tbl;
+    const double bpade = T.bpade;
+    const bool mc = a.cloud == 2;
+    const bool clr = a.slot[SV_DC] >= 0 && a.slot[SV_DC] != a.slot[SV_D];      // a clear-sky stream of its own
+    constexpr int CH = SOLVE_CHUNK, ND = IDRV ? CH : 1;
+    const double plankbnd = a.plankbnd[i + ld * (size_t)b], reflect = 1. - a.emis[i + ld * (size_t)b];
+    const double dplankbnd = IDRV ? a.dplankbnd_dt[i + ld * (size_t)b] : 0.0;
+
+    // The band's g-points CH at a time, each chunk down and up through all levels; a level's sum over the chunk is added to the band's
+    // partial, which only this thread touches (the first chunk stores): the order of the sum is fixed, a column's lanes exchange nothing.
+    for (int j0 = 0; j0 < ng; j0 += CH) {
+        const bool first = j0 == 0;
+        const auto put = [&](int v, size_t lev, double x) {
+            double *p = a.part + (((size_t)a.slot[v] * NBND + (size_t)b) * nlev + lev) * nb + i;
+            *p = first ? x : *p + x;
+        };
+        double radld[CH], radclrd[CH];
+#pragma unroll
+        for (int j = 0; j < CH; j++) { radld[j] = 0.0; radclrd[j] = 0.0; }
+        bool iclddn = false;
+        if (first) { put(SV_D, L, 0.0); if (clr) put(SV_DC, L, 0.0); }
+        for (int lev = nlay; lev >= 1; lev--) {                     // rtrn :361-466
+            const int k = lev - 1;
+            const double blay = a.planklay[i + ld * ((size_t)k + L * (size_t)b)];
+            const double dplankup = a.planklev[i + ld * ((size_t)lev + nlev * (size_t)b)] - blay;
+            const double dplankdn = a.planklev[i + ld * ((size_t)k + nlev * (size_t)b)] - blay;
+            const SolveCloud cl = solve_cloud(a, i, k, b);
+            if (cl.cldy) iclddn = true;
+            double sd = 0.0, sdc = 0.0;
+#pragma unroll
+            for (int j = 0; j < CH; j++) {
+                if (j0 + j < ng) {
+                    const int g = g0 + j0 + j;
+                    const size_t at = i + ld * ((size_t)k + L * (size_t)g);
+                    const bool bit = !mc || (cl.cldy && solve_bit(a, i, k, g));
+                    const double cf = bit ? cl.cf : 0.0, odc = bit ? cl.odc : 0.0, efc = bit ? cl.efc : 0.0;
+                    const SolveCell c = solve_cell(lut, tau_tbl, bpade, cl.cldy, a.tau[at], odc, a.fracs[at], blay, dplankup, dplankdn);
+                    if (cl.cldy) radld[j] = radld[j] - radld[j] * (c.atrans + efc * (1. - c.atrans)) + c.gassrc + cf * (c.bbdtot * c.atot - c.gassrc);
+                    else radld[j] = radld[j] + (c.bbd - radld[j]) * c.atrans;
+                    sd = sd + radld[j];
+                    if (iclddn) radclrd[j] = radclrd[j] + (c.bbd - radclrd[j]) * c.atrans;
+                    else radclrd[j] = radld[j];
+                    sdc = sdc + radclrd[j];
+                }
+            }
+            put(SV_D, (size_t)k, sd);
+            if (clr) put(SV_DC, (size_t)k, sdc);
+        }
+        // the surface, rtrn :476-495
+        double radlu[CH], radclru[CH], dlu[ND], dclru[ND];
+        {
+            double su = 0.0, suc = 0.0, sdu = 0.0;
+#pragma unroll
+            for (int j = 0; j < CH; j++) {
+                radlu[j] = 0.0; radclru[j] = 0.0;
+                if (IDRV) { dlu[IDRV ? j : 0] = 0.0; dclru[IDRV ? j : 0] = 0.0; }
+                if (j0 + j < ng) {
+                    const double f1 = a.fracs[i + ld * (L * (size_t)(g0 + j0 + j))];
+                    const double rad0 = f1 * plankbnd;
+                    radlu[j] = rad0 + reflect * radld[j];
+                    radclru[j] = rad0 + reflect * radclrd[j];
+                    su = su + radlu[j];
+                    suc = suc + radclru[j];
+                    if (IDRV) { dlu[IDRV ? j : 0] = f1 * dplankbnd; dclru[IDRV ? j : 0] = dlu[IDRV ? j : 0]; sdu = sdu + dlu[IDRV ? j : 0]; }
+                }
+            }
+            put(SV_U, 0, su);
+            if (clr) put(SV_UC, 0, suc);
+            if (IDRV) { put(SV_DU, 0, sdu); if (clr) put(SV_DUC, 0, sdu); }
+        }
+        for (int lev = 1; lev <= nlay; lev++) {                     // rtrn :497-540
+            const int k = lev - 1;
+            const double blay = a.planklay[i + ld * ((size_t)k + L * (size_t)b)];
+            const double dplankup = a.planklev[i + ld * ((size_t)lev + nlev * (size_t)b)] - blay;
+            const double dplankdn = a.planklev[i + ld * ((size_t)k + nlev * (size_t)b)] - blay;
+            const SolveCloud cl = solve_cloud(a, i, k, b);
+            double su = 0.0, suc = 0.0, sdu = 0.0, sduc = 0.0;
+#pragma unroll
+            for (int j = 0; j < CH; j++) {
+                if (j0 + j < ng) {
+                    const int g = g0 + j0 + j;
+                    const size_t at = i + ld * ((size_t)k + L * (size_t)g);
+                    const bool bit = !mc || (cl.cldy && solve_bit(a, i, k, g));
+                    const double cf = bit ? cl.cf : 0.0, odc = bit ? cl.odc : 0.0, efc = bit ? cl.efc : 0.0;
+                    const SolveCell c = solve_cell(lut, tau_tbl, bpade, cl.cldy, a.tau[at], odc, a.fracs[at], blay, dplankup, dplankdn);
+                    if (cl.cldy) {
+                        const double gassrc = c.bbugas * c.atrans;
+                        radlu[j] = radlu[j] - radlu[j] * (c.atrans + efc * (1. - c.atrans)) + gassrc + cf * (c.bbutot * c.atot - gassrc);
+                        if (IDRV) dlu[IDRV ? j : 0] = dlu[IDRV ? j : 0] * cf * (1.0 - c.atot) + dlu[IDRV ? j : 0] * (1.0 - cf) * (1.0 - c.atrans);
+                    } else {
+                        radlu[j] = radlu[j] + (c.bbugas - radlu[j]) * c.atrans;
+                        if (IDRV) dlu[IDRV ? j : 0] = dlu[IDRV ? j : 0] * (1.0 - c.atrans);
+                    }
+                    su = su + radlu[j];
+                    if (iclddn) radclru[j] = radclru[j] + (c.bbugas - radclru[j]) * c.atrans;
+                    else radclru[j] = radlu[j];
+                    suc = suc + radclru[j];
+                    if (IDRV) {
+                        sdu = sdu + dlu[IDRV ? j : 0];
+                        if (iclddn) dclru[IDRV ? j : 0] = dclru[IDRV ? j : 0] * (1.0 - c.atrans);
+                        else dclru[IDRV ? j : 0] = dlu[IDRV ? j : 0];
+                        sduc = sduc + dclru[IDRV ? j : 0];
+                    }
+                }
+            }
+            put(SV_U, (size_t)lev, su);
+            if (clr) put(SV_UC, (size_t)lev, suc);
+            if (IDRV) { put(SV_DU, (size_t)lev, sdu); if (clr) put(SV_DUC, (size_t)lev, sduc); }
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_solve_flux(const DevTables T, const SolveArgs a)
+{
+#pragma clang fp contract(off)
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= (size_t)a.nb) return;
+    const size_t ld = (size_t)a.ld, nb = (size_t)a.nb, nlev = (size_t)a.nlay + 1;
+    const double wtdiff = 0.5;
+    const bool clear = a.uflxc != nullptr, deriv = a.slot[SV_DU] >= 0;
+    double netp = 0.0, netcp = 0.0, pp = 0.0;
+    for (size_t lev = 0; lev < nlev; lev++) {
+        double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int q = 0; q < 6; q++) {
+            if (a.slot[q] < 0 || (!clear && (q == SV_UC || q == SV_DC))) continue;
+            const double *p = a.part + ((size_t)a.slot[q] * NBND * nlev + lev) * nb + i;
+            for (int b = 0; b < NBND; b++) {
+                const double f = p[(size_t)b * nlev * nb] * wtdiff;
+                if (q >= SV_DU) v[q] = v[q] + f * T.delwave[b] * T.fluxfac;      // rtrn :566-574
+                else v[q] = v[q] + f * T.delwave[b];                             // rtrn :549-562
+            }
+            if (q < SV_DU) v[q] = v[q] * T.fluxfac;                              // rtrn :580-596
+        }
+        const size_t o = i + ld * lev;
+        const double p = a.plev[o];
+        a.uflx[o] = v[SV_U]; a.dflx[o] = v[SV_D];
+        const double net = v[SV_U] - v[SV_D], netc = v[SV_UC] - v[SV_DC];
+        if (clear) { a.uflxc[o] = v[SV_UC]; a.dflxc[o] = v[SV_DC]; }
+        if (deriv) { a.duflx_dt[o] = v[SV_DU]; a.duflxc_dt[o] = v[SV_DUC]; }
+        if (lev > 0) {                                                          // rtrn :597-604
+            a.hr[o - ld] = T.heatfac * (netp - net) / (pp - p);
+            if (clear) a.hrc[o - ld] = T.heatfac * (netcp - netc) / (pp - p);
+        }
+        netp = net; netcp = netc; pp = p;
     }
 }
 

@@ -20,6 +20,15 @@
 !      ncbands        (ncol)              cldprop's band count at the end of the column (16 with imca = 1)
 !      secdiff        (ncol,nbndlw)       the diffusivity secants; needs plev (ncol,nlay+1) and h2ovmr (ncol,nlay)
 !  Larger arrays (pcols > ncol) as above.  A particle size out of bounds ends the program with the reference's text (rrtmg_lw_hip_abort).
+!
+!  The solver on the caller's optical depths and sources (include/rrtmg_lw_hip.h, "The solver on the caller's optical depths and sources"):
+!      use rrtmg_lw_optics, only: rrtmg_lw_solve
+!      call rrtmg_lw_solve(ncol, nlay, cloud, plev, emis, tau, fracs, planklay, planklev, plankbnd, uflx, dflx, hr &
+!                          [, uflxc, dflxc, hrc] [, dplankbnd_dt, duflx_dt, duflxc_dt] [, cldfr] [, odcld] [, submask])
+!  tau, fracs (ncol,nlay,ngptlw); planklay, odcld (ncol,nlay,nbndlw); planklev (ncol,0:nlay,nbndlw); emis, plankbnd, dplankbnd_dt
+!  (ncol,nbndlw); cldfr (ncol,nlay); submask (ncol,nlay,(ngptlw+31)/32) default-kind C integers as rrtmg_lw_cloud_cover returns them.
+!  cloud = 0: no cloud; 1: rtrn on cldfr and odcld; 2: rtrnmc on submask and odcld.  duflx_dt present = idrv 1 (then dplankbnd_dt and
+!  duflxc_dt as well).  A host entry: larger arrays (pcols > ncol) as above, nothing outside (1:ncol, ...) is written.
       module rrtmg_lw_optics
 
       use iso_c_binding
@@ -28,9 +37,17 @@
 
       implicit none
 
-      public :: rrtmg_lw_gas_optics, rrtmg_lw_cloud_optics
+      public :: rrtmg_lw_gas_optics, rrtmg_lw_cloud_optics, rrtmg_lw_solve
 
       interface
+         function rrtmg_lw_hip_solve(ncol, nlay, cloud, idrv, plev, emis, tau, fracs, planklay, planklev, plankbnd, dplankbnd_dt, &
+               cldfr, odcld, submask, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt) bind(C, name='rrtmg_lw_hip_solve') result(rc)
+            import :: c_int, c_double, c_ptr
+            integer(c_int), value :: ncol, nlay, cloud, idrv
+            real(c_double), intent(in) :: plev(*), emis(*), tau(*), fracs(*), planklay(*), planklev(*), plankbnd(*)
+            type(c_ptr), value :: dplankbnd_dt, cldfr, odcld, submask, uflx, dflx, hr, uflxc, dflxc, hrc, duflx_dt, duflxc_dt
+            integer(c_int) :: rc
+         end function rrtmg_lw_hip_solve
          function rrtmg_lw_hip_cloud_optics(ncol, nlay, imca, inflglw, iceflglw, liqflglw, cldfr, taucld, cicewp, cliqwp, reice, reliq, &
                plev, h2ovmr, taucloud, ncbands, secdiff) bind(C, name='rrtmg_lw_hip_cloud_optics') result(rc)
             import :: c_int, c_double, c_ptr
@@ -167,6 +184,118 @@
       if (allocated(t3)) secdiff(1:ncol, 1:16) = t3
 
       end subroutine rrtmg_lw_cloud_optics
+
+      subroutine rrtmg_lw_solve &
+            (ncol    ,nlay    ,cloud   , &
+             plev    ,emis    ,tau     ,fracs   , &
+             planklay,planklev,plankbnd, &
+             uflx    ,dflx    ,hr      ,uflxc   ,dflxc   ,hrc     , &
+             dplankbnd_dt,duflx_dt,duflxc_dt, &
+             cldfr   ,odcld   ,submask)
+
+      integer(kind=im), intent(in) :: ncol, nlay
+      integer(kind=im), intent(in) :: cloud           ! 0: no cloud, 1: rtrn (cldfr, odcld), 2: rtrnmc (submask, odcld)
+      real(kind=rb), intent(in) :: plev(:,:)          ! Interface pressures (hPa, mb)       (ncol,nlay+1)
+      real(kind=rb), intent(in) :: emis(:,:)          ! Surface emissivity                  (ncol,nbndlw)
+      real(kind=rb), intent(in) :: tau(:,:,:)         ! Clear-sky optical depth along the diffusivity path (ncol,nlay,ngptlw)
+      real(kind=rb), intent(in) :: fracs(:,:,:)       ! Planck fractions                    (ncol,nlay,ngptlw)
+      real(kind=rb), intent(in) :: planklay(:,:,:)    ! (ncol,nlay,nbndlw)
+      real(kind=rb), intent(in) :: planklev(:,:,:)    ! (ncol,0:nlay,nbndlw)
+      real(kind=rb), intent(in) :: plankbnd(:,:)      ! (ncol,nbndlw)
+      real(kind=rb), intent(out), target :: uflx(:,:), dflx(:,:)                        ! (ncol,nlay+1)
+      real(kind=rb), intent(out), target :: hr(:,:)                                     ! (ncol,nlay)
+      real(kind=rb), intent(out), optional, target :: uflxc(:,:), dflxc(:,:), hrc(:,:)  ! all three or none
+      real(kind=rb), intent(in), optional :: dplankbnd_dt(:,:)                          ! (ncol,nbndlw): with duflx_dt
+      real(kind=rb), intent(out), optional, target :: duflx_dt(:,:), duflxc_dt(:,:)     ! (ncol,nlay+1): present = idrv 1
+      real(kind=rb), intent(in), optional :: cldfr(:,:)                                 ! (ncol,nlay): cloud = 1
+      real(kind=rb), intent(in), optional :: odcld(:,:,:)                               ! (ncol,nlay,nbndlw): cloud = 1, 2
+      integer(c_int), intent(in), optional :: submask(:,:,:)                            ! (ncol,nlay,(ngptlw+31)/32): cloud = 2
+
+      integer(c_int) :: rc, idrv, ng, mw
+      real(c_double), allocatable, target :: t(:,:,:)            ! the outputs' temporaries, one plane each
+      real(c_double), allocatable, target :: hd(:,:), hc(:,:), ho(:,:,:)
+      integer(c_int), allocatable, target :: hm(:,:,:)
+      type(c_ptr) :: p(8), pd, pc, po, pm
+      logical :: tmp(8)
+
+      ng = rrtmg_lw_hip_gpoints()
+      mw = (ng + 31) / 32
+      call check_extent('plev', size(plev,1), size(plev,2), ncol, nlay+1)
+      call check_extent('emis', size(emis,1), size(emis,2), ncol, 16)
+      call check_extent('plankbnd', size(plankbnd,1), size(plankbnd,2), ncol, 16)
+      call check_extent('tau', size(tau,1), size(tau,2), ncol, nlay)
+      call check_extent('fracs', size(fracs,1), size(fracs,2), ncol, nlay)
+      call check_extent('planklay', size(planklay,1), size(planklay,2), ncol, nlay)
+      call check_extent('planklev', size(planklev,1), size(planklev,2), ncol, nlay+1)
+      idrv = merge(1, 0, present(duflx_dt))
+      p = c_null_ptr; pd = c_null_ptr; pc = c_null_ptr; po = c_null_ptr; pm = c_null_ptr
+      tmp = .false.
+      allocate(t(ncol, nlay+1, 8))
+      call outl('uflx', uflx, 1, nlay+1)
+      call outl('dflx', dflx, 2, nlay+1)
+      call outl('hr', hr, 3, nlay)
+      if (present(uflxc)) call outl('uflxc', uflxc, 4, nlay+1)
+      if (present(dflxc)) call outl('dflxc', dflxc, 5, nlay+1)
+      if (present(hrc)) call outl('hrc', hrc, 6, nlay)
+      if (present(duflx_dt)) call outl('duflx_dt', duflx_dt, 7, nlay+1)
+      if (present(duflxc_dt)) call outl('duflxc_dt', duflxc_dt, 8, nlay+1)
+      if (present(dplankbnd_dt)) then
+         call check_extent('dplankbnd_dt', size(dplankbnd_dt,1), size(dplankbnd_dt,2), ncol, 16)
+         allocate(hd(ncol, 16))
+         hd = dplankbnd_dt(1:ncol, 1:16)
+         pd = c_loc(hd)
+      endif
+      if (present(cldfr)) then
+         call check_extent('cldfr', size(cldfr,1), size(cldfr,2), ncol, nlay)
+         allocate(hc(ncol, nlay))
+         hc = cldfr(1:ncol, 1:nlay)
+         pc = c_loc(hc)
+      endif
+      if (present(odcld)) then
+         call check_extent('odcld', size(odcld,1), size(odcld,2), ncol, nlay)
+         allocate(ho(ncol, nlay, 16))
+         ho = odcld(1:ncol, 1:nlay, 1:16)
+         po = c_loc(ho)
+      endif
+      if (present(submask)) then
+         call check_extent('submask', size(submask,1), size(submask,2), ncol, nlay)
+         allocate(hm(ncol, nlay, mw))
+         hm = submask(1:ncol, 1:nlay, 1:mw)
+         pm = c_loc(hm)
+      endif
+      rc = rrtmg_lw_hip_solve(int(ncol, c_int), int(nlay, c_int), int(cloud, c_int), idrv, &
+            plev(1:ncol,1:nlay+1), emis(1:ncol,1:16), tau(1:ncol,1:nlay,1:ng), fracs(1:ncol,1:nlay,1:ng), &
+            planklay(1:ncol,1:nlay,1:16), planklev(1:ncol,1:nlay+1,1:16), plankbnd(1:ncol,1:16), pd, pc, po, pm, &
+            p(1), p(2), p(3), p(4), p(5), p(6), p(7), p(8))
+      if (rc /= 0) call rrtmg_lw_hip_abort('rrtmg_lw_solve')
+      if (tmp(1)) uflx(1:ncol, 1:nlay+1) = t(:, :, 1)
+      if (tmp(2)) dflx(1:ncol, 1:nlay+1) = t(:, :, 2)
+      if (tmp(3)) hr(1:ncol, 1:nlay) = t(:, 1:nlay, 3)
+      if (tmp(4)) uflxc(1:ncol, 1:nlay+1) = t(:, :, 4)
+      if (tmp(5)) dflxc(1:ncol, 1:nlay+1) = t(:, :, 5)
+      if (tmp(6)) hrc(1:ncol, 1:nlay) = t(:, 1:nlay, 6)
+      if (tmp(7)) duflx_dt(1:ncol, 1:nlay+1) = t(:, :, 7)
+      if (tmp(8)) duflxc_dt(1:ncol, 1:nlay+1) = t(:, :, 8)
+
+      contains
+
+      ! output k, (ncol,n2): an exactly sized, contiguous actual goes across in place, a larger or strided one through plane k of t
+      ! (its first ncol x n2 elements: the C entry's layout), copied back after the call
+      subroutine outl(name, a, k, n2)
+      character(len=*), intent(in) :: name
+      real(kind=rb), intent(inout), target :: a(:,:)
+      integer, intent(in) :: k
+      integer(kind=im), intent(in) :: n2
+      call check_extent(name, size(a,1), size(a,2), ncol, n2)
+      if (size(a,1) == ncol .and. size(a,2) == n2 .and. is_contiguous(a)) then
+         p(k) = c_loc(a)
+      else
+         tmp(k) = .true.
+         p(k) = c_loc(t(1, 1, k))
+      endif
+      end subroutine outl
+
+      end subroutine rrtmg_lw_solve
 
       ! an output (n1,n2,n3): exactly sized, contiguous actuals go across in place; larger or strided ones through the temporary t,
       ! copied back after the call
